@@ -103,7 +103,31 @@ def parse():
                     help="N > 1: 'rows' = BASELINE's configuration (corpus row-sharded, RCCL all-gather + top-k merge); 'queries' = "
                          "every GPU holds the corpus and answers Q / N queries (one all-gather, no merge); 'auto' = whichever "
                          "lotus_amd.plan.pick_split projects ahead for this shape")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned - distances.npy (float32) and indices.npy "
+                         "(float64), [Q, k] - to DIR (rank 0); above 64 MB a fixed, seeded row sample, its row numbers in rows.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(np, out_dir, D, I):
+    """The (D, I) a caller of the timed path receives, as .npy files: D float32, I float64 (ids < 2^53 are exact).  Results of
+    more than DUMP_MAX_BYTES are cut to a fixed sample of rows (seeded, sorted), whose row numbers go to rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    nq, k = int(D.shape[0]), int(D.shape[1])
+    max_rows = max(1, DUMP_MAX_BYTES // (k * (4 + 8) + 8))  # + 8: the row number in rows.npy
+    if nq > max_rows:
+        rows = np.sort(np.random.default_rng(20260923).choice(nq, max_rows, replace=False))
+        sel = D.new_tensor(rows, dtype=I.dtype)
+        D, I = D[sel], I[sel]
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "distances.npy"), D.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "indices.npy"), I.cpu().numpy().astype(np.float64))
 
 
 def csrc_hash() -> str:
@@ -258,6 +282,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(np, args.dump_outputs, D, I)
 
     # ---- sanity on the result (outside the timed region) ----
     planted_at_1 = float((I[:, 0] == planted).float().mean().item())

@@ -1,5 +1,6 @@
 """Host-side pieces added in round 3: the regenerable bench inputs (SURVEY.md 8(d) recipe) and the split planner."""
 import numpy as np
+import pytest
 
 import benchdata
 from lotus_amd import plan
@@ -174,3 +175,43 @@ def test_bench_builds_the_torchrun_command_for_its_own_ranks(monkeypatch):
     assert 1024 < int(cmd[cmd.index("--master-port") + 1]) < 65536
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"] and cmd[-7].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" and int(seen["env"]["OMP_NUM_THREADS"]) >= 1
+
+
+def test_bench_dumps_the_last_steps_result_within_the_size_cap(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: the (D, I) of the last timed step as float32 / float64 .npy files, whole when small; above the cap a
+    seeded row sample that is the same from run to run, its row numbers beside it, all of it within the cap."""
+    import os
+
+    import torch
+
+    import bench
+
+    D = torch.arange(300 * 10, dtype=torch.float32).reshape(300, 10) / 7
+    I = torch.arange(300 * 10, dtype=torch.int64).reshape(300, 10) * 1_000_003
+    bench.dump_outputs(np, str(tmp_path / "all"), D, I)
+    assert sorted(os.listdir(tmp_path / "all")) == ["distances.npy", "indices.npy"]
+    d, i = np.load(tmp_path / "all" / "distances.npy"), np.load(tmp_path / "all" / "indices.npy")
+    assert d.dtype == np.float32 and i.dtype == np.float64
+    assert np.array_equal(d, D.numpy()) and np.array_equal(i, I.numpy().astype(np.float64))
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * (10 * 12 + 8))
+    for run in ("a", "b"):
+        bench.dump_outputs(np, str(tmp_path / run), D, I)
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "distances.npy"), D.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "a" / "indices.npy"), I.numpy()[r].astype(np.float64))
+    data_bytes = sum(np.load(tmp_path / "a" / f).nbytes for f in ("rows.npy", "distances.npy", "indices.npy"))
+    assert data_bytes <= bench.DUMP_MAX_BYTES
+
+
+def test_bench_rejects_zero_timed_steps(monkeypatch):
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

@@ -77,7 +77,8 @@ def test_rccl_transport_branch_runs_on_device_tensors():
     assert s == 35.0 and c == 10.0 and o == 3.5
 
 
-@pytest.mark.parametrize("gpus,split,queries,corpus", [(2, "rows", 4096, 262144), (8, "rows", 20480, 600_003), (8, "queries", 20480, 262144)])
+# (at most four ranks: with the test process itself no more than five processes have the one GPU open at a time)
+@pytest.mark.parametrize("gpus,split,queries,corpus", [(2, "rows", 4096, 262144), (4, "rows", 20480, 300_003), (4, "queries", 10240, 262144)])
 def test_bench_self_launches_its_ranks_and_prints_one_line(gpus, split, queries, corpus):
     """`python bench.py --gpus 2 ...` with no launcher around it (the form of the driver's N = 1 command): bench.py starts its
     own two ranks under torch.distributed.run, rank 0 prints the one JSON line.  Rehearsal mode (both ranks on cuda:0 over
@@ -92,9 +93,9 @@ def test_bench_self_launches_its_ranks_and_prints_one_line(gpus, split, queries,
     env = dict(os.environ, LOTUS_BENCH_REHEARSAL="1")
     for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(var, None)
-    # (r6: the EIGHT-rank forms too - the driver's N = 8 command on a one-GPU box: row split with 75 000-row shards through the
-    # chunked register-resident path and pooled thresholds, and the query split; RCCL itself cannot run here - two ranks on one
-    # device are refused - so the transport under rehearsal is gloo)
+    # (the per-rank shapes of the driver's N = 8 command on a one-GPU box, with four ranks: row split with 75 001-row shards
+    # through the chunked register-resident path and pooled thresholds, and the query split with 2 560 queries per rank; RCCL
+    # itself cannot run here - two ranks on one device are refused - so the transport under rehearsal is gloo)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
                         "--queries", str(queries), "--corpus", str(corpus), "--check-sample", "128", "--split", split],
                        env=env, cwd=root, capture_output=True, text=True, timeout=1500)

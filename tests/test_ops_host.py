@@ -233,3 +233,50 @@ def test_joined_frame_shortcut_equals_the_reference_joins():
     dup = pd.DataFrame({"q": ["a", "b"]}, index=[1, 1])
     assert ops._joined_frame(dup, pd.DataFrame({"t": ["x"]}), np.array([0]), np.array([1]), np.array([0]),
                              np.array([0.5], np.float32), "", "", "", False) is None
+
+
+def test_ops_match_the_stored_reference_frames(tmp_path):
+    """The golden frames of the reference accessors (tests/golden/frames_scenarios.json) against lotus_amd.ops + HipVS on the
+    oracle-backed test double: the scenarios of tests/test_gpu_ops.py, checked without a GPU or the reference checkout."""
+    import json
+    import os
+
+    import fake_rm
+    from lotus_amd import RM, HipVS, ops
+    from lotus_amd.cluster import kmeans
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "frames_scenarios.json")) as f:
+        gold = json.load(f)
+
+    def frame(d):
+        return pd.DataFrame(d["data"], columns=d["columns"]).set_index(d["columns"][0]).rename_axis(None)
+
+    def check(ref, got, score_col):
+        assert ref.index.tolist() == got.index.tolist()
+        assert ref.columns.tolist() == got.columns.tolist()
+        for c in ref.columns:
+            if c == score_col:
+                assert np.allclose(ref[c].astype(float), got[c].astype(float), atol=1e-5), c
+            else:
+                assert ref[c].tolist() == got[c].tolist(), c
+
+    inp = gold["inputs"]
+    be = OracleBackend()
+    rm = fake_rm.make_rm(RM)
+    vs = HipVS(backend=be)
+    df1 = pd.DataFrame({"L": inp["left"]})
+    df2 = ops.sem_index(pd.DataFrame({"R": inp["right"], "keep": np.arange(400) % 5 != 2}), "R", str(tmp_path / "r"),
+                        rm=rm, vs=vs)
+    check(frame(gold["join_full_k3"]), ops.sem_sim_join(df1, df2, "L", "R", 3, rm=rm, vs=vs), "_scores")
+    check(frame(gold["join_filtered_k4"]),
+          ops.sem_sim_join(df1, df2[df2["keep"]], "L", "R", 4, rm=rm, vs=vs, keep_index=True, score_suffix="_s"), "_scores_s")
+    check(frame(gold["search_k5"]),
+          ops.sem_search(df2, "R", "optimization geometry cooking", 5, rm=rm, vs=vs, return_scores=True),
+          "vec_scores_sim_score")
+    check(frame(gold["search_filtered_k3"]),
+          ops.sem_search(df2[df2["keep"]], "R", "harry potter history", 3, rm=rm, vs=vs, return_scores=True),
+          "vec_scores_sim_score")
+    dd = ops.sem_index(pd.DataFrame({"Text": inp["dedup"]}), "Text", str(tmp_path / "d"), rm=rm, vs=vs)
+    assert len(ops.sem_dedup(dd, "Text", 0.9, vs=vs)) == gold["dedup_kept_count"]
+    r = kmeans(fake_rm.embed(inp["dedup"]), 4, niter=8, backend=be)
+    assert (r.assign == np.array(gold["cluster_ids"])).mean() >= 0.99
