@@ -669,23 +669,6 @@ extern "C" int32_t lvs_gather_f32(const float* src, const int64_t* ids, int64_t 
 // search
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
-// lvs_flat_search_keys_hi: the same search planned over the fp16 "hi" parts only (one K segment whatever the pack modes)
-thread_local bool g_hi_only = false;
-struct HiOnlyScope {
-    HiOnlyScope() { g_hi_only = true; }
-    ~HiOnlyScope() { g_hi_only = false; }
-};
-// lvs_flat_search_keys_hi_banded: list slots beyond a per-query band below the kc-th best stay empty (LvsTileArgs::kc)
-struct BandSpec {
-    int kc;
-    float bscale, bslack;
-};
-thread_local BandSpec g_band = {0, 0.f, 0.f};
-struct BandScope {
-    BandScope(int kc, float bscale, float bslack) { g_band = BandSpec{kc, bscale, bslack}; }
-    ~BandScope() { g_band = BandSpec{0, 0.f, 0.f}; }
-};
-
 // bytes reserved for the small-batch kernel's candidate lists [ranges][nq][k]
 static inline int64_t lvs_stream_parts_bytes(int64_t nq, int k) {
     return lvs_round_up((int64_t)((lvs_tune_set("LVS_STREAM_WGS") ? LVS_STREAM_MAXWG : 256) + 8) * (nq > 0 ? nq : 1) *
@@ -712,6 +695,49 @@ struct Plan {
     int v2;  // 1: 256 x 256 geometry (k <= LVS2_KCAP, TOP1 / SCORES / RANGE); 0: 256 x 128 geometry (k > LVS2_KCAP)
     int64_t off_gtau, off_partial, off_pass, off_seed, total;
 };
+
+// The plan-derived fields of a tile-kernel launch over rows xb[0, nb) and queries xq[0, nq); every other field is zero, for
+// the caller to set those of its mode (outputs, k, thresholds, pairs).
+void tile_args(LvsTileArgs& a, const Plan& p, const void* xb, const void* xq, const float* bn, const float* qn, int64_t nb,
+               int64_t nq, int32_t metric, int64_t id_offset) {
+    memset(&a, 0, sizeof(a));
+    a.xb = xb;
+    a.xq = xq;
+    a.bn = bn;
+    a.qn = qn;
+    a.nb = nb;
+    a.nq = nq;
+    a.ldb = p.ldb;
+    a.ldq = p.ldq;
+    a.nseg = p.nseg;
+    for (int i = 0; i < 3; ++i) {
+        a.seg_q[i] = p.seg_q[i];
+        a.seg_c[i] = p.seg_c[i];
+    }
+    a.nkd = p.nkd;
+    a.nk = p.nk;
+    a.metric = metric;
+    a.ntiles = p.ntiles;
+    a.tiles_per_slab = p.tiles_per_slab;
+    a.nslab = p.nslab;
+    a.nqt = p.nqt;
+    a.bq = p.v2 ? LVS2_BQ : LVS3_BQ;
+    a.gq = p.gq;
+    a.lead_slabs = p.lead_slabs;
+    a.id_offset = id_offset;
+}
+
+// LVS_MODE_SEED over the corpus' first `tiles` tiles: one tile per slab, 256-query tiles, whatever the plan said
+void seed_tile_geometry(LvsTileArgs& a, int tiles) {
+    a.nb = (int64_t)tiles * LVS_BC;
+    a.ntiles = a.nslab = tiles;
+    a.tiles_per_slab = 1;
+    a.nqt = (int)lvs_ceil_div(a.nq, LVS2_BQ);
+    a.bq = LVS2_BQ;
+    a.gq = 1;
+    a.lead_slabs = 0;
+    a.k = 1;
+}
 
 // Seeded thresholds of a list launch.  A launch cuts the corpus into slabs that run concurrently, and a slab whose queries
 // have no threshold yet pays a cold start of ~k (1 + ln(slab rows / k)) lock-protected insertions per query: with few query
@@ -743,7 +769,8 @@ int tile_seed_tiles(int64_t nq, int64_t nb, int k) {
     return (int)tiles;
 }
 
-int make_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, int32_t k, Plan& p,
+// hi_only: plan over the fp16 "hi" parts only - one K segment whatever the pack modes (lvs_flat_search_keys_hi)
+int make_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, bool hi_only, int32_t k, Plan& p,
               bool force_v2 = false, int64_t min_slabs = 0, int64_t max_slabs_cap = 0, bool allow_l2 = true) {
     if (nq < 0 || nb < 0 || d <= 0 || k < 0) return LVS_EINVAL;
     if (xb_pack != LVS_PACK_F16 && xb_pack != LVS_PACK_SPLIT) return LVS_EINVAL;
@@ -761,8 +788,8 @@ int make_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pac
     };
     p.seg_q[0] = p.seg_q[1] = p.seg_q[2] = p.seg_c[0] = p.seg_c[1] = p.seg_c[2] = 0;
     seg(0, 0);
-    if (xb_pack == LVS_PACK_SPLIT && !g_hi_only) seg(0, p.dpad);
-    if (xq_pack == LVS_PACK_SPLIT && !g_hi_only) seg(p.dpad, 0);
+    if (xb_pack == LVS_PACK_SPLIT && !hi_only) seg(0, p.dpad);
+    if (xq_pack == LVS_PACK_SPLIT && !hi_only) seg(p.dpad, 0);
     p.nk = p.nseg * p.nkd;
     p.ntiles = (int)lvs_ceil_div(nb > 0 ? nb : 1, LVS_BC);
     // geometry: 256 queries per tile with 15 list slots (k <= 15 and every non-top-k mode), else 128 queries / 56 slots
@@ -866,7 +893,7 @@ int make_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pac
     // 100 k x 250 k 37.4 vs 38.6), and from 118 query tiles on the slabs are long anyway.
     if (slabs_l2 > 0 && p.nqt <= lvs_tune("LVS_L2_SHORT_NQT", 128) && p.tiles_per_slab < lvs_tune("LVS_L2_MIN_FINAL", 120) &&
         !lvs_tune_set("LVS_GQ") && !lvs_tune_set("LVS_NSLAB"))
-        return make_plan(nq, nb, d, xb_pack, xq_pack, k, p, force_v2, min_slabs, max_slabs_cap, false);
+        return make_plan(nq, nb, d, xb_pack, xq_pack, hi_only, k, p, force_v2, min_slabs, max_slabs_cap, false);
 #ifdef LVS_TUNING
     if (lvs_tune("LVS_PLAN_PRINT", 0) != 0)
         fprintf(stderr, "lvs plan: nq %lld nb %lld k %d -> nqt %d ntiles %d gq %d lead %d slabs %d x %d tiles, items %lld, xcd rounds %d\n",
@@ -1030,7 +1057,7 @@ struct TwoPhasePlan {
     int64_t off_thr, off_cnt, off_bucket, total;
 };
 
-bool make_two_phase_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, int32_t k,
+bool make_two_phase_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, bool hi_only, int32_t k,
                          TwoPhasePlan& tp) {
     if (k <= LVS_KPASS || nq <= 0 || nb <= 0) return false;
     if (lvs_tune("LVS_TWO_PHASE", 1) == 0) return false;
@@ -1041,11 +1068,11 @@ bool make_two_phase_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int
     const int64_t cap_slabs = LVS_SELECT_MAX / tp.slots;        // the selection kernel sorts at most 4096 keys per query
     int64_t want_slabs = lvs_ceil_div(2ll * k, tp.slots);       // ~2k candidates: a tight bound at a moderate slab count
     if (want_slabs > cap_slabs) want_slabs = cap_slabs;
-    if (make_plan(nq, nb, d, xb_pack, xq_pack, tp.slots, tp.a, tp.slots == LVS2_KCAP, want_slabs, cap_slabs) != LVS_OK)
+    if (make_plan(nq, nb, d, xb_pack, xq_pack, hi_only, tp.slots, tp.a, tp.slots == LVS2_KCAP, want_slabs, cap_slabs) != LVS_OK)
         return false;
     if ((int64_t)tp.a.nslab * tp.slots > LVS_SELECT_MAX) return false;
     if ((int64_t)tp.a.nslab * tp.slots < (int64_t)k + k / 4) return false;  // corpus too small for a useful bound
-    if (make_plan(nq, nb, d, xb_pack, xq_pack, LVS2_KCAP, tp.b, true) != LVS_OK) return false;
+    if (make_plan(nq, nb, d, xb_pack, xq_pack, hi_only, LVS2_KCAP, tp.b, true) != LVS_OK) return false;
     tp.capacity = pow2_ceil(2 * k < 512 ? 512 : 2 * k);
     if (tp.capacity > LVS_SELECT_MAX) tp.capacity = LVS_SELECT_MAX;
     if (tp.capacity < k) return false;
@@ -1116,27 +1143,421 @@ __global__ void copy_pass_kernel(const u64* __restrict__ src, long long nq, int 
     int j = (int)(i - q * kp);
     if (col0 + j < k) dst[q * k + col0 + j] = src[i];
 }
+
+// gtau[q] = order key of the k-th largest of seeds[p][q], p < nparts, for every query q < nq (seed_kth_kernel)
+hipError_t launch_seed_kth(const float* seeds, int nparts, int64_t nq, int k, uint32_t* gtau, hipStream_t st, int kc = 0,
+                           const float* qn = nullptr, float bscale = 0.f, float bslack = 0.f) {
+    hipLaunchKernelGGL(seed_kth_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, seeds, nparts, (long long)nq, k,
+                       gtau, kc, qn, bscale, bslack);
+    return hipGetLastError();
+}
+
+// out[q * out_ld + 0..k) = the best k keys of the nparts partial lists [nparts][nq][k] of every query q < nq.  wide: one
+// workgroup of 16 waves per query (merge_keys_wide_kernel, never predicated); else one wave per query (merge_keys_kernel).
+hipError_t launch_merge(bool wide, const u64* parts, int nparts, int64_t nq, int k, u64* out, long long out_ld,
+                        const uint32_t* pred, hipStream_t st) {
+    if (wide)
+        hipLaunchKernelGGL(merge_keys_wide_kernel, dim3((unsigned)nq), dim3(1024), 0, st, parts, nparts, (long long)nq, k, out,
+                           out_ld);
+    else
+        hipLaunchKernelGGL(merge_keys_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, parts, nparts,
+                           (long long)nq, k, out, out_ld, pred);
+    return hipGetLastError();
+}
+
+// Chunked calls of lvs_rq_kernel / lvs_rj_kernel: a chunk is 4 096 queries (16 groups x 16 corpus ranges) or 8 192 x 2^i
+// (32 / 64 / 128 / 256 groups x 8 / 4 / 2 / 1 ranges: a multiple of 32 groups - lvs_rq_item), the largest such size up to
+// `want`; what is left at the end goes out in launches of 8 192, 4 096 and one of <= 4 096 queries (rq_chunk_len).
+int64_t rq_chunk_size(int64_t want) {
+    int64_t c = LVS_RQ_MAXQ;
+    while (2 * c <= want && 2 * c <= LVS_RQ_CHUNK_MAX) c *= 2;
+    return c;
+}
+int64_t rq_chunk_len(int64_t left, int64_t chunk) {
+    return left >= chunk ? chunk : (left >= 8192 ? 8192 : (left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left));
+}
+
+// What a flat search does beyond its operands (the lvs_flat_search_keys variants)
+struct SearchOpts {
+    bool hi_only = false;  // lvs_flat_search_keys_hi: planned over the fp16 "hi" parts only (one K segment whatever the pack modes)
+    // lvs_flat_search_keys_hi_banded: list slots beyond a per-query band below the kc-th best stay empty (LvsTileArgs::kc)
+    int kc = 0;
+    float bscale = 0.f, bslack = 0.f;
+    // lvs_flat_search_keys_seeded (nullable): [ext_rows][nq] scores of real rows of the SEARCHED SET (any shard of it, e.g. the
+    // all-gathered sample maxima of every corpus shard of a multi-GPU join, lvs_flat_search_seed_scores): the k-th largest per
+    // query replaces the launch's own sample pass as its starting threshold.
+    const float* ext_seeds = nullptr;
+    int32_t ext_rows = 0;
+};
+
+// One flat-search call as its paths see it: the checked arguments, the plan and the workspace carved by it
+struct SearchCall {
+    const void* xb;
+    const void* xq;
+    const float* bn;  // [nb] |y|^2 (L2 only)
+    const float* qn;  // [nq] |q|^2 (L2 only)
+    int64_t nb, nq, id_offset;
+    int32_t d, metric, k, xb_pack, xq_pack;
+    const uint32_t* row_ids;
+    u64* out_keys;  // [nq][k]
+    hipStream_t st;
+    SearchOpts o;
+    Plan p;
+    char* ws;  // laid out by p
+    int64_t ws_bytes;
+    uint32_t* gtau;  // ws + p.off_gtau
+    u64* partial;    // ws + p.off_partial
+};
+
+// a tile launch of the search over its whole corpus and all its queries, on plan pl
+void search_tile_args(LvsTileArgs& a, const SearchCall& sc, const Plan& pl, uint32_t* gtau, u64* out) {
+    tile_args(a, pl, sc.xb, sc.xq, sc.bn, sc.qn, sc.nb, sc.nq, sc.metric, sc.id_offset);
+    a.row_ids = sc.row_ids;
+    a.gtau = gtau;
+    a.out = out;
+    a.debug_hot = (int)lvs_tune("LVS_DEBUG_HOT", 0);
+}
+
+// ---- k > LVS_KPASS: two corpus passes whatever k is (see make_two_phase_plan).  A bucket overflow (mass ties, or the top k
+// clustered in one slab) sets a device-side flag; the selection passes then run PREDICATED on that flag (their kernels return
+// at once when it is clear), so the call never synchronises the stream.  *pred = that flag, or NULL when the two phases did
+// not run (no two-phase plan, or a workspace too small for it).
+int32_t search_two_phase(const SearchCall& sc, const uint32_t** pred) {
+    *pred = nullptr;
+    const int64_t nq = sc.nq;
+    const int k = sc.k;
+    hipStream_t st = sc.st;
+    TwoPhasePlan tp;
+    if (!make_two_phase_plan(nq, sc.nb, sc.d, sc.xb_pack, sc.xq_pack, sc.o.hi_only, k, tp) || tp.total > sc.ws_bytes)
+        return LVS_OK;
+    char* ws = sc.ws;
+    uint32_t* gtau2 = (uint32_t*)(ws + tp.a.off_gtau);
+    u64* lists = (u64*)(ws + tp.a.off_partial);    // [nslab][nq][slots]
+    u64* thr = (u64*)(ws + tp.off_thr);            // [nq]
+    uint32_t* cnt = (uint32_t*)(ws + tp.off_cnt);  // [nq]
+    uint32_t* flag = (uint32_t*)ws;                // status word 0: some bucket overflowed
+    u64* bucket = (u64*)(ws + tp.off_bucket);      // [nq][capacity]
+    LvsTileArgs ta;
+    search_tile_args(ta, sc, tp.a, gtau2, lists);
+    ta.k = tp.slots;
+    ta.no_share = 1;  // the bound needs every slab's own top list, not lists pruned by other slabs' thresholds
+    LVS_HIP_CHECK(hipMemsetAsync(gtau2, 0, (size_t)nq * 4, st));
+    LVS_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+    LVS_HIP_CHECK(hipMemsetAsync(flag, 0, 4, st));
+    {
+        ScopedKernelTimer timer(st);
+        LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOPK, ta, st));
+    }
+    // T[q] = k-th largest of the nslab * slots listed keys (element (slab, j) of query q at (slab * nq + q) * slots + j)
+    LVS_HIP_CHECK(launch_select(lists, tp.slots, tp.slots, (long long)nq * tp.slots, tp.a.nslab * tp.slots, nullptr, k, thr,
+                                nullptr, 0, nullptr, nq, st));
+    LvsTileArgs tb;
+    search_tile_args(tb, sc, tp.b, gtau2, lists);
+    tb.k = 1;
+    tb.thr_key = thr;
+    tb.bucket_count = cnt;
+    tb.bucket = bucket;
+    tb.bucket_capacity = tp.capacity;
+    LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_COLLECT, tb, st));
+    LVS_HIP_CHECK(launch_select(bucket, tp.capacity, tp.capacity, 0, tp.capacity, cnt, k, nullptr, sc.out_keys, k, flag, nq, st));
+    *pred = flag;
+#ifdef LVS_TUNING
+    if (lvs_tune_set("LVS_TWO_PHASE_DEBUG")) {  // bucket statistics of this call (synchronises)
+        std::vector<uint32_t> h((size_t)nq);
+        uint32_t overflowed = 0;
+        LVS_HIP_CHECK(hipStreamSynchronize(st));
+        LVS_HIP_CHECK(hipMemcpy(&overflowed, flag, 4, hipMemcpyDeviceToHost));
+        LVS_HIP_CHECK(hipMemcpy(h.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost));
+        uint32_t mn = ~0u, mx = 0;
+        double sum = 0;
+        for (uint32_t v : h) {
+            mn = v < mn ? v : mn;
+            mx = v > mx ? v : mx;
+            sum += v;
+        }
+        fprintf(stderr, "[lvs] two-phase k=%d slots=%d slabs=%d capacity=%d: bucket counts min %u mean %.1f max %u overflow=%u\n",
+                k, tp.slots, tp.a.nslab, tp.capacity, mn, sum / (double)nq, mx, overflowed);
+    }
+#endif
+    return LVS_OK;
+}
+
+// ---- lvs_rq_kernel / lvs_rj_kernel, one launch per chunk of queries (rq_chunk_size): a query belongs to one chunk, so every
+// chunk is a complete search of its own (own seeds, own lists, own merge) ----
+int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
+    const Plan& p = sc.p;
+    const int64_t nq = sc.nq, nb = sc.nb;
+    const int k = sc.k;
+    hipStream_t st = sc.st;
+    uint32_t* gtau = sc.gtau;
+    u64* partial = sc.partial;
+    const bool rq_ext_seeds = sc.o.ext_seeds && sc.o.ext_rows >= k;
+    if (rq_join && rq_ext_seeds)  // the k-th largest of the caller's sample scores, for every query of the call at once
+        LVS_HIP_CHECK(launch_seed_kth(sc.o.ext_seeds, (int)sc.o.ext_rows, nq, k, gtau, st));
+    const int64_t chunk = rq_chunk_size(lvs_tune("LVS_RQ_CHUNK", LVS_RQ_CHUNK_DEFAULT));
+    for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
+        cn = rq_chunk_len(nq - c0, chunk);
+        LvsRqArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.xb = sc.xb;
+        ra.xq = (const _Float16*)sc.xq + c0 * p.ldq;
+        ra.bn = sc.bn;
+        ra.qn = sc.qn ? sc.qn + c0 : nullptr;
+        ra.row_ids = sc.row_ids;
+        ra.gtau = gtau + c0;
+        ra.out = partial;
+        ra.nb = nb;
+        ra.ldb = p.ldb;
+        ra.ldq = p.ldq;
+        ra.id_offset = sc.id_offset;
+        ra.nq = (int)cn;
+        ra.k = k;
+        ra.metric = sc.metric;
+        // thresholds seeded from a sample of the rows scanned by this kernel's own SEED mode (bit-identical scores; see
+        // search_stream for why a caller's pooled sample scores are not used)
+        int64_t sample = nb / 8 / 1024 * 1024;
+        // (eight groups or more: a workgroup sees 30 000+ rows and fills its own lists - a quarter of the sample costs the main
+        // pass 1 % and saves 3 % of the call; profiles/r09b_rq_groups_sample_probe.log)
+        // (chunks of 16 384 queries or more see the corpus in <= 4 long ranges whose lists fill at once: half of that sample again
+        // costs the launches nothing and the sample pass half - 100 k x 1 M: call 126.0-127.8 -> 125.4-126.2 ms, same box,
+        // profiles/r12d_knobs.log)
+        const int64_t sample_cap = lvs_tune("LVS_RQ_SAMPLE", cn >= 16384 ? LVS_RQ_SEED_ROWS / 8
+                                                             : (cn > 7 * LVS_RQ_GROUPQ ? LVS_RQ_SEED_ROWS / 4 : LVS_RQ_SEED_ROWS));
+        if (sample > sample_cap) sample = sample_cap;
+        if (rq_join && rq_ext_seeds) {
+            // seeded above
+        } else if (sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0) {
+            // (the k-th largest of one maximum per corpus range needs >= k ranges: the sample pass keeps launches of <= 16 groups)
+            float* seeds = (float*)((char*)partial + lvs_rq_parts_bytes(cn, k));  // [ranges][<= 4 096]
+            for (int64_t s0 = 0; s0 < cn; s0 += LVS_RQ_MAXQ) {
+                const int64_t sn = cn - s0 < LVS_RQ_MAXQ ? cn - s0 : LVS_RQ_MAXQ;
+                LvsRqArgs rs = ra;
+                rs.xq = (const _Float16*)ra.xq + s0 * p.ldq;
+                rs.qn = ra.qn ? ra.qn + s0 : nullptr;
+                rs.gtau = ra.gtau + s0;
+                rs.nq = (int)sn;
+                rs.nb = sample;
+                rs.seed_out = seeds;
+                LVS_HIP_CHECK(lvs_rq_launch(rs, p.dpad, st));
+                LVS_HIP_CHECK(launch_seed_kth(seeds, rs.nparts, sn, k, gtau + c0 + s0, st));  // writes every gtau[q] of the piece
+            }
+        } else {
+            LVS_HIP_CHECK(hipMemsetAsync(gtau + c0, 0, (size_t)cn * 4, st));
+        }
+        // (r6) one wave per SIMD, 64 queries per wave (lvs_rj.hip) for the launches it takes: whole 32-row blocks there, the
+        // corpus' last nb % 32 rows through lvs_rq_kernel as one more list per query
+        if (lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_rj_fits(cn, nb, p.dpad, k, sc.row_ids != nullptr)) {
+            {
+                ScopedKernelTimer timer(st, LVS_KERNEL_RJ, c0 > 0);
+                LVS_HIP_CHECK(lvs_rj_launch(ra, p.dpad, st));
+            }
+            const int64_t nb_full = nb / 32 * 32;
+            if (nb_full < nb) {
+                LvsRqArgs rt = ra;
+                rt.xb = (const char*)sc.xb + nb_full * p.ldb * 2;
+                rt.bn = sc.bn ? sc.bn + nb_full : nullptr;
+                rt.nb = nb - nb_full;
+                rt.id_offset = sc.id_offset + nb_full;
+                rt.out = partial + (int64_t)ra.nparts * cn * k;
+                LVS_HIP_CHECK(lvs_rq_launch(rt, p.dpad, st));
+                ra.nparts += rt.nparts;
+            }
+        } else {
+            ScopedKernelTimer timer(st, LVS_KERNEL_RQ, c0 > 0);
+            LVS_HIP_CHECK(lvs_rq_launch(ra, p.dpad, st));
+        }
+        LVS_HIP_CHECK(launch_merge(ra.nparts >= 16, partial, ra.nparts, cn, k, sc.out_keys + c0 * k, k, nullptr, st));
+    }
+    return LVS_OK;
+}
+
+// the small-batch kernel's shape for a call (lvs_stream_plan)
+struct StreamShape {
+    int nbfrag;  // B fragments per query block: query K segments x dpad / 16
+    int kcap, nqb, groups;
+};
+
+// ---- lvs_stream_kernel: stream the corpus once, queries resident in LDS ----
+int32_t search_stream(const SearchCall& sc, const StreamShape& sh) {
+    const Plan& p = sc.p;
+    const int64_t nq = sc.nq, nb = sc.nb;
+    const int k = sc.k;
+    hipStream_t st = sc.st;
+    uint32_t* gtau = sc.gtau;
+    u64* partial = sc.partial;
+    const int jper = p.dpad / 16;
+    LvsStreamArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.xb = sc.xb;
+    sa.xq = sc.xq;
+    sa.bn = sc.bn;
+    sa.qn = sc.qn;
+    sa.row_ids = sc.row_ids;
+    sa.gtau = gtau;
+    sa.out = partial;
+    sa.nb = nb;
+    sa.ldb = p.ldb;
+    sa.ldq = p.ldq;
+    sa.id_offset = sc.id_offset;
+    sa.nq = (int)nq;
+    sa.k = k;
+    sa.metric = sc.metric;
+    sa.jper = jper;
+    sa.nseg = p.nseg;
+    sa.nj = p.nseg * jper;
+    sa.nbfrag = sh.nbfrag;
+    sa.kcap = sh.kcap;
+    sa.nqb = sh.nqb;
+    sa.groups = sh.groups;
+    for (int i = 0; i < 3; ++i) {
+        sa.seg_q[i] = p.seg_q[i];
+        sa.seg_c[i] = p.seg_c[i];
+        sa.seg_b[i] = p.seg_q[i] == 0 ? 0 : jper;
+    }
+    // Every workgroup scans its own contiguous range, all at the same time: without help each of them starts with
+    // empty lists and pays its own cold start (~k (1 + ln(range / k)) insertions per query and workgroup - with
+    // dozens of queries that, not HBM, set the time in round 2).  So with several queries the thresholds are
+    // SEEDED: the same kernel first scans a sample (the first nb / 8 rows, at most 32 768) in SEED mode - no lists,
+    // every workgroup just keeps the best score per query over its 4 row blocks - and one wave per query takes the
+    // k-th largest of those per-range maxima as the starting threshold (~15 + 5 us; round 3's first version scored the
+    // sample into a matrix with the tile kernel and radix-selected it: 130-180 us).  A workgroup of the main scan then
+    // only inserts rows that beat it (~k * nb / sample per query over the WHOLE launch).  Exact: every value is a
+    // real row's score and the k-th largest of a subset never exceeds the k-th largest of all rows; the sample
+    // rows themselves are scanned again with the rest.
+    int64_t sample = nb / 8 / 1024 * 1024;
+    if (sample > LVS_STREAM_SEED_ROWS) sample = LVS_STREAM_SEED_ROWS;
+    // A caller's pooled sample scores (ext_seeds) are NOT used here: they come from the tile kernel's SEED mode, whose
+    // accumulation order differs from this kernel's, and "the k-th largest of a subset is a lower bound" is only exact
+    // when the threshold and the scan see bit-identical scores - one ulp the wrong way could reject a true top-k row on
+    // its own shard.  This path seeds itself, with its own arithmetic.
+    if (nq >= lvs_tune("LVS_STREAM_SEED_MINQ", 2) && sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0) {
+        float* seeds = (float*)((char*)partial + lvs_stream_parts_bytes(nq, k));  // [ranges][nq]
+        LvsStreamArgs ss = sa;
+        ss.nb = sample;
+        ss.seed_out = seeds;
+        LVS_HIP_CHECK(lvs_stream_launch(ss, st));
+        LVS_HIP_CHECK(launch_seed_kth(seeds, ss.nparts, nq, k, gtau, st));  // writes every gtau[q]
+    } else {
+        LVS_HIP_CHECK(hipMemsetAsync(gtau, 0, (size_t)nq * 4, st));
+    }
+    {
+        ScopedKernelTimer timer(st, LVS_KERNEL_STREAM);
+        LVS_HIP_CHECK(lvs_stream_launch(sa, st));
+    }
+    LVS_HIP_CHECK(launch_merge(sa.nparts >= 16 && k <= 64, partial, sa.nparts, nq, k, sc.out_keys, k, nullptr, st));
+    return LVS_OK;
+}
+
+// ---- the list kernel (lvs_tile.hip): ceil(k / LVS_KPASS) passes of per-slab lists and their merge; pred (nullable): every
+// launch is a no-op unless *pred != 0 (the fallback of the two-phase search) ----
+int32_t search_list_passes(const SearchCall& sc, const uint32_t* pred) {
+    const Plan& p = sc.p;
+    const int64_t nq = sc.nq;
+    const int k = sc.k;
+    hipStream_t st = sc.st;
+    uint32_t* gtau = sc.gtau;
+    u64* partial = sc.partial;
+    u64* passbuf = (u64*)(sc.ws + p.off_pass);
+    LvsTileArgs a;
+    search_tile_args(a, sc, p, gtau, partial);
+    a.pred = pred;
+    unsigned long long* dbg_counters = nullptr;
+#if defined(LVS_COUNT_EVENTS) && defined(LVS_TUNING)
+    if (lvs_tune("LVS_COUNT", 0)) {  // tuning build only: count slow-path events of this call (allocates, synchronises)
+        LVS_HIP_CHECK(hipMalloc((void**)&dbg_counters, 8 * sizeof(unsigned long long)));
+        LVS_HIP_CHECK(hipMemsetAsync(dbg_counters, 0, 8 * sizeof(unsigned long long), st));
+        a.dbg = dbg_counters;
+    }
+#endif
+    // k == 1: the list-free per-lane running best (TOP1) wins on short streams (k-means assignment: a few corpus tiles
+    // per query, nearly every block improves some lane's best); on long streams the threshold filter of the list
+    // kernel skips almost every block, so k = 1 goes through it like any other k.  Same winner either way
+    // (best score, lowest row among equals).
+    bool use_top1 = k == 1 && !sc.row_ids && p.tiles_per_slab <= 64;
+    if (lvs_tune_set("LVS_TOP1")) use_top1 = k == 1 && !sc.row_ids && lvs_tune("LVS_TOP1", 0) != 0;  // -DLVS_TUNING only
+    for (int pass = 0; pass < p.npass; ++pass) {
+        const int col0 = pass * p.kpass;
+        const int kp = (k - col0) < p.kpass ? (k - col0) : p.kpass;
+        a.k = kp;
+        // pass > 0: only keys strictly below the last key of the previous pass take part
+        a.ub = pass == 0 ? nullptr : sc.out_keys + (col0 - 1);
+        a.ub_stride = k;
+        const bool banded = sc.o.kc > 0 && sc.o.kc < kp && p.npass == 1 && !pred && !use_top1 && sc.qn;
+        a.kc = banded ? sc.o.kc : 0;
+        a.bscale = banded ? sc.o.bscale : 0.f;
+        a.bslack = banded ? sc.o.bslack : 0.f;
+        const bool seedable = pass == 0 && p.npass == 1 && !pred && !use_top1;
+        const int seed_tiles = seedable ? tile_seed_tiles(nq, sc.nb, kp) : 0;
+        if (seedable && sc.o.ext_seeds && sc.o.ext_rows >= kp) {  // the caller's pooled sample scores (every shard's sample)
+            LVS_HIP_CHECK(launch_seed_kth(sc.o.ext_seeds, (int)sc.o.ext_rows, nq, kp, gtau, st, a.kc, sc.qn, a.bscale,
+                                          a.bslack));  // writes every gtau[q]
+        } else if (seed_tiles > 0) {  // thresholds seeded from a sample instead of cold starts (tile_seed_tiles)
+            float* seeds = (float*)(sc.ws + p.off_seed);
+            LvsTileArgs sd = a;
+            seed_tile_geometry(sd, seed_tiles);
+            sd.kc = 0;
+            sd.ub = nullptr;
+            sd.seed_out = seeds;
+            LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_SEED, sd, st));
+            LVS_HIP_CHECK(launch_seed_kth(seeds, sd.nslab, nq, kp, gtau, st, a.kc, sc.qn, a.bscale, a.bslack));  // writes every gtau[q]
+        } else {
+            LVS_HIP_CHECK(hipMemsetAsync(gtau, 0, (size_t)nq * 4, st));
+        }
+        if (pred) {  // predicated fallback pass: not a measurement of the dominant kernel
+            LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOPK, a, st));
+        } else {
+            ScopedKernelTimer timer(st);
+            LVS_HIP_CHECK(lvs_tile_launch(use_top1 ? LVS_MODE_TOP1 : LVS_MODE_TOPK, a, st));
+        }
+        if (p.npass == 1 && kp == 1) {
+            hipLaunchKernelGGL(merge_top1_kernel, dim3((unsigned)lvs_ceil_div(nq, 256)), dim3(256), 0, st, partial, p.nslab,
+                               (long long)nq, sc.out_keys, (long long)k);
+        } else if (p.npass == 1) {
+            // few queries, many slabs: one workgroup of 16 waves per query (one wave per query walks hundreds of partial
+            // lists as a chain of dependent loads: 150 us of a 0.5 ms call at 256 queries x 489 slabs)
+            const bool wide = !pred && p.nslab >= 16 && nq <= 4096;
+            LVS_HIP_CHECK(launch_merge(wide, partial, p.nslab, nq, kp, sc.out_keys, k, pred, st));
+        } else {
+            // the upper bounds of this pass live in out_keys, so merge into a side buffer first
+            LVS_HIP_CHECK(launch_merge(false, partial, p.nslab, nq, kp, passbuf, kp, pred, st));
+            hipLaunchKernelGGL(copy_pass_kernel, dim3((unsigned)lvs_ceil_div(nq * kp, 256)), dim3(256), 0, st, passbuf,
+                               (long long)nq, kp, sc.out_keys, k, col0, pred);
+        }
+        LVS_HIP_CHECK(hipGetLastError());
+    }
+    if (dbg_counters) {
+        unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        LVS_HIP_CHECK(hipStreamSynchronize(st));
+        LVS_HIP_CHECK(hipMemcpy(h, dbg_counters, sizeof(h), hipMemcpyDeviceToHost));
+        (void)hipFree(dbg_counters);
+        fprintf(stderr,
+                "[lvs] nq=%lld nb=%lld k=%d nslab=%d: wave-tiles %llu, block visits %llu, insertions %llu (%.1f per query); "
+                "cycles per wave-tile: filter %.0f, visit loop %.0f (of which insertions %.0f); per visit %.0f, per insertion %.0f\n",
+                (long long)nq, (long long)sc.nb, k, p.nslab, h[2], h[0], h[1], (double)h[1] / (double)(nq > 0 ? nq : 1),
+                (double)h[3] / (double)(h[2] ? h[2] : 1), (double)h[4] / (double)(h[2] ? h[2] : 1),
+                (double)h[5] / (double)(h[2] ? h[2] : 1), (double)(h[4] - h[5]) / (double)(h[0] ? h[0] : 1),
+                (double)h[5] / (double)(h[1] ? h[1] : 1));
+    }
+    return LVS_OK;
+}
 }  // namespace
 
 extern "C" int64_t lvs_flat_search_workspace_bytes(int64_t nq, int64_t nb, int32_t d, int32_t k, int32_t xb_pack,
                                                    int32_t xq_pack) {
     Plan p;
-    if (make_plan(nq, nb, d, xb_pack, xq_pack, k, p) != LVS_OK) return LVS_EINVAL;
+    if (make_plan(nq, nb, d, xb_pack, xq_pack, false, k, p) != LVS_OK) return LVS_EINVAL;
     TwoPhasePlan tp;
-    if (make_two_phase_plan(nq, nb, d, xb_pack, xq_pack, k, tp) && tp.total > p.total) return tp.total;
+    if (make_two_phase_plan(nq, nb, d, xb_pack, xq_pack, false, k, tp) && tp.total > p.total) return tp.total;
     return p.total;
 }
 
-// ext_seeds (nullable): [ext_rows][nq] scores of real rows of the SEARCHED SET (any shard of it, e.g. the all-gathered
-// sample maxima of every corpus shard of a multi-GPU join, lvs_flat_search_seed_scores): the k-th largest per query replaces
-// the launch's own sample pass as its starting threshold.
 static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
                                 int64_t nq, int32_t d, int32_t metric, int32_t k, const float* xb_norms_sq,
                                 const float* xq_norms_sq, int64_t id_offset, const uint32_t* row_ids,
                                 uint64_t* out_keys, void* workspace, int64_t workspace_bytes, void* stream,
-                                const float* ext_seeds, int32_t ext_rows) {
+                                const SearchOpts& o) {
     Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, k, p) == LVS_OK,
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, o.hi_only, k, p) == LVS_OK,
                 "bad shape nq=%lld nb=%lld d=%d k=%d pack=%d/%d", (long long)nq, (long long)nb, d, k, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(k <= LVS_MAX_K, "k=%d exceeds LVS_MAX_K", k);
@@ -1156,391 +1577,35 @@ static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, con
         return LVS_ENOMEM;
     }
     char* ws = (char*)workspace;
-    uint32_t* gtau = (uint32_t*)(ws + p.off_gtau);
-    u64* partial = (u64*)(ws + p.off_partial);
-    u64* passbuf = (u64*)(ws + p.off_pass);
+    const SearchCall sc = {xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, id_offset, d, metric, k, xb_pack, xq_pack, row_ids,
+                           (u64*)out_keys, st, o, p, ws, workspace_bytes, (uint32_t*)(ws + p.off_gtau), (u64*)(ws + p.off_partial)};
 
-    auto fill_args = [&](LvsTileArgs& a, const Plan& pl, uint32_t* gtau_, u64* out_) {
-        memset(&a, 0, sizeof(a));
-        a.xb = xb;
-        a.xq = xq;
-        a.bn = xb_norms_sq;
-        a.qn = xq_norms_sq;
-        a.row_ids = row_ids;
-        a.gtau = gtau_;
-        a.out = out_;
-        a.nb = nb;
-        a.nq = nq;
-        a.ldb = pl.ldb;
-        a.ldq = pl.ldq;
-        a.nseg = pl.nseg;
-        for (int i = 0; i < 3; ++i) {
-            a.seg_q[i] = pl.seg_q[i];
-            a.seg_c[i] = pl.seg_c[i];
-        }
-        a.id_offset = id_offset;
-        a.nkd = pl.nkd;
-        a.nk = pl.nk;
-        a.metric = metric;
-        a.ntiles = pl.ntiles;
-        a.tiles_per_slab = pl.tiles_per_slab;
-        a.nslab = pl.nslab;
-        a.nqt = pl.nqt;
-        a.bq = pl.v2 ? LVS2_BQ : LVS3_BQ;
-        a.gq = pl.gq;
-        a.lead_slabs = pl.lead_slabs;
-        a.debug_hot = (int)lvs_tune("LVS_DEBUG_HOT", 0);
-    };
-
-    // ---- k > LVS_KPASS: two corpus passes whatever k is (see make_two_phase_plan).  A bucket overflow (mass ties, or
-    // the top k clustered in one slab) sets a device-side flag; the selection passes below then run PREDICATED on that
-    // flag (their kernels return at once when it is clear), so the call never synchronises the stream. ----
     const uint32_t* pred = nullptr;
-    {
-        TwoPhasePlan tp;
-        if (make_two_phase_plan(nq, nb, d, xb_pack, xq_pack, k, tp) && tp.total <= workspace_bytes) {
-            uint32_t* gtau2 = (uint32_t*)(ws + tp.a.off_gtau);
-            u64* lists = (u64*)(ws + tp.a.off_partial);          // [nslab][nq][slots]
-            u64* thr = (u64*)(ws + tp.off_thr);                  // [nq]
-            uint32_t* cnt = (uint32_t*)(ws + tp.off_cnt);        // [nq]
-            uint32_t* flag = (uint32_t*)ws;                      // status word 0: some bucket overflowed
-            u64* bucket = (u64*)(ws + tp.off_bucket);            // [nq][capacity]
-            LvsTileArgs ta;
-            fill_args(ta, tp.a, gtau2, lists);
-            ta.k = tp.slots;
-            ta.no_share = 1;  // the bound needs every slab's own top list, not lists pruned by other slabs' thresholds
-            LVS_HIP_CHECK(hipMemsetAsync(gtau2, 0, (size_t)nq * 4, st));
-            LVS_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
-            LVS_HIP_CHECK(hipMemsetAsync(flag, 0, 4, st));
-            {
-                ScopedKernelTimer timer(st);
-                LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOPK, ta, st));
-            }
-            // T[q] = k-th largest of the nslab * slots listed keys (element (slab, j) of query q at (slab * nq + q) * slots + j)
-            LVS_HIP_CHECK(launch_select(lists, tp.slots, tp.slots, (long long)nq * tp.slots, tp.a.nslab * tp.slots,
-                                        nullptr, k, thr, nullptr, 0, nullptr, nq, st));
-            LvsTileArgs tb;
-            fill_args(tb, tp.b, gtau2, lists);
-            tb.k = 1;
-            tb.thr_key = thr;
-            tb.bucket_count = cnt;
-            tb.bucket = bucket;
-            tb.bucket_capacity = tp.capacity;
-            LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_COLLECT, tb, st));
-            LVS_HIP_CHECK(launch_select(bucket, tp.capacity, tp.capacity, 0, tp.capacity, cnt, k, nullptr,
-                                        (u64*)out_keys, k, flag, nq, st));
-            pred = flag;
-#ifdef LVS_TUNING
-            if (lvs_tune_set("LVS_TWO_PHASE_DEBUG")) {  // bucket statistics of this call (synchronises)
-                std::vector<uint32_t> h((size_t)nq);
-                uint32_t overflowed = 0;
-                LVS_HIP_CHECK(hipStreamSynchronize(st));
-                LVS_HIP_CHECK(hipMemcpy(&overflowed, flag, 4, hipMemcpyDeviceToHost));
-                LVS_HIP_CHECK(hipMemcpy(h.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost));
-                uint32_t mn = ~0u, mx = 0;
-                double sum = 0;
-                for (uint32_t v : h) {
-                    mn = v < mn ? v : mn;
-                    mx = v > mx ? v : mx;
-                    sum += v;
-                }
-                fprintf(stderr, "[lvs] two-phase k=%d slots=%d slabs=%d capacity=%d: bucket counts min %u mean %.1f max %u overflow=%u\n",
-                        k, tp.slots, tp.a.nslab, tp.capacity, mn, sum / (double)nq, mx, overflowed);
-            }
-#endif
-        }
-    }
+    const int32_t rc = search_two_phase(sc, &pred);
+    if (rc != LVS_OK) return rc;
 
-    LvsTileArgs a;
-    fill_args(a, p, gtau, partial);
-    a.pred = pred;
-    a.dbg = nullptr;
-    unsigned long long* dbg_counters = nullptr;
-#if defined(LVS_COUNT_EVENTS) && defined(LVS_TUNING)
-    if (lvs_tune("LVS_COUNT", 0)) {  // tuning build only: count slow-path events of this call (allocates, synchronises)
-        LVS_HIP_CHECK(hipMalloc((void**)&dbg_counters, 8 * sizeof(unsigned long long)));
-        LVS_HIP_CHECK(hipMemsetAsync(dbg_counters, 0, 8 * sizeof(unsigned long long), st));
-        a.dbg = dbg_counters;
-    }
-#endif
-
+    // ---- routing: one path serves the (rest of the) call ----
     // 97 .. 256 queries (and up to 4 096 in groups of 256), one K segment of fp16 k-slices: the queries live in REGISTERS
     // (lvs_rq.hip), the corpus streams through LDS once - between the HBM-bound batches below and the joins the list kernel is
-    // built for.  (r6) Beyond 4 096 queries the same launch repeats per CHUNK of 4 096 queries (16 groups x 16 corpus ranges):
-    // a query belongs to one chunk, so every chunk is a complete search of its own (own seeds, own lists, own merge).
-    const bool rq_ok = lvs_tune("LVS_RQ", 1) != 0 && p.nseg == 1 && p.npass == 1 && !pred && g_band.kc == 0;
-    // (a corpus SHARD qualifies from 65 536 rows on: its thresholds may come from the caller - the pooled sample scores of all
+    // built for.  (r6) Beyond 4 096 queries the same launch repeats per CHUNK of queries (search_rq_chunks).
+    const bool rq_ok = lvs_tune("LVS_RQ", 1) != 0 && p.nseg == 1 && p.npass == 1 && !pred && o.kc == 0;
+    // (a corpus SHARD qualifies from 32 768 rows on: its thresholds may come from the caller - the pooled sample scores of all
     // shards, scored by the list kernel's SEED mode in the same arithmetic - or from its own first rows)
     const bool rq_join = rq_ok && nq > LVS_RQ_MAXQ && lvs_tune("LVS_RQ_JOIN", LVS_RQ_JOIN_DEFAULT) != 0 &&
                          lvs_rq_shape_ok(p.dpad, k) && nb >= lvs_tune("LVS_RQ_JOIN_MINROWS", LVS_RQ_JOIN_MINROWS);
-    const bool rq_ext_seeds = ext_seeds && ext_rows >= k;
-    if (rq_join && rq_ext_seeds) {  // the k-th largest of the caller's sample scores, for every query of the call at once
-        hipLaunchKernelGGL(seed_kth_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, ext_seeds, (int)ext_rows,
-                           (long long)nq, k, gtau);
-        LVS_HIP_CHECK(hipGetLastError());
-    }
-    if (rq_join || (rq_ok && lvs_rq_fits(nq, nb, p.dpad, k))) {
-        // a chunk is 4 096 queries (16 groups x 16 corpus ranges) or 8 192 x 2^i (32 / 64 / 128 / 256 groups x 8 / 4 / 2 / 1 ranges:
-        // a multiple of 32 groups - lvs_rq_item); what is left at the end goes out in launches of 8 192, 4 096 and one of <= 4 096 queries
-        int64_t chunk = lvs_tune("LVS_RQ_CHUNK", LVS_RQ_CHUNK_DEFAULT);
-        {
-            int64_t c = LVS_RQ_MAXQ;
-            while (2 * c <= chunk && 2 * c <= LVS_RQ_CHUNK_MAX) c *= 2;
-            chunk = c;
-        }
-        for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
-            const int64_t left = nq - c0;
-            cn = left >= chunk ? chunk : (left >= 8192 ? 8192 : (left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left));
-            LvsRqArgs ra;
-            memset(&ra, 0, sizeof(ra));
-            ra.xb = xb;
-            ra.xq = (const _Float16*)xq + c0 * p.ldq;
-            ra.bn = xb_norms_sq;
-            ra.qn = xq_norms_sq ? xq_norms_sq + c0 : nullptr;
-            ra.row_ids = row_ids;
-            ra.gtau = gtau + c0;
-            ra.out = partial;
-            ra.nb = nb;
-            ra.ldb = p.ldb;
-            ra.ldq = p.ldq;
-            ra.id_offset = id_offset;
-            ra.nq = (int)cn;
-            ra.k = k;
-            ra.metric = metric;
-            // thresholds seeded from a sample of the rows scanned by this kernel's own SEED mode (bit-identical scores; see the
-            // streaming path below for why a caller's pooled sample scores are not used)
-            int64_t sample = nb / 8 / 1024 * 1024;
-            // (eight groups or more: a workgroup sees 30 000+ rows and fills its own lists - a quarter of the sample costs the main
-            // pass 1 % and saves 3 % of the call; profiles/r09b_rq_groups_sample_probe.log)
-            // (chunks of 16 384 queries or more see the corpus in <= 4 long ranges whose lists fill at once: half of that sample again
-            // costs the launches nothing and the sample pass half - 100 k x 1 M: call 126.0-127.8 -> 125.4-126.2 ms, same box,
-            // profiles/r12d_knobs.log)
-            const int64_t sample_cap = lvs_tune("LVS_RQ_SAMPLE", cn >= 16384 ? LVS_RQ_SEED_ROWS / 8
-                                                                 : (cn > 7 * LVS_RQ_GROUPQ ? LVS_RQ_SEED_ROWS / 4 : LVS_RQ_SEED_ROWS));
-            if (sample > sample_cap) sample = sample_cap;
-            if (rq_join && rq_ext_seeds) {
-                // seeded above
-            } else if (sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0) {
-                // (the k-th largest of one maximum per corpus range needs >= k ranges: the sample pass keeps launches of <= 16 groups)
-                float* seeds = (float*)((char*)partial + lvs_rq_parts_bytes(cn, k));  // [ranges][<= 4 096]
-                for (int64_t s0 = 0; s0 < cn; s0 += LVS_RQ_MAXQ) {
-                    const int64_t sn = cn - s0 < LVS_RQ_MAXQ ? cn - s0 : LVS_RQ_MAXQ;
-                    LvsRqArgs rs = ra;
-                    rs.xq = (const _Float16*)ra.xq + s0 * p.ldq;
-                    rs.qn = ra.qn ? ra.qn + s0 : nullptr;
-                    rs.gtau = ra.gtau + s0;
-                    rs.nq = (int)sn;
-                    rs.nb = sample;
-                    rs.seed_out = seeds;
-                    LVS_HIP_CHECK(lvs_rq_launch(rs, p.dpad, st));
-                    hipLaunchKernelGGL(seed_kth_kernel, dim3((unsigned)lvs_ceil_div(sn, 4)), dim3(256), 0, st, (const float*)seeds,
-                                       rs.nparts, (long long)sn, k, gtau + c0 + s0);  // writes every gtau[q] of the piece
-                    LVS_HIP_CHECK(hipGetLastError());
-                }
-            } else {
-                LVS_HIP_CHECK(hipMemsetAsync(gtau + c0, 0, (size_t)cn * 4, st));
-            }
-            // (r6) one wave per SIMD, 64 queries per wave (lvs_rj.hip) for the launches it takes: whole 32-row blocks there, the
-            // corpus' last nb % 32 rows through lvs_rq_kernel as one more list per query
-            if (lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_rj_fits(cn, nb, p.dpad, k, row_ids != nullptr)) {
-                {
-                    ScopedKernelTimer timer(st, LVS_KERNEL_RJ, c0 > 0);
-                    LVS_HIP_CHECK(lvs_rj_launch(ra, p.dpad, st));
-                }
-                const int64_t nb_full = nb / 32 * 32;
-                if (nb_full < nb) {
-                    LvsRqArgs rt = ra;
-                    rt.xb = (const char*)xb + nb_full * p.ldb * 2;
-                    rt.bn = xb_norms_sq ? xb_norms_sq + nb_full : nullptr;
-                    rt.nb = nb - nb_full;
-                    rt.id_offset = id_offset + nb_full;
-                    rt.out = partial + (int64_t)ra.nparts * cn * k;
-                    LVS_HIP_CHECK(lvs_rq_launch(rt, p.dpad, st));
-                    ra.nparts += rt.nparts;
-                }
-            } else {
-                ScopedKernelTimer timer(st, LVS_KERNEL_RQ, c0 > 0);
-                LVS_HIP_CHECK(lvs_rq_launch(ra, p.dpad, st));
-            }
-            u64* okeys = (u64*)out_keys + c0 * k;
-            if (ra.nparts >= 16)
-                hipLaunchKernelGGL(merge_keys_wide_kernel, dim3((unsigned)cn), dim3(1024), 0, st, partial, ra.nparts, (long long)cn, k,
-                                   okeys, (long long)k);
-            else
-                hipLaunchKernelGGL(merge_keys_kernel, dim3((unsigned)lvs_ceil_div(cn, 4)), dim3(256), 0, st, partial, ra.nparts,
-                                   (long long)cn, k, okeys, (long long)k, (const uint32_t*)nullptr);
-            LVS_HIP_CHECK(hipGetLastError());
-        }
-        return LVS_OK;
-    }
-    // HBM-bound regime (the literal sem_search: one query per call; small batches up to 256 queries): stream the corpus
-    // once, queries resident in LDS
-    {
-        const int nqseg = (xq_pack == LVS_PACK_SPLIT && !g_hi_only) ? 2 : 1;
-        const int jper = p.dpad / 16;
-        int kcap = 0, nqb = 0, groups = 0;
-        const bool fits = lvs_stream_plan(nq, k, nqseg * jper, &kcap, &nqb, &groups) > 0;
-        const bool want = lvs_tune("LVS_STREAM", 1) != 0 && nq <= lvs_tune("LVS_STREAM_MAXQ_RT", LVS_STREAM_MAXQ);
-        // several sibling workgroups per corpus range (beyond 96 fp16 queries) leave the HBM-bound regime - the siblings'
-        // re-reads are bound by the fabric behind the L2 (0.45 / 0.70 ms at 128 / 256 queries x 1 M rows) - while the seeded
-        // list kernel runs such batches near its MFMA rate: the stream kernel keeps the single-group batches
-        const bool beyond = groups > lvs_tune("LVS_STREAM_MAXG", 1) && p.npass == 1 && tile_seed_tiles(nq, nb, k) > 0;
-        if (want && fits && nb >= 4096 && !beyond) {
-            LvsStreamArgs sa;
-            memset(&sa, 0, sizeof(sa));
-            sa.xb = xb;
-            sa.xq = xq;
-            sa.bn = xb_norms_sq;
-            sa.qn = xq_norms_sq;
-            sa.row_ids = row_ids;
-            sa.gtau = gtau;
-            sa.out = partial;
-            sa.nb = nb;
-            sa.ldb = p.ldb;
-            sa.ldq = p.ldq;
-            sa.id_offset = id_offset;
-            sa.nq = (int)nq;
-            sa.k = k;
-            sa.metric = metric;
-            sa.jper = jper;
-            sa.nseg = p.nseg;
-            sa.nj = p.nseg * jper;
-            sa.nbfrag = nqseg * jper;
-            sa.kcap = kcap;
-            sa.nqb = nqb;
-            sa.groups = groups;
-            for (int i = 0; i < 3; ++i) {
-                sa.seg_q[i] = p.seg_q[i];
-                sa.seg_c[i] = p.seg_c[i];
-                sa.seg_b[i] = p.seg_q[i] == 0 ? 0 : jper;
-            }
-            // Every workgroup scans its own contiguous range, all at the same time: without help each of them starts with
-            // empty lists and pays its own cold start (~k (1 + ln(range / k)) insertions per query and workgroup - with
-            // dozens of queries that, not HBM, set the time in round 2).  So with several queries the thresholds are
-            // SEEDED: the same kernel first scans a sample (the first nb / 8 rows, at most 32 768) in SEED mode - no lists,
-            // every workgroup just keeps the best score per query over its 4 row blocks - and one wave per query takes the
-            // k-th largest of those per-range maxima as the starting threshold (~15 + 5 us; round 3's first version scored the
-            // sample into a matrix with the tile kernel and radix-selected it: 130-180 us).  A workgroup of the main scan then
-            // only inserts rows that beat it (~k * nb / sample per query over the WHOLE launch).  Exact: every value is a
-            // real row's score and the k-th largest of a subset never exceeds the k-th largest of all rows; the sample
-            // rows themselves are scanned again with the rest.
-            int64_t sample = nb / 8 / 1024 * 1024;
-            if (sample > LVS_STREAM_SEED_ROWS) sample = LVS_STREAM_SEED_ROWS;
-            // A caller's pooled sample scores (ext_seeds) are NOT used here: they come from the tile kernel's SEED mode, whose
-            // accumulation order differs from this kernel's, and "the k-th largest of a subset is a lower bound" is only exact
-            // when the threshold and the scan see bit-identical scores - one ulp the wrong way could reject a true top-k row on
-            // its own shard.  This path seeds itself, with its own arithmetic.
-            if (nq >= lvs_tune("LVS_STREAM_SEED_MINQ", 2) && sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0) {
-                float* seeds = (float*)((char*)partial + lvs_stream_parts_bytes(nq, k));  // [ranges][nq]
-                LvsStreamArgs ss = sa;
-                ss.nb = sample;
-                ss.seed_out = seeds;
-                LVS_HIP_CHECK(lvs_stream_launch(ss, st));
-                hipLaunchKernelGGL(seed_kth_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, (const float*)seeds,
-                                   ss.nparts, (long long)nq, k, gtau);  // writes every gtau[q]
-                LVS_HIP_CHECK(hipGetLastError());
-            } else {
-                LVS_HIP_CHECK(hipMemsetAsync(gtau, 0, (size_t)nq * 4, st));
-            }
-            {
-                ScopedKernelTimer timer(st, LVS_KERNEL_STREAM);
-                LVS_HIP_CHECK(lvs_stream_launch(sa, st));
-            }
-            if (sa.nparts >= 16 && k <= 64)
-                hipLaunchKernelGGL(merge_keys_wide_kernel, dim3((unsigned)nq), dim3(1024), 0, st, partial, sa.nparts,
-                                   (long long)nq, k, (u64*)out_keys, (long long)k);
-            else
-                hipLaunchKernelGGL(merge_keys_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, partial,
-                                   sa.nparts, (long long)nq, k, (u64*)out_keys, (long long)k, (const uint32_t*)nullptr);
-            LVS_HIP_CHECK(hipGetLastError());
-            return LVS_OK;
-        }
-    }
-    // k == 1: the list-free per-lane running best (TOP1) wins on short streams (k-means assignment: a few corpus tiles
-    // per query, nearly every block improves some lane's best); on long streams the threshold filter of the list
-    // kernel skips almost every block, so k = 1 goes through it like any other k.  Same winner either way
-    // (best score, lowest row among equals).
-    bool use_top1 = k == 1 && !row_ids && p.tiles_per_slab <= 64;
-    if (lvs_tune_set("LVS_TOP1")) use_top1 = k == 1 && !row_ids && lvs_tune("LVS_TOP1", 0) != 0;  // -DLVS_TUNING only
-    for (int pass = 0; pass < p.npass; ++pass) {
-        const int col0 = pass * p.kpass;
-        const int kp = (k - col0) < p.kpass ? (k - col0) : p.kpass;
-        a.k = kp;
-        // pass > 0: only keys strictly below the last key of the previous pass take part
-        a.ub = pass == 0 ? nullptr : (const u64*)out_keys + (col0 - 1);
-        a.ub_stride = k;
-        const bool banded = g_band.kc > 0 && g_band.kc < kp && p.npass == 1 && !pred && !use_top1 && xq_norms_sq;
-        a.kc = banded ? g_band.kc : 0;
-        a.bscale = banded ? g_band.bscale : 0.f;
-        a.bslack = banded ? g_band.bslack : 0.f;
-        const bool seedable = pass == 0 && p.npass == 1 && !pred && !use_top1;
-        const int seed_tiles = seedable ? tile_seed_tiles(nq, nb, kp) : 0;
-        if (seedable && ext_seeds && ext_rows >= kp) {  // the caller's pooled sample scores (every shard's sample)
-            hipLaunchKernelGGL(seed_kth_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, ext_seeds, (int)ext_rows,
-                               (long long)nq, kp, gtau, a.kc, xq_norms_sq, a.bscale, a.bslack);  // writes every gtau[q]
-            LVS_HIP_CHECK(hipGetLastError());
-        } else if (seed_tiles > 0) {  // thresholds seeded from a sample instead of cold starts (tile_seed_tiles)
-            float* seeds = (float*)(ws + p.off_seed);
-            LvsTileArgs sd = a;
-            sd.nb = (int64_t)seed_tiles * LVS_BC;
-            sd.ntiles = sd.nslab = seed_tiles;
-            sd.tiles_per_slab = 1;
-            sd.nqt = (int)lvs_ceil_div(nq, LVS2_BQ);
-            sd.bq = LVS2_BQ;
-            sd.gq = 1;
-            sd.lead_slabs = 0;
-            sd.k = 1;
-            sd.kc = 0;
-            sd.ub = nullptr;
-            sd.seed_out = seeds;
-            LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_SEED, sd, st));
-            hipLaunchKernelGGL(seed_kth_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, (const float*)seeds,
-                               sd.nslab, (long long)nq, kp, gtau, a.kc, xq_norms_sq, a.bscale, a.bslack);  // writes every gtau[q]
-            LVS_HIP_CHECK(hipGetLastError());
-        } else {
-            LVS_HIP_CHECK(hipMemsetAsync(gtau, 0, (size_t)nq * 4, st));
-        }
-        if (pred) {  // predicated fallback pass: not a measurement of the dominant kernel
-            LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOPK, a, st));
-        } else {
-            ScopedKernelTimer timer(st);
-            LVS_HIP_CHECK(lvs_tile_launch(use_top1 ? LVS_MODE_TOP1 : LVS_MODE_TOPK, a, st));
-        }
-        dim3 mgrid((unsigned)lvs_ceil_div(nq, 4)), mblock(256);
-        if (p.npass == 1 && kp == 1) {
-            hipLaunchKernelGGL(merge_top1_kernel, dim3((unsigned)lvs_ceil_div(nq, 256)), mblock, 0, st, partial,
-                               p.nslab, (long long)nq, (u64*)out_keys, (long long)k);
-        } else if (p.npass == 1 && !pred && p.nslab >= 16 && nq <= 4096) {
-            // few queries, many slabs: one workgroup of 16 waves per query (one wave per query walks hundreds of partial
-            // lists as a chain of dependent loads: 150 us of a 0.5 ms call at 256 queries x 489 slabs)
-            hipLaunchKernelGGL(merge_keys_wide_kernel, dim3((unsigned)nq), dim3(1024), 0, st, partial, p.nslab, (long long)nq,
-                               kp, (u64*)out_keys, (long long)k);
-        } else if (p.npass == 1) {
-            hipLaunchKernelGGL(merge_keys_kernel, mgrid, mblock, 0, st, partial, p.nslab, (long long)nq, kp,
-                               (u64*)out_keys, (long long)k, pred);
-        } else {
-            // the upper bounds of this pass live in out_keys, so merge into a side buffer first
-            hipLaunchKernelGGL(merge_keys_kernel, mgrid, mblock, 0, st, partial, p.nslab, (long long)nq, kp, passbuf,
-                               (long long)kp, pred);
-            hipLaunchKernelGGL(copy_pass_kernel, dim3((unsigned)lvs_ceil_div(nq * kp, 256)), dim3(256), 0, st, passbuf,
-                               (long long)nq, kp, (u64*)out_keys, k, col0, pred);
-        }
-        LVS_HIP_CHECK(hipGetLastError());
-    }
-    if (dbg_counters) {
-        unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        LVS_HIP_CHECK(hipStreamSynchronize(st));
-        LVS_HIP_CHECK(hipMemcpy(h, dbg_counters, sizeof(h), hipMemcpyDeviceToHost));
-        (void)hipFree(dbg_counters);
-        fprintf(stderr,
-                "[lvs] nq=%lld nb=%lld k=%d nslab=%d: wave-tiles %llu, block visits %llu, insertions %llu (%.1f per query); "
-                "cycles per wave-tile: filter %.0f, visit loop %.0f (of which insertions %.0f); per visit %.0f, per insertion %.0f\n",
-                (long long)nq, (long long)nb, k, p.nslab, h[2], h[0], h[1], (double)h[1] / (double)(nq > 0 ? nq : 1),
-                (double)h[3] / (double)(h[2] ? h[2] : 1), (double)h[4] / (double)(h[2] ? h[2] : 1),
-                (double)h[5] / (double)(h[2] ? h[2] : 1), (double)(h[4] - h[5]) / (double)(h[0] ? h[0] : 1),
-                (double)h[5] / (double)(h[1] ? h[1] : 1));
-    }
-    return LVS_OK;
+    if (rq_join || (rq_ok && lvs_rq_fits(nq, nb, p.dpad, k))) return search_rq_chunks(sc, rq_join);
+    // HBM-bound regime (the literal sem_search: one query per call; small batches up to 256 queries): the small-batch kernel
+    StreamShape sh = {0, 0, 0, 0};
+    sh.nbfrag = ((xq_pack == LVS_PACK_SPLIT && !o.hi_only) ? 2 : 1) * (p.dpad / 16);
+    const bool stream_fits = lvs_stream_plan(nq, k, sh.nbfrag, &sh.kcap, &sh.nqb, &sh.groups) > 0;
+    const bool stream_want = lvs_tune("LVS_STREAM", 1) != 0 && nq <= lvs_tune("LVS_STREAM_MAXQ_RT", LVS_STREAM_MAXQ);
+    // several sibling workgroups per corpus range (beyond 96 fp16 queries) leave the HBM-bound regime - the siblings'
+    // re-reads are bound by the fabric behind the L2 (0.45 / 0.70 ms at 128 / 256 queries x 1 M rows) - while the seeded
+    // list kernel runs such batches near its MFMA rate: the stream kernel keeps the single-group batches
+    const bool stream_beyond = sh.groups > lvs_tune("LVS_STREAM_MAXG", 1) && p.npass == 1 && tile_seed_tiles(nq, nb, k) > 0;
+    if (stream_want && stream_fits && nb >= 4096 && !stream_beyond) return search_stream(sc, sh);
+    // everything else, and the predicated fallback of the two-phase search: the list kernel
+    return search_list_passes(sc, pred);
 }
 
 extern "C" int32_t lvs_flat_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
@@ -1548,7 +1613,7 @@ extern "C" int32_t lvs_flat_search_keys(const void* xb, int32_t xb_pack, int64_t
                                         const float* xq_norms_sq, int64_t id_offset, const uint32_t* row_ids,
                                         uint64_t* out_keys, void* workspace, int64_t workspace_bytes, void* stream) {
     return flat_search_impl(xb, xb_pack, nb, xq, xq_pack, nq, d, metric, k, xb_norms_sq, xq_norms_sq, id_offset, row_ids,
-                            out_keys, workspace, workspace_bytes, stream, nullptr, 0);
+                            out_keys, workspace, workspace_bytes, stream, SearchOpts{});
 }
 
 extern "C" int32_t lvs_flat_search_keys_seeded(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
@@ -1557,8 +1622,11 @@ extern "C" int32_t lvs_flat_search_keys_seeded(const void* xb, int32_t xb_pack, 
                                                const float* seed_scores, int32_t seed_rows, uint64_t* out_keys,
                                                void* workspace, int64_t workspace_bytes, void* stream) {
     LVS_REQUIRE(seed_rows >= 0 && (seed_rows == 0 || seed_scores), "bad seed scores");
+    SearchOpts o;
+    o.ext_seeds = seed_rows > 0 ? seed_scores : nullptr;
+    o.ext_rows = seed_rows;
     return flat_search_impl(xb, xb_pack, nb, xq, xq_pack, nq, d, metric, k, xb_norms_sq, xq_norms_sq, id_offset, row_ids,
-                            out_keys, workspace, workspace_bytes, stream, seed_rows > 0 ? seed_scores : nullptr, seed_rows);
+                            out_keys, workspace, workspace_bytes, stream, o);
 }
 
 extern "C" int32_t lvs_flat_search_seed_tiles(int64_t nq, int64_t nb, int32_t k) {
@@ -1579,7 +1647,7 @@ extern "C" int32_t lvs_flat_search_seed_scores(const void* xb, int32_t xb_pack, 
                                                int64_t nq, int32_t d, int32_t metric, const float* xb_norms_sq,
                                                const float* xq_norms_sq, int32_t tiles, float* out_scores, void* stream) {
     Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, 1, p, true) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
                 (long long)nq, (long long)nb, d, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(tiles >= 0, "bad tile count %d", tiles);
@@ -1598,29 +1666,8 @@ extern "C" int32_t lvs_flat_search_seed_scores(const void* xb, int32_t xb_pack, 
     LVS_REQUIRE(xb && xq, "NULL rows");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LvsTileArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xb = xb;
-    a.xq = xq;
-    a.bn = xb_norms_sq;
-    a.qn = xq_norms_sq;
-    a.nb = (int64_t)have * LVS_BC;
-    a.nq = nq;
-    a.ldb = p.ldb;
-    a.ldq = p.ldq;
-    a.nseg = p.nseg;
-    for (int i = 0; i < 3; ++i) {
-        a.seg_q[i] = p.seg_q[i];
-        a.seg_c[i] = p.seg_c[i];
-    }
-    a.nkd = p.nkd;
-    a.nk = p.nk;
-    a.metric = metric;
-    a.k = 1;
-    a.ntiles = a.nslab = have;
-    a.tiles_per_slab = 1;
-    a.nqt = (int)lvs_ceil_div(nq, LVS2_BQ);
-    a.bq = LVS2_BQ;
-    a.gq = 1;
+    tile_args(a, p, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, 0);
+    seed_tile_geometry(a, have);
     a.seed_out = out_scores;
     LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_SEED, a, st));
     return LVS_OK;
@@ -1628,7 +1675,7 @@ extern "C" int32_t lvs_flat_search_seed_scores(const void* xb, int32_t xb_pack, 
 
 extern "C" int64_t lvs_nearest_hi_workspace_bytes(int64_t nq, int64_t nb, int32_t d) {
     Plan p;
-    if (make_plan(nq, nb, d, LVS_PACK_F16, LVS_PACK_F16, 1, p, true) != LVS_OK) return LVS_EINVAL;
+    if (make_plan(nq, nb, d, LVS_PACK_F16, LVS_PACK_F16, false, 1, p, true) != LVS_OK) return LVS_EINVAL;
     return 256 + lvs_round_up((int64_t)p.nslab * nq * 8, 256) + lvs_round_up((int64_t)p.nslab * nq * 4, 256);
 }
 
@@ -1637,7 +1684,7 @@ extern "C" int32_t lvs_nearest_hi(const void* xb, int32_t xb_pack, int64_t nb, c
                                   int64_t id_offset, uint64_t* out_keys, float* out_second, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
     Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, 1, p, true) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
                 (long long)nq, (long long)nb, d, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(id_offset >= 0 && id_offset + nb < 0xFFFFFFFFll, "ids must stay below 2^32-1");
@@ -1656,28 +1703,12 @@ extern "C" int32_t lvs_nearest_hi(const void* xb, int32_t xb_pack, int64_t nb, c
     u64* pk = (u64*)ws;
     float* ps = (float*)(ws + lvs_round_up((int64_t)p.nslab * nq * 8, 256));
     LvsTileArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xb = xb;
-    a.xq = xq;
-    a.bn = xb_norms_sq;
-    a.qn = xq_norms_sq;
-    a.nb = nb;
-    a.nq = nq;
-    a.ldb = p.ldb;  // SPLIT rows keep their leading dimension; only the fp16 "hi" half (columns [0, dpad)) is read
-    a.ldq = p.ldq;
+    tile_args(a, p, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, id_offset);
+    // SPLIT rows keep their leading dimension; only the fp16 "hi" half (columns [0, dpad)) is read
     a.nseg = 1;
-    a.id_offset = id_offset;
-    a.nkd = p.nkd;
     a.nk = p.nkd;
-    a.metric = metric;
-    a.k = 1;
-    a.ntiles = p.ntiles;
-    a.tiles_per_slab = p.tiles_per_slab;
-    a.nslab = p.nslab;
-    a.nqt = p.nqt;
     a.bq = LVS2_BQ;
-    a.gq = p.gq;
-    a.lead_slabs = p.lead_slabs;
+    a.k = 1;
     a.out = p.nslab == 1 ? (u64*)out_keys : pk;
     a.out_second = p.nslab == 1 ? out_second : ps;
     {
@@ -1724,9 +1755,10 @@ extern "C" int32_t lvs_flat_search_keys_hi(const void* xb, int32_t xb_pack, int6
                                            int64_t nq, int32_t d, int32_t metric, int32_t k, const float* xb_norms_sq,
                                            const float* xq_norms_sq, int64_t id_offset, const uint32_t* row_ids,
                                            uint64_t* out_keys, void* workspace, int64_t workspace_bytes, void* stream) {
-    HiOnlyScope hi;
-    return lvs_flat_search_keys(xb, xb_pack, nb, xq, xq_pack, nq, d, metric, k, xb_norms_sq, xq_norms_sq, id_offset, row_ids,
-                                out_keys, workspace, workspace_bytes, stream);
+    SearchOpts o;
+    o.hi_only = true;
+    return flat_search_impl(xb, xb_pack, nb, xq, xq_pack, nq, d, metric, k, xb_norms_sq, xq_norms_sq, id_offset, row_ids,
+                            out_keys, workspace, workspace_bytes, stream, o);
 }
 
 extern "C" int32_t lvs_flat_search_keys_hi_banded(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
@@ -1738,10 +1770,13 @@ extern "C" int32_t lvs_flat_search_keys_hi_banded(const void* xb, int32_t xb_pac
     LVS_REQUIRE(kc >= 1 && kc <= k, "banded search: 1 <= kc <= k (got kc=%d, k=%d)", kc, k);
     LVS_REQUIRE(band_scale >= 0.f && band_slack >= 0.f, "negative band");
     LVS_REQUIRE(nq == 0 || xq_norms_sq, "banded search needs the query norms");
-    HiOnlyScope hi;
-    BandScope band(kc, band_scale, band_slack);
-    return lvs_flat_search_keys(xb, xb_pack, nb, xq, xq_pack, nq, d, metric, k, xb_norms_sq, xq_norms_sq, id_offset, row_ids,
-                                out_keys, workspace, workspace_bytes, stream);
+    SearchOpts o;
+    o.hi_only = true;
+    o.kc = kc;
+    o.bscale = band_scale;
+    o.bslack = band_slack;
+    return flat_search_impl(xb, xb_pack, nb, xq, xq_pack, nq, d, metric, k, xb_norms_sq, xq_norms_sq, id_offset, row_ids,
+                            out_keys, workspace, workspace_bytes, stream, o);
 }
 
 extern "C" int32_t lvs_sort_keys_desc(uint64_t* keys, int64_t nq, int32_t k, void* stream) {
@@ -1833,9 +1868,7 @@ extern "C" int32_t lvs_merge_keys(const uint64_t* parts, int32_t nparts, int64_t
         }
         return LVS_OK;
     }
-    hipLaunchKernelGGL(merge_keys_kernel, dim3((unsigned)lvs_ceil_div(nq, 4)), dim3(256), 0, st, (const u64*)parts, nparts,
-                       (long long)nq, k, (u64*)out_keys, (long long)k, (const uint32_t*)nullptr);
-    LVS_HIP_CHECK(hipGetLastError());
+    LVS_HIP_CHECK(launch_merge(false, (const u64*)parts, nparts, nq, k, (u64*)out_keys, k, nullptr, st));
     return LVS_OK;
 }
 
@@ -1860,41 +1893,18 @@ extern "C" int32_t lvs_scores(const void* xb, int32_t xb_pack, int64_t nb, const
                               int32_t score_exp, float* out, int64_t ld_out, void* stream) {
     Plan p;
     LVS_REQUIRE(score_exp >= -120 && score_exp <= 120, "score_exp %d out of range", score_exp);
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, 1, p, true) == LVS_OK, "bad shape");
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape");
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     if (nq == 0 || nb == 0) return LVS_OK;
     LVS_REQUIRE(xb && xq && out && ld_out >= nb, "bad buffers");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LVS_DEVICE_GUARD(stream);
     LvsTileArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xb = xb;
-    a.xq = xq;
-    a.bn = xb_norms_sq;
-    a.qn = xq_norms_sq;
+    tile_args(a, p, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, 0);
     a.scores = out;
     a.ld_scores = ld_out;
     a.out_scale = ldexpf(1.0f, -score_exp);
-    a.nb = nb;
-    a.nq = nq;
-    a.ldb = p.ldb;
-    a.ldq = p.ldq;
-    a.nseg = p.nseg;
-    for (int i = 0; i < 3; ++i) {
-        a.seg_q[i] = p.seg_q[i];
-        a.seg_c[i] = p.seg_c[i];
-    }
-    a.nkd = p.nkd;
-    a.nk = p.nk;
-    a.metric = metric;
     a.k = 1;
-    a.ntiles = p.ntiles;
-    a.tiles_per_slab = p.tiles_per_slab;
-    a.nslab = p.nslab;
-    a.nqt = p.nqt;
-    a.bq = p.v2 ? LVS2_BQ : LVS3_BQ;
-    a.gq = p.gq;
-    a.lead_slabs = p.lead_slabs;
     LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_SCORES, a, (hipStream_t)stream));
     return LVS_OK;
 }
@@ -1906,7 +1916,7 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
                                   float* out_s, uint64_t* out_count, void* stream) {
     Plan p;
     LVS_REQUIRE(score_exp >= -120 && score_exp <= 120, "score_exp %d out of range", score_exp);
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, 1, p, true) == LVS_OK, "bad shape");
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape");
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(capacity >= 0 && out_count, "bad output buffers");
     LVS_REQUIRE(qt_stride >= 1 && qt_phase >= 0 && qt_phase < qt_stride, "bad tile dealing %d/%d", qt_phase, qt_stride);
@@ -1914,44 +1924,19 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
     LVS_REQUIRE(xb && xq && (capacity == 0 || (out_q && out_j && out_s)), "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LVS_DEVICE_GUARD(stream);
-    // (r6) fp16 rows, inner product, one rank's tiles: the register-resident-queries kernel in RANGE mode (lvs_rj.hip) - chunks of
-    // <= 32 768 queries, each against the rows that can still pair with it (a self-join skips the rows below the chunk's first
-    // query: j > i), whole 32-row blocks; the corpus' last nb % 32 rows and chunks left with a short corpus go through the list
-    // kernel below.  Same pairs (keys are scores of the same MFMA sequence), one shared counter.
-    const bool rj_range = lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_tune("LVS_RJ_RANGE", 1) != 0 && xb_pack == LVS_PACK_F16 &&
-                          xq_pack == LVS_PACK_F16 && metric == LVS_METRIC_IP && qt_stride == 1 && nq >= 2048 &&
-                          lvs_rq_shape_ok(p.dpad, 1);
-    // one launch of the list kernel over queries [c0, c0 + cn) x rows [r0, r0 + rn)
-    auto tile_launch = [&](int64_t c0, int64_t cn, int64_t r0, int64_t rn, bool continuation) -> int32_t {
+    hipStream_t st = (hipStream_t)stream;
+    const float thr = threshold * ldexpf(1.0f, score_exp);  // the device scores are 2^score_exp x the caller's (exact)
+    const float out_scale = ldexpf(1.0f, -score_exp);
+    // one launch of the list kernel over queries [c0, c0 + cn) x rows [r0, r0 + rn), query tiles dealt stride / phase
+    auto tile_launch = [&](int64_t c0, int64_t cn, int64_t r0, int64_t rn, int32_t stride, int32_t phase,
+                           bool continuation) -> int32_t {
         Plan pl;
-        LVS_REQUIRE(make_plan(cn, rn, d, xb_pack, xq_pack, 1, pl, true) == LVS_OK, "bad shape");
+        LVS_REQUIRE(make_plan(cn, rn, d, xb_pack, xq_pack, false, 1, pl, true) == LVS_OK, "bad shape");
         LvsTileArgs a;
-        memset(&a, 0, sizeof(a));
-        a.xb = (const char*)xb + r0 * pl.ldb * 2;
-        a.xq = (const char*)xq + c0 * pl.ldq * 2;
-        a.bn = xb_norms_sq ? xb_norms_sq + r0 : nullptr;
-        a.qn = xq_norms_sq ? xq_norms_sq + c0 : nullptr;
-        a.nb = rn;
-        a.nq = cn;
-        a.ldb = pl.ldb;
-        a.ldq = pl.ldq;
-        a.nseg = pl.nseg;
-        for (int i = 0; i < 3; ++i) {
-            a.seg_q[i] = pl.seg_q[i];
-            a.seg_c[i] = pl.seg_c[i];
-        }
-        a.id_offset = id_offset + r0;
-        a.nkd = pl.nkd;
-        a.nk = pl.nk;
-        a.metric = metric;
+        tile_args(a, pl, (const char*)xb + r0 * pl.ldb * 2, (const char*)xq + c0 * pl.ldq * 2,
+                  xb_norms_sq ? xb_norms_sq + r0 : nullptr, xq_norms_sq ? xq_norms_sq + c0 : nullptr, rn, cn, metric,
+                  id_offset + r0);
         a.k = 1;
-        a.ntiles = pl.ntiles;
-        a.tiles_per_slab = pl.tiles_per_slab;
-        a.nslab = pl.nslab;
-        a.nqt = pl.nqt;
-        a.bq = pl.v2 ? LVS2_BQ : LVS3_BQ;
-        a.gq = pl.gq;
-        a.lead_slabs = pl.lead_slabs;
         a.pair_q = (long long*)out_q;
         a.pair_j = (long long*)out_j;
         a.pair_s = out_s;
@@ -1959,109 +1944,71 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
         a.pair_capacity = capacity;
         a.q_row0 = q_row0 >= 0 ? q_row0 + c0 : -1;
         a.q_base = c0;
-        a.threshold = threshold * ldexpf(1.0f, score_exp);
-        a.out_scale = ldexpf(1.0f, -score_exp);
-        a.qt_stride = 1;
-        a.qt_phase = 0;
-        ScopedKernelTimer timer((hipStream_t)stream, LVS_KERNEL_TILE, continuation);
-        LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_RANGE, a, (hipStream_t)stream));
+        a.threshold = thr;
+        a.out_scale = out_scale;
+        a.qt_stride = stride;
+        a.qt_phase = phase;
+        ScopedKernelTimer timer(st, LVS_KERNEL_TILE, continuation);
+        LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_RANGE, a, st));
         return LVS_OK;
     };
-    if (rj_range) {
-        const int64_t chunk = 32768;
-        bool first = true;
-        for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
-            const int64_t left = nq - c0;
-            cn = left >= chunk ? chunk : (left >= 8192 ? 8192 : (left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left));
-            // rows that can pair with this chunk's queries: all of them, or (self-join) those above the chunk's first query row
-            int64_t r0 = 0;
-            if (q_row0 >= 0) {
-                r0 = (q_row0 + c0 - id_offset) / 32 * 32;
-                if (r0 < 0) r0 = 0;
-                if (r0 > nb) r0 = nb;
-            }
-            const int64_t r_full = nb / 32 * 32;  // the register-resident kernel sees whole blocks
-            const int64_t rn = r_full - r0;
-            const int64_t groups = (cn + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
-            const bool take = rn >= LVS_RQ_JOIN_MINROWS && cn > 128 && (groups <= 32 || groups % 32 == 0);
-            if (take) {
-                LvsRqArgs ra;
-                memset(&ra, 0, sizeof(ra));
-                ra.xb = (const char*)xb + r0 * p.ldb * 2;
-                ra.xq = (const _Float16*)xq + c0 * p.ldq;
-                ra.nb = rn;
-                ra.ldb = p.ldb;
-                ra.ldq = p.ldq;
-                ra.id_offset = id_offset + r0;
-                ra.nq = (int)cn;
-                ra.k = 1;
-                ra.metric = metric;
-                ra.pair_q = (long long*)out_q;
-                ra.pair_j = (long long*)out_j;
-                ra.pair_s = out_s;
-                ra.pair_count = (unsigned long long*)out_count;
-                ra.pair_capacity = capacity;
-                ra.q_row0 = q_row0 >= 0 ? q_row0 + c0 : -1;
-                ra.q_base = c0;
-                ra.threshold = threshold * ldexpf(1.0f, score_exp);
-                ra.out_scale = ldexpf(1.0f, -score_exp);
-                {
-                    ScopedKernelTimer timer((hipStream_t)stream, LVS_KERNEL_RJ, !first);
-                    LVS_HIP_CHECK(lvs_rj_range_launch(ra, p.dpad, (hipStream_t)stream));
-                }
-                first = false;
-                if (r_full < nb) {  // the corpus' last nb % 32 rows
-                    const int32_t rc = tile_launch(c0, cn, r_full, nb - r_full, true);
-                    if (rc != LVS_OK) return rc;
-                }
-            } else if (nb - r0 > 0) {
-                const int32_t rc = tile_launch(c0, cn, r0, nb - r0, !first);
-                if (rc != LVS_OK) return rc;
-                first = false;
-            }
+    // (r6) fp16 rows, inner product, one rank's tiles: the register-resident-queries kernel in RANGE mode (lvs_rj.hip) - chunks of
+    // <= 32 768 queries, each against the rows that can still pair with it (a self-join skips the rows below the chunk's first
+    // query: j > i), whole 32-row blocks; the corpus' last nb % 32 rows and chunks left with a short corpus go through the list
+    // kernel.  Same pairs (keys are scores of the same MFMA sequence), one shared counter.
+    const bool rj_range = lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_tune("LVS_RJ_RANGE", 1) != 0 && xb_pack == LVS_PACK_F16 &&
+                          xq_pack == LVS_PACK_F16 && metric == LVS_METRIC_IP && qt_stride == 1 && nq >= 2048 &&
+                          lvs_rq_shape_ok(p.dpad, 1);
+    if (!rj_range) return tile_launch(0, nq, 0, nb, qt_stride, qt_phase, false);
+    bool first = true;
+    for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
+        cn = rq_chunk_len(nq - c0, LVS_RQ_CHUNK_DEFAULT);
+        // rows that can pair with this chunk's queries: all of them, or (self-join) those above the chunk's first query row
+        int64_t r0 = 0;
+        if (q_row0 >= 0) {
+            r0 = (q_row0 + c0 - id_offset) / 32 * 32;
+            if (r0 < 0) r0 = 0;
+            if (r0 > nb) r0 = nb;
         }
-        return LVS_OK;
-    }
-    LvsTileArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xb = xb;
-    a.xq = xq;
-    a.bn = xb_norms_sq;
-    a.qn = xq_norms_sq;
-    a.nb = nb;
-    a.nq = nq;
-    a.ldb = p.ldb;
-    a.ldq = p.ldq;
-    a.nseg = p.nseg;
-    for (int i = 0; i < 3; ++i) {
-        a.seg_q[i] = p.seg_q[i];
-        a.seg_c[i] = p.seg_c[i];
-    }
-    a.id_offset = id_offset;
-    a.nkd = p.nkd;
-    a.nk = p.nk;
-    a.metric = metric;
-    a.k = 1;
-    a.ntiles = p.ntiles;
-    a.tiles_per_slab = p.tiles_per_slab;
-    a.nslab = p.nslab;
-    a.nqt = p.nqt;
-    a.bq = p.v2 ? LVS2_BQ : LVS3_BQ;
-    a.gq = p.gq;
-    a.lead_slabs = p.lead_slabs;
-    a.pair_q = (long long*)out_q;
-    a.pair_j = (long long*)out_j;
-    a.pair_s = out_s;
-    a.pair_count = (unsigned long long*)out_count;
-    a.pair_capacity = capacity;
-    a.q_row0 = q_row0;
-    a.threshold = threshold * ldexpf(1.0f, score_exp);  // the device scores are 2^score_exp x the caller's (exact)
-    a.out_scale = ldexpf(1.0f, -score_exp);
-    a.qt_stride = qt_stride;
-    a.qt_phase = qt_phase;
-    {
-        ScopedKernelTimer timer((hipStream_t)stream);
-        LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_RANGE, a, (hipStream_t)stream));
+        const int64_t r_full = nb / 32 * 32;  // the register-resident kernel sees whole blocks
+        const int64_t rn = r_full - r0;
+        const int64_t groups = (cn + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
+        const bool take = rn >= LVS_RQ_JOIN_MINROWS && cn > 128 && (groups <= 32 || groups % 32 == 0);
+        if (take) {
+            LvsRqArgs ra;
+            memset(&ra, 0, sizeof(ra));
+            ra.xb = (const char*)xb + r0 * p.ldb * 2;
+            ra.xq = (const _Float16*)xq + c0 * p.ldq;
+            ra.nb = rn;
+            ra.ldb = p.ldb;
+            ra.ldq = p.ldq;
+            ra.id_offset = id_offset + r0;
+            ra.nq = (int)cn;
+            ra.k = 1;
+            ra.metric = metric;
+            ra.pair_q = (long long*)out_q;
+            ra.pair_j = (long long*)out_j;
+            ra.pair_s = out_s;
+            ra.pair_count = (unsigned long long*)out_count;
+            ra.pair_capacity = capacity;
+            ra.q_row0 = q_row0 >= 0 ? q_row0 + c0 : -1;
+            ra.q_base = c0;
+            ra.threshold = thr;
+            ra.out_scale = out_scale;
+            {
+                ScopedKernelTimer timer(st, LVS_KERNEL_RJ, !first);
+                LVS_HIP_CHECK(lvs_rj_range_launch(ra, p.dpad, st));
+            }
+            first = false;
+            if (r_full < nb) {  // the corpus' last nb % 32 rows
+                const int32_t rc = tile_launch(c0, cn, r_full, nb - r_full, 1, 0, true);
+                if (rc != LVS_OK) return rc;
+            }
+        } else if (nb - r0 > 0) {
+            const int32_t rc = tile_launch(c0, cn, r0, nb - r0, 1, 0, !first);
+            if (rc != LVS_OK) return rc;
+            first = false;
+        }
     }
     return LVS_OK;
 }

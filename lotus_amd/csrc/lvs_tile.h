@@ -280,15 +280,13 @@ __host__ __device__ inline bool lvs_rq_item(int b, int groups, int nparts, int& 
 }
 bool lvs_rq_fits(int64_t nq, int64_t nb, int dpad, int k);
 bool lvs_rq_shape_ok(int dpad, int k);
-#define LVS_RQ_JOIN_MINROWS 65536  // shortest corpus (shard) a chunked call takes: 2 ranges of 1 024 blocks at 128 groups
+#define LVS_RQ_JOIN_MINROWS 32768  // shortest corpus (shard) a chunked call takes (r6: 50 k x 50 k 5.3 -> 4.4 ms; at 20 000 rows the list kernel wins)
 hipError_t lvs_rq_launch(LvsRqArgs& a, int dpad, hipStream_t stream);
 // ---- lvs_rj.hip: the same launches with ONE wave per SIMD and 64 queries per wave (B fragments in named accumulation registers)
 #define LVS_RJ_DEFAULT 1    // launches lvs_rj_fits accepts go through lvs_rj_kernel (1) or lvs_rq_kernel (0)
 bool lvs_rj_fits(int64_t nq, int64_t nb, int dpad, int k, bool has_row_ids);
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // whole 32-row blocks only: the caller adds the tail
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // the same geometry, RANGE epilogue (inner product)
-#undef LVS_RQ_JOIN_MINROWS
-#define LVS_RQ_JOIN_MINROWS 32768  // shortest corpus (shard) a chunked call takes (r6: 50 k x 50 k 5.3 -> 4.4 ms; at 20 000 rows the list kernel wins)
 
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);
