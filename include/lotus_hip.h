@@ -39,7 +39,9 @@ extern "C" {
                              5: banded candidate lists for the certified one-pass search (lvs_flat_search_keys_hi_banded,
                                 lvs_certify_topk_banded);
                              6: the row-sharded search with its exchange steps inside the library (lvs_search_sharded with a
-                                caller-supplied all-gather, lvs_search_sharded_rccl on an ncclComm_t, lvs_rccl_available / _bind) */
+                                caller-supplied all-gather, lvs_search_sharded_rccl on an ncclComm_t, lvs_rccl_available / _bind);
+                             7 + additive: IVF-Flat lists and search (lvs_ivf_build_workspace_bytes, lvs_ivf_build_lists,
+                                lvs_ivf_search_workspace_bytes, lvs_ivf_search_keys, LVS_KERNEL_IVF) - no existing entry changed */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -412,6 +414,37 @@ int32_t lvs_rand_perm_prefix_host(int64_t n, int64_t seed, int64_t m, int64_t* o
 int32_t lvs_kmeans_split_clusters_host(int32_t d, int32_t k, int64_t n, float* hassign, float* centroids,
                                        int32_t* out_nsplit);
 
+/* ---- IVF-Flat: an inverted-file index over the flat packed rows (faiss "IVF<nlist>,Flat"; the reference's
+ * FaissVS(factory_string=...), lotus/vector_store/faiss_vs.py:14).  The lists hold ROW NUMBERS into the flat image that
+ * lvs_flat_search_keys searches - the corpus is never copied into list order; the list scan gathers the rows it needs.
+ * ---- */
+/* scratch of lvs_ivf_build_lists for n rows and nlist lists (negative: bad arguments). */
+int64_t lvs_ivf_build_workspace_bytes(int64_t n, int32_t nlist);
+/* Stable counting sort of the rows by list: assign [n] int64 list id of every row (ids outside [0, nlist) are left out of
+ * every list) -> out_offsets [nlist + 1] int64 (list l = out_rows[out_offsets[l] .. out_offsets[l + 1])), out_rows [n]
+ * uint32 row numbers, ascending inside a list.  n < 2^32 - 1. */
+int32_t lvs_ivf_build_lists(const int64_t* assign, int64_t n, int32_t nlist, int64_t* out_offsets, uint32_t* out_rows,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+/* scratch of lvs_ivf_search_keys (centroids and queries packed with `pack`).  Calls with many queries run in chunks of at
+ * most 16 384 queries, fewer when the chunk's scratch would exceed 512 MB, so the size is bounded whatever nq is.
+ * LVS_EUNSUPPORTED: the list scan keeps a tile's 32 queries in LDS and cannot take this d and k (hi|lo queries: d > 1088,
+ * or d > 1216 for k <= 16; fp16 queries: d > 2240, or d > 2432 for k <= 16) - search such shapes with
+ * lvs_flat_search_keys; lvs_ivf_search_keys returns the same status for them. */
+int64_t lvs_ivf_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t pack);
+/* IVF-Flat search, everything on `stream`, no synchronisation:
+ *   1. coarse step: lvs_flat_search_keys(centroids [nlist][d], queries, k = nprobe) under `metric`;
+ *   2. the (query, probe rank) pairs are grouped by list (counting sort, scan, scatter);
+ *   3. lvs_ivf_scan_kernel: per list, the rows rows[offsets[l] .. offsets[l + 1]) gathered from xb against the queries that
+ *      probe it -> per-probe lists [nprobe][nq][k];
+ *   4. lvs_merge_keys -> out_keys [nq][k], best first, keys as lvs_flat_search_keys (global row numbers, no id_offset).
+ * Exact over the rows of the probed lists; slots beyond them are key 0.  out_probe (nullable): [nq][nprobe] int32 list ids
+ * of the probes, best first.  1 <= nprobe <= nlist, 1 <= k <= 56.  xb_norms_sq / c_norms_sq / xq_norms_sq: squared L2 only. */
+int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq, const int64_t* offsets,
+                            const uint32_t* rows, int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                            const void* xq, int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric,
+                            int32_t nprobe, int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* ---- measurement hook: average duration in ms of the dominant search kernel's launches since the last reset,
  * measured with HIP events on the launch stream (enabled with lvs_timing_enable(1)). ---- */
 int32_t lvs_timing_enable(int32_t on);
@@ -423,6 +456,7 @@ int32_t lvs_timing_read(double* out_total_ms, int64_t* out_launches);
 #define LVS_KERNEL_STREAM 1 /* lvs_stream_kernel: up to 96 queries resident in LDS */
 #define LVS_KERNEL_RQ 2     /* lvs_rq_kernel: 32 queries per wave resident in registers */
 #define LVS_KERNEL_RJ 3     /* lvs_rj_kernel: 64 queries per wave resident in registers, one wave per SIMD */
+#define LVS_KERNEL_IVF 4    /* lvs_ivf_scan_kernel: one inverted list x up to 32 probing queries (lvs_ivf_search_keys) */
 int32_t lvs_timing_read_calls(double* out_total_ms, int64_t* out_launches, int64_t* out_calls, int32_t* out_kernel);
 
 #ifdef __cplusplus

@@ -18,6 +18,7 @@ METRIC_IP, METRIC_L2 = 0, 1
 PACK_F16, PACK_SPLIT = 0, 1
 MAX_K = 2048
 NEAREST3_MAX_ROWS = 16384
+IVF_MAX_K = 56  # largest k of the one-pass list scan (lvs_ivf_search_keys)
 ABI_VERSION = 7
 BUILD_TUNING, BUILD_COUNT_EVENTS = 1, 2
 PACK_FLAG_NONFINITE, PACK_FLAG_RANGE = 1, 2
@@ -96,6 +97,11 @@ SIGNATURES = {
     "lvs_kmeans_iteration_rccl": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _i64, _vp]),
     "lvs_rccl_bind_all_reduce": (_i32, [_vp]),
+    "lvs_ivf_build_workspace_bytes": (_i64, [_i64, _i32]),
+    "lvs_ivf_build_lists": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "lvs_ivf_search_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
+    "lvs_ivf_search_keys": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32,
+                                   _i32, _vp, _vp, _vp, _i64, _vp]),
     "lvs_timing_enable": (_i32, [_i32]),
     "lvs_timing_read": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),
     "lvs_timing_read_calls": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),

@@ -24,6 +24,22 @@ class PackedRows:
     flags: "object" = None  # device int32 [1] of LVS_PACK_FLAG_* when the pack was validated lazily (check="lazy")
 
 
+@dataclass
+class IvfLists:
+    """Inverted lists of an IVF-Flat index over a flat device image: row NUMBERS into that image, grouped by list."""
+
+    centroids: "object"  # PackedRows [nlist, d], packed like the image (same mode, same scale exponent)
+    offsets: "object"    # torch.Tensor int64 [nlist + 1]: list l = rows[offsets[l]:offsets[l + 1]]
+    rows: "object"       # torch.Tensor int32 [n] holding uint32 row numbers, ascending inside a list
+    nlist: int
+    metric: int
+
+
+def ivf_fits(d: int, k: int, mode: int) -> bool:
+    """Host-only query of the library: does ``lvs_ivf_search_keys`` take this dimension, k and pack mode?"""
+    return int(_capi.load().lvs_ivf_search_workspace_bytes(1, 1, 1, int(d), int(k), int(mode))) >= 0
+
+
 class _DevBytes:
     """A raw device pointer as something ``torch.as_tensor`` understands (the all-gather callback of ``lvs_search_sharded``)."""
 
@@ -893,6 +909,66 @@ class HipBackend:
         _capi.check(st, "lvs_search_sharded")
         return keys
 
+    # ---- IVF-Flat ----
+    IVF_ASSIGN_CHUNK_ROWS = 262144  # rows assigned to their list per search call while the lists are built
+
+    def ivf_build(self, packed: PackedRows, centroids, metric: int, offsets=None, rows=None) -> IvfLists:
+        """Inverted lists of ``packed`` around ``centroids`` (float32 [nlist, d], the caller's units).  Every row goes to its
+        best centroid under ``metric`` (faiss's IVF quantizer: an ``IndexFlatIP`` / ``IndexFlatL2`` over the centroids; ties
+        to the lower list id), then a stable counting sort groups the row numbers by list (``lvs_ivf_build_lists``).  The
+        image itself is not copied.  ``offsets`` / ``rows`` (host arrays): lists built before (a persisted sidecar) - only
+        uploaded."""
+        torch = self.torch
+        c = centroids if torch.is_tensor(centroids) else np.ascontiguousarray(centroids, dtype=np.float32)
+        nlist = int(c.shape[0])
+        cpk = self.pack(c, packed.mode, exp=int(packed.exp))
+        if offsets is not None:
+            return IvfLists(centroids=cpk, offsets=self.to_device(np.asarray(offsets, dtype=np.int64)),
+                            rows=self.to_device(np.asarray(rows, dtype=np.uint32).view(np.int32)), nlist=nlist, metric=metric)
+        n = packed.n
+        assign = torch.empty((n,), dtype=torch.int64, device=self.device)
+        step = self.IVF_ASSIGN_CHUNK_ROWS
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            keys = self.search_keys(cpk, self.slice_rows(packed, r0, r1), 1, metric).reshape(-1)
+            assign[r0:r1] = 0xFFFFFFFF - (keys & 0xFFFFFFFF)
+        off = torch.empty((nlist + 1,), dtype=torch.int64, device=self.device)
+        out_rows = torch.empty((n,), dtype=torch.int32, device=self.device)
+        need = int(self.lib.lvs_ivf_build_workspace_bytes(n, nlist))
+        if need < 0:
+            raise LotusHipError("lvs_ivf_build_workspace_bytes rejected the shape")
+        ws = self._workspace(need)
+        self._c("lvs_ivf_build_lists", _ptr(assign), n, nlist, _ptr(off), _ptr(out_rows), _ptr(ws), int(ws.numel()),
+                self._stream())
+        return IvfLists(centroids=cpk, offsets=off, rows=out_rows, nlist=nlist, metric=metric)
+
+    def ivf_fits(self, d: int, k: int, mode: int) -> bool:
+        """Can the list scan serve queries of dimension ``d`` packed with ``mode`` at this ``k``?  It keeps a tile's queries
+        in LDS, which bounds d (``lvs_ivf_search_workspace_bytes`` answers LVS_EUNSUPPORTED beyond); callers search the other
+        shapes exactly."""
+        return ivf_fits(d, k, mode)
+
+    def ivf_search(self, corpus: PackedRows, lists: IvfLists, queries: PackedRows, k: int, metric: int, nprobe: int,
+                   want_probe: bool = False):
+        """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] list ids of the probes, best first): the exact
+        top k over the rows of each query's ``nprobe`` best lists (``lvs_ivf_search_keys``); key 0 past those rows."""
+        torch = self.torch
+        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
+            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
+        nq = queries.n
+        keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
+        need = int(self.lib.lvs_ivf_search_workspace_bytes(nq, lists.nlist, nprobe, corpus.d, k, queries.mode))
+        if need < 0:
+            raise LotusHipError(f"lvs_ivf_search_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe} k={k}")
+        ws = self._workspace(need)
+        cpk = lists.centroids
+        self._c("lvs_ivf_search_keys", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets),
+                _ptr(lists.rows), lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(queries.rows), queries.mode, nq,
+                _ptr(queries.norms), corpus.d, metric, int(nprobe), int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()),
+                self._stream())
+        return (keys, probe) if want_probe else keys
+
     def merge_keys(self, parts):
         """parts int64 [P, nq, k] -> [nq, k]."""
         torch = self.torch
@@ -1155,7 +1231,7 @@ class HipBackend:
     def timing_enable(self, on: bool) -> None:
         _capi.check(self.lib.lvs_timing_enable(int(on)))
 
-    KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel"}
+    KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel", 4: "lvs_ivf_scan_kernel"}
 
     def timing_read(self):
         """-> (total ms of the dominant kernel's launches, searches that timed at least one): total / searches = kernel time per

@@ -2012,3 +2012,219 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
     }
     return LVS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// IVF-Flat (lvs_ivf.hip): inverted lists over the flat packed image, searched by probing nprobe lists per query
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// the timing hook reports the list scan: the coarse step's own flat search is not timed
+struct TimingPause {
+    bool was;
+    TimingPause() {
+        std::lock_guard<std::mutex> lk(g_timing.mu);
+        was = g_timing.on;
+        g_timing.on = false;
+    }
+    ~TimingPause() {
+        std::lock_guard<std::mutex> lk(g_timing.mu);
+        g_timing.on = was;
+    }
+};
+
+// does the list scan's LDS image (the tile's query fragments + its lists) fit a workgroup for queries of dimension d packed
+// with xq_pack?  hi|lo queries: d <= 1088 (k <= 16: 1216); fp16 queries: d <= 2240 (2432).  Larger shapes are not served
+bool ivf_fits(int32_t d, int32_t k, int32_t xq_pack) {
+    const int jper = (int)(lvs_round_up(d, LVS_BK) / 16);
+    const int nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper;
+    return lvs_ivf_lds_bytes(nbfrag, lvs_ivf_kcap(k)) <= 160 * 1024;
+}
+
+constexpr int64_t IVF_WS_BUDGET = 512ll << 20;  // scratch of one call; more queries go through in chunks
+constexpr int64_t IVF_CHUNK_MAX = 16384;
+
+struct IvfLayout {
+    int64_t chunk;  // queries per chunk
+    int64_t off_coarse, off_sort, off_tiles, off_items, off_parts, flat_bytes, sort_bytes, max_items, total;
+};
+
+// scratch of a chunk of `c` queries: [flat search scratch | coarse keys [c][nprobe] | bucket sort | tile offsets | work items
+// | parts [nprobe][c][k]]
+bool ivf_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack, IvfLayout& L) {
+    L.chunk = c;
+    L.flat_bytes = lvs_flat_search_workspace_bytes(c, nlist, d, nprobe, c_pack, xq_pack);
+    if (L.flat_bytes < 0) return false;
+    const int64_t npairs = c * nprobe;
+    L.sort_bytes = lvs_bucket_workspace_bytes(npairs, nlist);
+    if (L.sort_bytes < 0) return false;
+    L.max_items = lvs_ivf_max_items(npairs, nlist);
+    int64_t off = lvs_round_up(L.flat_bytes, 256);
+    L.off_coarse = off;
+    off += lvs_round_up(npairs * 8, 256);
+    L.off_sort = off;
+    off += lvs_round_up(L.sort_bytes, 256);
+    L.off_tiles = off;
+    off += lvs_round_up((int64_t)(nlist + 1) * 4, 256);
+    L.off_items = off;
+    off += lvs_round_up(L.max_items * 4, 256);
+    L.off_parts = off;
+    off += lvs_round_up(npairs * k * 8, 256);
+    L.total = off;
+    return true;
+}
+
+// the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits
+bool ivf_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack, IvfLayout& L) {
+    int64_t c = nq < IVF_CHUNK_MAX ? nq : IVF_CHUNK_MAX;
+    if (c < 1) c = 1;
+    for (;;) {
+        if (!ivf_layout(c, nlist, nprobe, d, k, c_pack, xq_pack, L)) return false;
+        if (L.total <= IVF_WS_BUDGET || c == 1) return c * nprobe < 0xFFFFFFFFll;
+        c = (c + 1) / 2;
+    }
+}
+}  // namespace
+
+extern "C" int64_t lvs_ivf_build_workspace_bytes(int64_t n, int32_t nlist) {
+    if (n < 0 || nlist < 1 || n >= 0xFFFFFFFFll) return LVS_EINVAL;
+    const int64_t b = lvs_bucket_workspace_bytes(n > 0 ? n : 1, nlist);
+    return b < 0 ? LVS_EINVAL : b;
+}
+
+extern "C" int32_t lvs_ivf_build_lists(const int64_t* assign, int64_t n, int32_t nlist, int64_t* out_offsets, uint32_t* out_rows,
+                                       void* workspace, int64_t workspace_bytes, void* stream) {
+    LVS_REQUIRE(n >= 0 && n < 0xFFFFFFFFll, "n=%lld out of range", (long long)n);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(out_offsets, "NULL offsets");
+    LVS_REQUIRE(n == 0 || (assign && out_rows && workspace), "NULL buffer");
+    const int64_t need = lvs_ivf_build_workspace_bytes(n, nlist);
+    LVS_REQUIRE(need >= 0, "nlist=%d is beyond the bucket sort", nlist);
+    if (n > 0 && workspace_bytes < need) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)need);
+        return LVS_ENOMEM;
+    }
+    LVS_DEVICE_GUARD(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        LVS_HIP_CHECK(hipMemsetAsync(out_offsets, 0, (size_t)(nlist + 1) * 8, st));
+        return LVS_OK;
+    }
+    const uint32_t *rows = nullptr, *offs = nullptr;
+    const int32_t rc = lvs_bucket_positions(nullptr, assign, n, nlist, workspace, workspace_bytes, st, &rows, &offs);
+    if (rc != LVS_OK) return rc;
+    LVS_HIP_CHECK(hipMemcpyAsync(out_rows, rows, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    LVS_HIP_CHECK(lvs_ivf_offsets_launch(offs, nlist, out_offsets, st));
+    return LVS_OK;
+}
+
+extern "C" int64_t lvs_ivf_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t pack) {
+    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
+        return LVS_EINVAL;
+    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
+    if (!ivf_fits(d, k, pack)) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
+    IvfLayout L;
+    if (!ivf_plan(nq, nlist, nprobe, d, k, pack, pack, L)) return LVS_EINVAL;
+    return L.total;
+}
+
+extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
+                                       const int64_t* offsets, const uint32_t* rows, int32_t nlist, const void* centroids,
+                                       int32_t c_pack, const float* c_norms_sq, const void* xq, int32_t xq_pack, int64_t nq,
+                                       const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                       uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                       void* stream) {
+    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
+    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
+                (long long)nq, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
+                nlist, LVS_MAX_K);
+    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
+    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
+    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    if (nq == 0) return LVS_OK;
+    LVS_REQUIRE(xb && offsets && rows && centroids && xq && out_keys && workspace, "NULL buffer");
+    LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
+    Plan p;
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, k, p) == LVS_OK, "bad plan");
+    const int jper = p.dpad / 16;
+    const int nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper;
+    const int kcap = lvs_ivf_kcap(k);
+    if (!ivf_fits(d, k, xq_pack)) {
+        lvs_set_error("d=%d with k=%d does not fit the list scan's LDS (see lvs_ivf_search_workspace_bytes)", d, k);
+        return LVS_EUNSUPPORTED;
+    }
+    IvfLayout L;
+    LVS_REQUIRE(ivf_plan(nq, nlist, nprobe, d, k, c_pack, xq_pack, L), "shape beyond the IVF search");
+    if (workspace_bytes < L.total) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
+        return LVS_ENOMEM;
+    }
+    LVS_DEVICE_GUARD(stream);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)workspace;
+    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
+    uint32_t* tile_offs = (uint32_t*)(w + L.off_tiles);
+    uint32_t* items = (uint32_t*)(w + L.off_items);
+    u64* parts = (u64*)(w + L.off_parts);
+
+    LvsIvfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xb = xb;
+    a.bn = xb_norms_sq;
+    a.rows = rows;
+    a.offsets = offsets;
+    a.out = parts;
+    a.nb = nb;
+    a.ldb = p.ldb;
+    a.ldq = p.ldq;
+    a.nlist = nlist;
+    a.nprobe = nprobe;
+    a.k = k;
+    a.metric = metric;
+    a.jper = jper;
+    a.nseg = p.nseg;
+    a.nbfrag = nbfrag;
+    a.kcap = kcap;
+    a.tile_offs = tile_offs;
+    a.item_list = items;
+    for (int i = 0; i < 3; ++i) {
+        a.seg_c[i] = p.seg_c[i];
+        a.seg_b[i] = p.seg_q[i] == 0 ? 0 : jper;
+    }
+    const size_t qrow_bytes = (size_t)p.ldq * 2;
+    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
+        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
+        const int64_t npairs = cn * nprobe;
+        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
+        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
+        // 1. coarse step: the nprobe best centroids of every query under the index's metric
+        {
+            TimingPause pause;
+            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq,
+                                                    qn_c, 0, nullptr, coarse, w, L.flat_bytes, stream);
+            if (rc != LVS_OK) return rc;
+        }
+        if (out_probe) LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, npairs, out_probe + q0 * nprobe, st));
+        // 2. invert the (query, probe) pairs: pair numbers q * nprobe + p grouped by list, then work items per list
+        const uint32_t *pairs = nullptr, *pair_offs = nullptr;
+        int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, w + L.off_sort, L.sort_bytes, st, &pairs, &pair_offs);
+        if (rc != LVS_OK) return rc;
+        LVS_HIP_CHECK(lvs_ivf_tiles_launch(pair_offs, nlist, tile_offs, items, st));
+        // 3. the list scan (a pair whose probe named no list - never with nprobe <= nlist - keeps empty slots)
+        LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+        a.xq = xq_c;
+        a.qn = qn_c;
+        a.nq = (int)cn;
+        a.pairs = pairs;
+        a.pair_offs = pair_offs;
+        {
+            ScopedKernelTimer timer(st, LVS_KERNEL_IVF, q0 > 0);
+            LVS_HIP_CHECK(lvs_ivf_scan_launch(a, lvs_ivf_max_items(npairs, nlist), st));
+        }
+        // 4. merge the per-probe lists
+        rc = lvs_merge_keys((const uint64_t*)parts, nprobe, cn, k, out_keys + q0 * k, stream);
+        if (rc != LVS_OK) return rc;
+    }
+    return LVS_OK;
+}

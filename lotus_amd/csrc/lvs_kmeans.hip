@@ -943,6 +943,45 @@ int32_t km_accumulate(const void* x, int64_t n, int32_t d, int32_t pack_mode, co
 }
 }  // namespace
 
+namespace {
+template <typename KeyT>
+int32_t km_bucket_positions(const KeyT* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes, hipStream_t st,
+                            const uint32_t** rows_out, const uint32_t** offs_out) {
+    KmSortPlan p;
+    LVS_REQUIRE(km_sort_plan(n, k, p), "k=%d is beyond the bucket sort", k);
+    if (ws_bytes < p.total) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)p.total);
+        return LVS_ENOMEM;
+    }
+    static LvsPerDeviceOnce attr_count, attr_scatter;
+    int dev = 0;
+    LVS_HIP_CHECK(hipGetDevice(&dev));
+    const size_t lds = (size_t)KM_MAX_BINS * 4;
+    if (!attr_count.done(dev, lds)) {
+        LVS_HIP_CHECK(hipFuncSetAttribute((const void*)km_count_kernel<KeyT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_count.set(dev, lds);
+    }
+    if (!attr_scatter.done(dev, lds)) {
+        LVS_HIP_CHECK(hipFuncSetAttribute((const void*)km_scatter_kernel<KeyT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_scatter.set(dev, lds);
+    }
+    return km_bucket_rows<KeyT>(assign, n, k, 0, p, (char*)ws, st, rows_out, offs_out);
+}
+}  // namespace
+
+// the counting sort above for other callers (the IVF lists and the inversion of an IVF search's probes, lvs_capi.hip)
+int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k) {
+    KmSortPlan p;
+    if (!km_sort_plan(n, k, p)) return LVS_EINVAL;
+    return p.total;
+}
+int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
+                             hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out) {
+    LVS_REQUIRE(n > 0 && k > 0 && (keys == nullptr) != (assign == nullptr) && ws, "bad arguments");
+    if (keys) return km_bucket_positions<u64>((const u64*)keys, n, k, ws, ws_bytes, stream, rows_out, offs_out);
+    return km_bucket_positions<long long>((const long long*)assign, n, k, ws, ws_bytes, stream, rows_out, offs_out);
+}
+
 extern "C" int64_t lvs_kmeans_accumulate_workspace_bytes(int64_t n, int32_t k) {
     KmSortPlan p;
     if (!km_sort_plan(n, k, p)) return LVS_EINVAL;

@@ -288,6 +288,43 @@ bool lvs_rj_fits(int64_t nq, int64_t nb, int dpad, int k, bool has_row_ids);
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // whole 32-row blocks only: the caller adds the tail
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // the same geometry, RANGE epilogue (inner product)
 
+// ---- lvs_ivf.hip: the list scan of an IVF-Flat search.  A work item is one inverted list and a tile of up to 32 of the
+// (query, probe rank) pairs that probe it; the list's rows are gathered by number from the flat image. ----
+#define LVS_IVF_TILEQ 32     // pairs per work item (MFMA N)
+#define LVS_IVF_WAVES 4
+struct LvsIvfArgs {
+    const void* xb;              // the flat packed image [nb][ldb]
+    const float* bn;             // [nb] |row|^2 (L2 only)
+    const uint32_t* rows;        // [n] row numbers, list after list
+    const int64_t* offsets;      // [nlist + 1]
+    const void* xq;              // queries of this chunk [nq][ldq]
+    const float* qn;             // [nq] |q|^2 (L2 only)
+    const uint32_t* pairs;       // [nq * nprobe] pair numbers q * nprobe + p, bucketed by list
+    const uint32_t* pair_offs;   // [nlist + 1] first pair of every list
+    const uint32_t* tile_offs;   // [nlist + 1] first work item of every list (lvs_ivf_tiles_launch)
+    const uint32_t* item_list;   // [work items] list of every work item
+    u64* out;                    // [nprobe][nq][k]
+    long long nb, ldb, ldq;
+    int nq, nlist, nprobe, k, metric;
+    int jper, nseg, nbfrag, kcap;
+    int seg_c[3], seg_b[3];
+};
+size_t lvs_ivf_lds_bytes(int nbfrag, int kcap);
+int lvs_ivf_kcap(int k);
+// work items of a launch can never exceed this bound (sum over lists of ceil(pairs / 32))
+static inline int64_t lvs_ivf_max_items(int64_t npairs, int32_t nlist) { return npairs / LVS_IVF_TILEQ + nlist + 1; }
+hipError_t lvs_ivf_tiles_launch(const uint32_t* pair_offs, int nlist, uint32_t* tile_offs, uint32_t* item_list,
+                                hipStream_t stream);
+hipError_t lvs_ivf_scan_launch(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream);
+hipError_t lvs_ivf_probe_ids_launch(const u64* keys, int64_t n, int32_t* out, hipStream_t stream);
+hipError_t lvs_ivf_offsets_launch(const uint32_t* offs, int nlist, int64_t* out, hipStream_t stream);
+// stable bucketing (lvs_kmeans.hip): positions 0 .. n-1 grouped by the id in their result key (keys[i], id_offset 0) or
+// by assign[i] (exactly one of the two non-NULL), ascending inside a bucket; ids outside [0, k) are left out.
+// *rows_out [n] and *offs_out [k + 1] point into the workspace.
+int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k);
+int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
+                             hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out);
+
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);
 int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, int* out_groups);

@@ -240,3 +240,75 @@ def open_device_rows(index_dir: str):
             return rows, "index-mmap"
     with open(os.path.join(index_dir, "vecs"), "rb") as fp:  # no mappable file: only the pickle has the rows
         return np.asarray(pickle.load(fp)), "pickle"
+
+
+# ---- IVF sidecar --------------------------------------------------------------------------------------------------------
+# An IVF store (HipVS(factory_string="IVF<nlist>,Flat")) writes the directory exactly as a flat one - stock LOTUS and
+# FaissVS("Flat") still read it - plus ``{dir}/ivf.npz``: the trained centroids and the inverted lists (row numbers), so
+# that a reload needs no k-means.  It is stamped with the content stamp of ``index`` / ``vecs`` (``_file_stamps``) and void
+# once either file was rewritten.  Plain arrays only: it is read with ``allow_pickle=False``.
+IVF_SIDECAR = "ivf.npz"
+IVF_VERSION = 1
+
+
+def write_ivf(index_dir: str, nlist: int, metric: int, pack_mode: int, centroids: np.ndarray, offsets: np.ndarray,
+              rows: np.ndarray) -> None:
+    """Write the sidecar atomically (temporary file + rename)."""
+    n, d = int(rows.shape[0]), int(centroids.shape[1])
+    header = {"version": IVF_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "d": d, "n": n,
+              "written_with": _file_stamps(index_dir)}
+    import tempfile
+
+    fd, tmp = tempfile.mkstemp(prefix="ivf.", suffix=".npz.tmp", dir=index_dir)
+    try:
+        with os.fdopen(fd, "wb") as fp:
+            np.savez(fp, header=np.array(json.dumps(header)), centroids=np.ascontiguousarray(centroids, dtype=np.float32),
+                     offsets=np.ascontiguousarray(offsets, dtype=np.int64), rows=np.ascontiguousarray(rows, dtype=np.uint32))
+        os.replace(tmp, os.path.join(index_dir, IVF_SIDECAR))
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
+
+def _ivf_stamps_valid(index_dir: str, stamps) -> bool:
+    """The sidecar's stamp is ``rows.json``'s (``_file_stamps``: size, sampled fingerprint and mtime of ``index`` / ``vecs``),
+    but it is accepted only while ALL of it is unchanged.  ``_stamps_still_valid`` also keeps a row store whose files were
+    copied (same size and fingerprint, new mtime) after an exact comparison with the faiss file; the lists have no such
+    comparison - the sampled fingerprint alone cannot rule out a rewrite of a few rows - and retraining them costs one device
+    k-means (a fraction of a second at 1 M rows), after which the rewritten sidecar carries the new mtimes."""
+    if not isinstance(stamps, dict):
+        return False
+    now = _file_stamps(index_dir)
+    for name in ("index", "vecs"):
+        was = list(stamps.get(name, []))
+        if len(was) < 3 or now[name][0] < 0 or was[:3] != list(now[name]):
+            return False
+    return True
+
+
+def read_ivf(index_dir: str, nlist: int, metric: int, pack_mode: int, d: int, n: int):
+    """-> (centroids float32 [nlist_eff, d], offsets int64 [nlist_eff + 1], rows uint32 [n]) from a valid sidecar written for
+    this nlist, metric, pack mode and shape, else None (missing, unreadable, stale or built otherwise)."""
+    path = os.path.join(index_dir, IVF_SIDECAR)
+    if not os.path.exists(path):
+        return None
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            header = json.loads(str(z["header"]))
+            c, off, rows = np.array(z["centroids"]), np.array(z["offsets"]), np.array(z["rows"])
+    except (OSError, ValueError, KeyError, TypeError):
+        return None
+    want = {"version": IVF_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "d": int(d), "n": int(n)}
+    if any(header.get(key) != val for key, val in want.items()):
+        return None
+    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
+        return None
+    m = int(c.shape[0]) if c.ndim == 2 else -1
+    if (m < 1 or c.shape[1] != d or c.dtype != np.float32 or off.shape != (m + 1,) or off.dtype != np.int64
+            or rows.shape != (n,) or rows.dtype != np.uint32 or off[0] != 0 or off[-1] > n or (np.diff(off) < 0).any()
+            or (n and int(rows.max(initial=0)) >= n)):
+        return None
+    return c, off, rows

@@ -14,12 +14,16 @@ Differences that are deliberate supersets (SURVEY.md section 8(a) edge-case tabl
   * several indexes stay resident (keyed by ``index_dir``) so ``sem_sim_join`` flipping left/right
     (``sem_sim_join.py:111-128``) does not reload from disk;
   * with ``torch.distributed`` initialised and ``shard=True`` the corpus is row-sharded over the ranks and the
-    per-shard top-k lists are merged after one all-gather (RCCL over xGMI on GPUs).
+    per-shard top-k lists are merged after one all-gather (RCCL over xGMI on GPUs);
+  * ``factory_string="IVF<nlist>,Flat"`` builds the inverted-file index ``FaissVS`` advertises but cannot train
+    (``faiss_vs.py:23-24`` calls ``add()`` without ``train()``): plain searches probe ``nprobe`` lists, everything else
+    stays exact (see ``HipVS``).
 """
 from __future__ import annotations
 
 import os
 import pickle
+import re
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Any
@@ -34,6 +38,7 @@ METRIC_L2 = _capi.METRIC_L2  # == faiss.METRIC_L2 (1)
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 _RANK_BLOCK_SCORES = 1 << 28  # K = N ranking: scores (float32) materialised at a time
+_IVF_SEED = 1234  # k-means seed of the IVF centroids (faiss's ClusteringParameters default)
 
 
 @dataclass
@@ -47,6 +52,7 @@ class _Resident:
     lo: int  # first global row of this rank's shard
     hi: int
     sig: Any = None  # store.signature() of the directory when it was loaded (None: never persisted)
+    ivf: Any = None  # backend IvfLists over `packed` (IVF stores only): centroids, offsets, row numbers
 
 
 def _serialised(fn):
@@ -87,12 +93,33 @@ class HipVS(VS):
             such switch - it relies on the RM normalising (``sentence_transformers_rm.py:30,71``) - so the default is off.
         max_resident: how many indexes stay on the GPU.
         backend: injected device backend (tests); default ``HipBackend``.
+        factory_string: ``"Flat"`` (default) - exact search; ``"IVF<nlist>,Flat"`` - an inverted-file index as faiss's
+            ``index_factory`` builds it: ``index()`` / ``load_index()`` train ``min(nlist, n)`` centroids with this package's
+            k-means (squared L2, fixed seed, ``ivf_niter`` iterations, ``ivf_max_points_per_centroid`` subsampling) on the
+            device image, put every row into the list of its best centroid under ``metric`` and keep the lists as row numbers
+            into the same image.  A plain search (no ``ids``, ``K <= 56``, ``K < n``) then scans the rows of each query's ``nprobe`` best
+            lists (``__call__(..., nprobe=...)`` overrides it per call); ``ids`` subsets and larger ``K`` stay exact.  The
+            directory is written as for ``"Flat"`` plus an ``ivf.npz`` sidecar that a reload uses instead of retraining.
+            Single GPU only: any ``shard`` but ``False`` is refused.  Rows too wide for the list scan's LDS image (hi|lo storage:
+            d > 1088, fp16: d > 2240; ``HipBackend.ivf_fits``) and ``nprobe`` > 2 048 are searched exactly.
+        nprobe: lists probed per query (faiss's default 1).
     """
 
     def __init__(self, metric: int = METRIC_INNER_PRODUCT, storage: str = "auto", device: str | None = None,
                  shard: bool | str = False, max_resident: int = 4, backend=None, process_group=None,
-                 normalize: bool = False, abi_exchange: bool = False) -> None:
+                 normalize: bool = False, abi_exchange: bool = False, factory_string: str = "Flat", nprobe: int = 1,
+                 ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256) -> None:
         super().__init__()
+        m = re.fullmatch(r"IVF([0-9]+),Flat", factory_string) if isinstance(factory_string, str) else None
+        if factory_string != "Flat" and (m is None or int(m.group(1)) < 1):
+            raise ValueError(f"factory_string must be 'Flat' or 'IVF<nlist>,Flat' (nlist >= 1), got {factory_string!r}")
+        self.factory_string = factory_string
+        self._nlist = int(m.group(1)) if m is not None else None
+        if self._nlist is not None and shard is not False:
+            raise ValueError("an IVF index is single-GPU: shard must be False with factory_string='IVF<nlist>,Flat'")
+        self.nprobe = self._check_nprobe(nprobe)
+        self.ivf_niter = int(ivf_niter)
+        self.ivf_max_points_per_centroid = ivf_max_points_per_centroid
         # True: a row-sharded search runs its two exchanges from inside the C ABI (lvs_search_sharded, the process group's
         # all-gather handed over as a callback) instead of from this file - same kernels, same order, same result
         self.abi_exchange = bool(abi_exchange)
@@ -318,8 +345,12 @@ class HipVS(VS):
 
                 _dist.barrier(self._pg)
         # the signature is taken after the barrier: every rank records the finished directory
-        self._install(index_dir, emb, stored=None if is_dev else emb,
-                      sig=store.signature(index_dir) if persist else None)
+        ent = self._install(index_dir, emb, stored=None if is_dev else emb,
+                            sig=store.signature(index_dir) if persist else None)
+        if self._nlist is not None:
+            ent.ivf = self._ivf_train(ent)
+            if persist:
+                self._ivf_write(index_dir, ent, best_effort=False)
         self.index_dir = index_dir
 
     @_serialised
@@ -335,7 +366,15 @@ class HipVS(VS):
         sig = store.signature(index_dir)
         rows, _ = store.open_device_rows(index_dir)
         rows = self._as_matrix(rows, "stored vectors")
-        self._install(index_dir, rows, stored=None, sig=sig)
+        ent = self._install(index_dir, rows, stored=None, sig=sig)
+        if self._nlist is not None and ent.n:
+            side = store.read_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, ent.d, ent.n)
+            if side is not None:
+                c, off, rr = side
+                ent.ivf = self.backend.ivf_build(ent.packed, c, self.metric, offsets=off, rows=rr)
+            else:  # missing, stale or built for another nlist / metric: train again and try to leave a valid sidecar behind
+                ent.ivf = self._ivf_train(ent)
+                self._ivf_write(index_dir, ent, best_effort=True)
         self.index_dir = index_dir
 
     @_serialised
@@ -392,6 +431,12 @@ class HipVS(VS):
             return RMOutput(distances=np.full((nq, K), pad_d, np.float32), indices=np.full((nq, K), -1, np.int64))
         rank_all = k_eff > _capi.MAX_K  # K = N callers (sem_dedup.py:45, sem_filter.py:491-497): full score rows + sort
         qrank, qworld, rank, world, pg_query, pg_corpus = self._layout()
+        # IVF stores probe lists for the plain query only; ids subsets, K = N callers, K beyond the one-pass list scan, rows too
+        # wide for its LDS image and more than 2 048 probes take the exact path below - which also ends the reference
+        # sem_search's K-doubling loop (sem_search.py:120-138) once the probed lists hold fewer than K rows
+        nprobe = min(self._check_nprobe(kwargs.get("nprobe", self.nprobe)), ent.ivf.nlist) if ent.ivf is not None else 0
+        use_ivf = (ent.ivf is not None and sub is None and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
+                   and qworld == 1 and nprobe <= _capi.MAX_K and be.ivf_fits(ent.d, K, ent.packed.mode))
         q_all = nq
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
             per = -(-nq // qworld)
@@ -401,7 +446,7 @@ class HipVS(VS):
         # queries share the index's power-of-two scale (required for L2; for inner products it keeps one exponent per
         # index); they are validated while they are packed, the flag word comes back together with the results
         qexp = kwargs.get("_query_exp", ent.packed.exp)
-        if (sub is None and not rank_all and world == 1 and qworld == 1 and not return_device and k_eff == K
+        if (sub is None and not rank_all and not use_ivf and world == 1 and qworld == 1 and not return_device and k_eff == K
                 and not self._is_device_tensor(q) and qexp != "auto" and hasattr(be, "search_host_pipelined")
                 and nq >= be.CALL_PIPELINE_MIN_QUERIES and not self._fp32_path(ent, q)):
             # the plain big call (sem_sim_join.py:132-134 -> faiss_vs.py:75): transfers overlapped with the search
@@ -450,6 +495,8 @@ class HipVS(VS):
             if order is not None:
                 id_map = be.to_device(order)
             world = 1  # already complete on every rank: nothing left to merge
+        elif use_ivf:
+            keys = be.ivf_search(ent.packed, ent.ivf, queries, k_eff, self.metric, nprobe)
         elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
             # the same row-sharded search with its two exchanges issued from INSIDE the C ABI (lvs_search_sharded): the transport
             # is this process group's all-gather, handed over as a callback
@@ -504,6 +551,77 @@ class HipVS(VS):
         D[:, :k_eff] = Dh
         I[:, :k_eff] = Ih
         return RMOutput(distances=D, indices=I)
+
+    # ------------------------------------------------------------------------------------------------ IVF
+    @staticmethod
+    def _check_nprobe(nprobe) -> int:
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or int(nprobe) < 1:
+            raise ValueError(f"nprobe must be an int >= 1, got {nprobe!r}")
+        return int(nprobe)
+
+    def _ivf_train(self, ent: _Resident):
+        """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store; None without rows."""
+        if ent.n == 0:
+            return None
+        from . import cluster
+
+        be = self.backend
+        nlist = max(1, min(self._nlist, ent.n))
+        res = cluster.kmeans(None, nlist, niter=self.ivf_niter, seed=_IVF_SEED,
+                             max_points_per_centroid=self.ivf_max_points_per_centroid, backend=be, packed=ent.packed,
+                             final_assign=False)
+        # rows go to their best centroid under the index's metric, against the final centroids (faiss's IVF quantizer)
+        return be.ivf_build(ent.packed, np.asarray(res.centroids, dtype=np.float32), self.metric)
+
+    def _ivf_write(self, index_dir: str, ent: _Resident, best_effort: bool) -> None:
+        if ent.ivf is None:
+            return
+        c, off, rows = self._ivf_host(ent.ivf)
+        try:
+            store.write_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, c, off, rows)
+        except OSError:
+            if not best_effort:
+                raise
+
+    def _ivf_host(self, lists):
+        c = self.backend.unpack(lists.centroids).cpu().numpy().astype(np.float32)
+        off = lists.offsets.cpu().numpy().astype(np.int64)
+        rows = lists.rows.cpu().numpy().view(np.uint32).copy()
+        return c, off, rows
+
+    def _ivf_current(self) -> _Resident:
+        ent = self._current()
+        if ent.ivf is None:
+            raise ValueError("the loaded index has no IVF lists (factory_string='Flat', or no rows)")
+        return ent
+
+    @_serialised
+    def ivf_lists(self):
+        """-> (centroids float32 [nlist, d] as the device holds them, offsets int64 [nlist + 1], rows uint32 [n]): list l holds
+        rows[offsets[l]:offsets[l + 1]], ascending."""
+        return self._ivf_host(self._ivf_current().ivf)
+
+    @_serialised
+    def ivf_probe(self, query_vectors, nprobe: int | None = None) -> np.ndarray:
+        """-> int32 [nq, nprobe] ids of the lists a search probes for every query, best first (the device's coarse step).  For
+        rows too wide for the list scan (searched exactly, see ``__call__``) the same coarse ranking of the centroids."""
+        ent = self._ivf_current()
+        q = self._as_matrix(query_vectors, "query_vectors")
+        if q.shape[1] != ent.d:
+            raise ValueError(f"query dimension {q.shape[1]} does not match index dimension {ent.d}")
+        nprobe = min(self._check_nprobe(self.nprobe if nprobe is None else nprobe), ent.ivf.nlist)
+        if nprobe > _capi.MAX_K:
+            raise ValueError(f"ivf_probe ranks at most {_capi.MAX_K} lists per query")
+        be = self.backend
+        queries = be.pack(q, ent.packed.mode, normalize=self.normalize, exp=ent.packed.exp, check=True)
+        if queries.n == 0:
+            return np.zeros((0, nprobe), np.int32)
+        if be.ivf_fits(ent.d, 1, ent.packed.mode):
+            _, probe = be.ivf_search(ent.packed, ent.ivf, queries, 1, self.metric, nprobe, want_probe=True)
+            return probe.cpu().numpy()
+        # the coarse step on its own: lvs_flat_search_keys over the centroids, as inside lvs_ivf_search_keys
+        keys = be.search_keys(ent.ivf.centroids, queries, nprobe, self.metric, one_pass=False).cpu().numpy().view(np.uint64)
+        return np.where(keys == 0, -1, 0xFFFFFFFF - (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int32)
 
     @staticmethod
     def _fp32_path(ent, q) -> bool:
