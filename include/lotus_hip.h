@@ -41,7 +41,9 @@ extern "C" {
                              6: the row-sharded search with its exchange steps inside the library (lvs_search_sharded with a
                                 caller-supplied all-gather, lvs_search_sharded_rccl on an ncclComm_t, lvs_rccl_available / _bind);
                              7 + additive: IVF-Flat lists and search (lvs_ivf_build_workspace_bytes, lvs_ivf_build_lists,
-                                lvs_ivf_search_workspace_bytes, lvs_ivf_search_keys, LVS_KERNEL_IVF) - no existing entry changed */
+                                lvs_ivf_search_workspace_bytes, lvs_ivf_search_keys, LVS_KERNEL_IVF) - no existing entry changed;
+                                IVF-SQ8 codes and search (lvs_ivf_sq8_encode, lvs_ivf_sq8_search_workspace_bytes,
+                                lvs_ivf_sq8_search_keys, LVS_KERNEL_IVF_SQ8) */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -445,6 +447,39 @@ int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const f
                             int32_t nprobe, int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* ---- IVF-SQ8: IVF-Flat's lists and coarse step, the rows scored from 8-bit codes of their residuals (faiss
+ * "IVF<nlist>,SQ8": ScalarQuantizer QT_8bit, by_residual).  Per dimension j, with vmin / vdiff trained by the caller:
+ *   r = x - c_l (x: the stored row value, c_l: its list's centroid), code_j = floor(255 clamp((r_j - vmin_j) / vdiff_j, 0, 1))
+ *   (code 0 where vdiff_j == 0), decoded rhat_j = vmin_j + (code_j + 0.5) vdiff_j / 255.
+ * Every array is in the rows' stored scale (the packed values x 2^exp, as lvs_unpack_rows with the pack exponent).  Codes
+ * are kept in LIST order: position p of the `rows` array of lvs_ivf_build_lists, ldc = d rounded up to 64 bytes per row.
+ * ---- */
+/* codes of every list position: out_codes [n][ldc] uint8 (bytes past d are 0), out_residual_norms_sq [n] fp32 |rhat|^2.
+ * xb: the packed image; offsets [nlist + 1] / rows [n]: the lists (n = offsets[nlist]); centroids [nlist][d], vmin [d],
+ * vdiff [d]: fp32.  Everything on `stream`, no synchronisation. */
+int32_t lvs_ivf_sq8_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets, const uint32_t* rows,
+                           int32_t nlist, const float* centroids, const float* vmin, const float* vdiff, uint8_t* out_codes,
+                           float* out_residual_norms_sq, void* stream);
+/* scratch of lvs_ivf_sq8_search_keys, chunked and bounded as lvs_ivf_search_workspace_bytes.  LVS_EUNSUPPORTED: the scan
+ * keeps a tile's 16 query vectors as hi|lo fp16 fragments in LDS, whatever the queries' pack mode: d > 2368 (d > 2432 for
+ * k <= 32) - search such shapes with lvs_flat_search_keys; lvs_ivf_sq8_search_keys returns the same status for them. */
+int64_t lvs_ivf_sq8_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t pack);
+/* IVF-SQ8 search, everything on `stream`, no synchronisation:
+ *   1. coarse step: exactly lvs_ivf_search_keys's (centroids packed with c_pack, c_norms_sq) -> the same probes;
+ *   2. the (query, probe rank) pairs are grouped by list;
+ *   3. lvs_ivf_sq8_scan_kernel: per list, its codes against up to 16 probing queries; a row scores as its decoded value
+ *      c_l + rhat under `metric` (squared L2: |q - c_l|^2 - 2 <q - c_l, rhat> + |rhat|^2, residual_norms_sq per position),
+ *      fp32-accurate in the query operand (centroids_f32 [nlist][d]: the fp32 values of the packed centroids);
+ *   4. lvs_merge_keys -> out_keys [nq][k], keys as lvs_ivf_search_keys (global row numbers; rows with equal codes in one
+ *      list score alike and come out in ascending row order).  Slots past the probed lists' rows are key 0.
+ * out_probe (nullable): [nq][nprobe] int32 list ids of the probes.  1 <= nprobe <= nlist, 1 <= k <= 56. */
+int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norms_sq, const float* vmin, const float* vdiff,
+                                const int64_t* offsets, const uint32_t* rows, int64_t nb, int32_t nlist, const void* centroids,
+                                int32_t c_pack, const float* c_norms_sq, const float* centroids_f32, const void* xq,
+                                int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe,
+                                int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+
 /* ---- measurement hook: average duration in ms of the dominant search kernel's launches since the last reset,
  * measured with HIP events on the launch stream (enabled with lvs_timing_enable(1)). ---- */
 int32_t lvs_timing_enable(int32_t on);
@@ -457,6 +492,7 @@ int32_t lvs_timing_read(double* out_total_ms, int64_t* out_launches);
 #define LVS_KERNEL_RQ 2     /* lvs_rq_kernel: 32 queries per wave resident in registers */
 #define LVS_KERNEL_RJ 3     /* lvs_rj_kernel: 64 queries per wave resident in registers, one wave per SIMD */
 #define LVS_KERNEL_IVF 4    /* lvs_ivf_scan_kernel: one inverted list x up to 32 probing queries (lvs_ivf_search_keys) */
+#define LVS_KERNEL_IVF_SQ8 5 /* lvs_ivf_sq8_scan_kernel: one list's 8-bit codes x up to 16 probing queries (lvs_ivf_sq8_search_keys) */
 int32_t lvs_timing_read_calls(double* out_total_ms, int64_t* out_launches, int64_t* out_calls, int32_t* out_kernel);
 
 #ifdef __cplusplus

@@ -40,6 +40,23 @@ def ivf_fits(d: int, k: int, mode: int) -> bool:
     return int(_capi.load().lvs_ivf_search_workspace_bytes(1, 1, 1, int(d), int(k), int(mode))) >= 0
 
 
+@dataclass
+class IvfSq8Lists:
+    """The 8-bit residual codes of an IVF-SQ8 index beside its ``IvfLists``, all in the image's stored scale (values x 2^exp)."""
+
+    vmin: "object"       # torch.Tensor float32 [d]: per-dimension minimum of the training residuals
+    vdiff: "object"      # torch.Tensor float32 [d]: vmax - vmin
+    centroids: "object"  # torch.Tensor float32 [nlist, d]: the packed centroids' values
+    codes: "object"      # torch.Tensor uint8 [n, ldc] in LIST order (position p of IvfLists.rows), ldc = d rounded up to 64
+    rnorm: "object"      # torch.Tensor float32 [n]: |decoded residual|^2 per list position
+    exp: int             # the image's pack exponent
+
+
+def ivf_sq8_fits(d: int, k: int, mode: int) -> bool:
+    """Host-only query of the library: does ``lvs_ivf_sq8_search_keys`` take this dimension, k and pack mode?"""
+    return int(_capi.load().lvs_ivf_sq8_search_workspace_bytes(1, 1, 1, int(d), int(k), int(mode))) >= 0
+
+
 class _DevBytes:
     """A raw device pointer as something ``torch.as_tensor`` understands (the all-gather callback of ``lvs_search_sharded``)."""
 
@@ -969,6 +986,82 @@ class HipBackend:
                 self._stream())
         return (keys, probe) if want_probe else keys
 
+    # ---- IVF-SQ8 ----
+    SQ8_TRAIN_CHUNK_ROWS = 65536  # training rows unpacked at a time while the residual ranges are taken
+
+    def _list_of_rows(self, lists: IvfLists, n: int):
+        """int64 [n]: the list of every row (-1 for rows in no list)."""
+        torch = self.torch
+        sizes = lists.offsets[1:] - lists.offsets[:-1]
+        lid = torch.repeat_interleave(torch.arange(lists.nlist, device=self.device), sizes)
+        out = torch.full((n,), -1, dtype=torch.int64, device=self.device)
+        out[lists.rows.to(torch.int64) & 0xFFFFFFFF] = lid
+        return out
+
+    def ivf_sq8_train(self, packed: PackedRows, lists: IvfLists, train_ids):
+        """-> (vmin, vdiff) float32 [d] device tensors in the stored scale: per-dimension range of the residuals x - c_l of the
+        training rows ``train_ids`` (host int64; faiss trains the scalar quantizer on the coarse quantizer's training set)."""
+        torch = self.torch
+        c = self.unpack(lists.centroids, raw=True)
+        where = self._list_of_rows(lists, packed.n)
+        ids = np.asarray(train_ids, dtype=np.int64)
+        vmin = torch.full((packed.d,), float("inf"), dtype=torch.float32, device=self.device)
+        vmax = torch.full((packed.d,), float("-inf"), dtype=torch.float32, device=self.device)
+        for r0 in range(0, len(ids), self.SQ8_TRAIN_CHUNK_ROWS):
+            idd = self.to_device(ids[r0:r0 + self.SQ8_TRAIN_CHUNK_ROWS])
+            r = self.unpack(packed, idd, raw=True) - c[where[idd]]
+            vmin = torch.minimum(vmin, r.amin(dim=0))
+            vmax = torch.maximum(vmax, r.amax(dim=0))
+        return vmin, vmax - vmin
+
+    def ivf_sq8_encode(self, packed: PackedRows, lists: IvfLists, vmin, vdiff, codes=None, rnorm=None) -> IvfSq8Lists:
+        """Codes of every list position (``lvs_ivf_sq8_encode``).  ``codes`` / ``rnorm`` (host arrays, list order, codes
+        [n, d]): encoded before (a persisted sidecar) - only uploaded."""
+        torch = self.torch
+        d = packed.d
+        ldc = -(-d // 64) * 64
+        vmin = torch.as_tensor(np.asarray(vmin, np.float32) if not torch.is_tensor(vmin) else vmin, device=self.device)
+        vdiff = torch.as_tensor(np.asarray(vdiff, np.float32) if not torch.is_tensor(vdiff) else vdiff, device=self.device)
+        c = self.unpack(lists.centroids, raw=True).contiguous()
+        n = int(lists.rows.numel())
+        if codes is not None:
+            out = torch.zeros((n, ldc), dtype=torch.uint8, device=self.device)
+            out[:, :d] = self.to_device(np.ascontiguousarray(codes, dtype=np.uint8))
+            rn = self.to_device(np.ascontiguousarray(rnorm, dtype=np.float32))
+        else:
+            out = torch.empty((n, ldc), dtype=torch.uint8, device=self.device)
+            rn = torch.empty((n,), dtype=torch.float32, device=self.device)
+            self._c("lvs_ivf_sq8_encode", _ptr(packed.rows), packed.mode, n, d, _ptr(lists.offsets), _ptr(lists.rows),
+                    lists.nlist, _ptr(c), _ptr(vmin), _ptr(vdiff), _ptr(out), _ptr(rn), self._stream())
+        return IvfSq8Lists(vmin=vmin.contiguous(), vdiff=vdiff.contiguous(), centroids=c, codes=out, rnorm=rn,
+                           exp=int(packed.exp))
+
+    def ivf_sq8_fits(self, d: int, k: int, mode: int) -> bool:
+        """Can the SQ8 list scan serve queries of dimension ``d`` at this ``k``?  Its LDS image bounds d (d <= 2368);
+        callers search the other shapes exactly."""
+        return ivf_sq8_fits(d, k, mode)
+
+    def ivf_sq8_search(self, corpus: PackedRows, lists: IvfLists, sq8: IvfSq8Lists, queries: PackedRows, k: int, metric: int,
+                       nprobe: int, want_probe: bool = False):
+        """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
+        query's ``nprobe`` best lists (``lvs_ivf_sq8_search_keys``); key 0 past those rows."""
+        torch = self.torch
+        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
+            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
+        nq = queries.n
+        keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
+        need = int(self.lib.lvs_ivf_sq8_search_workspace_bytes(nq, lists.nlist, nprobe, corpus.d, k, queries.mode))
+        if need < 0:
+            raise LotusHipError(f"lvs_ivf_sq8_search_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe} k={k}")
+        ws = self._workspace(need)
+        cpk = lists.centroids
+        self._c("lvs_ivf_sq8_search_keys", _ptr(sq8.codes), _ptr(sq8.rnorm), _ptr(sq8.vmin), _ptr(sq8.vdiff),
+                _ptr(lists.offsets), _ptr(lists.rows), corpus.n, lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms),
+                _ptr(sq8.centroids), _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
+                int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
+        return (keys, probe) if want_probe else keys
+
     def merge_keys(self, parts):
         """parts int64 [P, nq, k] -> [nq, k]."""
         torch = self.torch
@@ -1231,7 +1324,8 @@ class HipBackend:
     def timing_enable(self, on: bool) -> None:
         _capi.check(self.lib.lvs_timing_enable(int(on)))
 
-    KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel", 4: "lvs_ivf_scan_kernel"}
+    KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel", 4: "lvs_ivf_scan_kernel",
+                    5: "lvs_ivf_sq8_scan_kernel"}
 
     def timing_read(self):
         """-> (total ms of the dominant kernel's launches, searches that timed at least one): total / searches = kernel time per

@@ -2228,3 +2228,138 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
     }
     return LVS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// IVF-SQ8 (lvs_ivf_sq8.hip): the IVF-Flat lists and coarse step, the rows scored from 8-bit residual codes
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// does the SQ8 scan's LDS image (the tile's w fragments, hi|lo whatever the query's pack mode, + its lists) fit?
+bool ivf_sq8_fits(int32_t d, int32_t k) {
+    return lvs_ivf_sq8_lds_bytes(lvs_ivf_sq8_ldc(d), lvs_ivf_kcap(k)) <= 160 * 1024;
+}
+}  // namespace
+
+extern "C" int32_t lvs_ivf_sq8_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets,
+                                      const uint32_t* rows, int32_t nlist, const float* centroids, const float* vmin,
+                                      const float* vdiff, uint8_t* out_codes, float* out_residual_norms_sq, void* stream) {
+    LVS_REQUIRE(n >= 0 && n < 0xFFFFFFFFll && d > 0, "bad shape n=%lld d=%d", (long long)n, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    if (n == 0) return LVS_OK;
+    LVS_REQUIRE(xb && offsets && rows && centroids && vmin && vdiff && out_codes && out_residual_norms_sq, "NULL buffer");
+    LVS_DEVICE_GUARD(stream);
+    const int64_t dpad = lvs_round_up(d, LVS_BK);
+    const int64_t ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
+    LVS_HIP_CHECK(lvs_ivf_sq8_encode_launch(xb, ldb, xb_pack == LVS_PACK_SPLIT, (int)dpad, n, d, offsets, nlist, rows, centroids,
+                                            vmin, vdiff, out_codes, out_residual_norms_sq, (hipStream_t)stream));
+    return LVS_OK;
+}
+
+extern "C" int64_t lvs_ivf_sq8_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k,
+                                                      int32_t pack) {
+    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
+        return LVS_EINVAL;
+    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
+    if (!ivf_sq8_fits(d, k)) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
+    IvfLayout L;
+    if (!ivf_plan(nq, nlist, nprobe, d, k, pack, pack, L)) return LVS_EINVAL;
+    return L.total;
+}
+
+extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norms_sq, const float* vmin,
+                                           const float* vdiff, const int64_t* offsets, const uint32_t* rows, int64_t nb,
+                                           int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                           const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
+                                           const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                           uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
+    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
+                (long long)nq, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
+                nlist, LVS_MAX_K);
+    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
+    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
+    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    if (nq == 0) return LVS_OK;
+    LVS_REQUIRE(codes && vmin && vdiff && offsets && rows && centroids && centroids_f32 && xq && out_keys && workspace,
+                "NULL buffer");
+    LVS_REQUIRE(metric != LVS_METRIC_L2 || (residual_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
+    if (!ivf_sq8_fits(d, k)) {
+        lvs_set_error("d=%d with k=%d does not fit the SQ8 list scan's LDS (see lvs_ivf_sq8_search_workspace_bytes)", d, k);
+        return LVS_EUNSUPPORTED;
+    }
+    IvfLayout L;
+    LVS_REQUIRE(ivf_plan(nq, nlist, nprobe, d, k, c_pack, xq_pack, L), "shape beyond the IVF search");
+    if (workspace_bytes < L.total) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
+        return LVS_ENOMEM;
+    }
+    LVS_DEVICE_GUARD(stream);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)workspace;
+    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
+    uint32_t* tile_offs = (uint32_t*)(w + L.off_tiles);
+    uint32_t* items = (uint32_t*)(w + L.off_items);
+    u64* parts = (u64*)(w + L.off_parts);
+    const int64_t qdpad = lvs_round_up(d, LVS_BK);
+    const int64_t ldq = xq_pack == LVS_PACK_SPLIT ? 2 * qdpad : qdpad;
+
+    LvsIvfSq8Args a;
+    memset(&a, 0, sizeof(a));
+    a.codes = codes;
+    a.rnorm = residual_norms_sq;
+    a.vmin = vmin;
+    a.vdiff = vdiff;
+    a.cent = centroids_f32;
+    a.rows = rows;
+    a.offsets = offsets;
+    a.tile_offs = tile_offs;
+    a.item_list = items;
+    a.out = parts;
+    a.ldq = ldq;
+    a.nlist = nlist;
+    a.nprobe = nprobe;
+    a.k = k;
+    a.metric = metric;
+    a.d = d;
+    a.ldc = lvs_ivf_sq8_ldc(d);
+    a.qsplit = xq_pack == LVS_PACK_SPLIT;
+    a.qdpad = (int)qdpad;
+    a.kcap = lvs_ivf_kcap(k);
+    const size_t qrow_bytes = (size_t)ldq * 2;
+    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
+        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
+        const int64_t npairs = cn * nprobe;
+        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
+        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
+        // 1. coarse step: exactly lvs_ivf_search_keys's
+        {
+            TimingPause pause;
+            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq,
+                                                    qn_c, 0, nullptr, coarse, w, L.flat_bytes, stream);
+            if (rc != LVS_OK) return rc;
+        }
+        if (out_probe) LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, npairs, out_probe + q0 * nprobe, st));
+        // 2. the (query, probe) pairs grouped by list, 32-pair work items per list (the SQ8 scan halves them)
+        const uint32_t *pairs = nullptr, *pair_offs = nullptr;
+        int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, w + L.off_sort, L.sort_bytes, st, &pairs, &pair_offs);
+        if (rc != LVS_OK) return rc;
+        LVS_HIP_CHECK(lvs_ivf_tiles_launch(pair_offs, nlist, tile_offs, items, st));
+        // 3. the SQ8 list scan
+        LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+        a.xq = xq_c;
+        a.nq = (int)cn;
+        a.pairs = pairs;
+        a.pair_offs = pair_offs;
+        {
+            ScopedKernelTimer timer(st, LVS_KERNEL_IVF_SQ8, q0 > 0);
+            LVS_HIP_CHECK(lvs_ivf_sq8_scan_launch(a, lvs_ivf_max_items(npairs, nlist), st));
+        }
+        // 4. merge the per-probe lists
+        rc = lvs_merge_keys((const uint64_t*)parts, nprobe, cn, k, out_keys + q0 * k, stream);
+        if (rc != LVS_OK) return rc;
+    }
+    return LVS_OK;
+}

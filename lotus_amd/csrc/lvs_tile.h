@@ -325,6 +325,35 @@ int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k);
 int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
                              hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out);
 
+// ---- lvs_ivf_sq8.hip: the 8-bit residual codec of IVF-SQ8 and its list scan.  A work item is one list and up to 16 of the
+// (query, probe rank) pairs that probe it (half of a work item of lvs_ivf_tiles_launch); the codes are in list order. ----
+#define LVS_SQ8_TILEQ 16  // pairs per work item (MFMA N of v_mfma_f32_16x16x32_f16)
+#define LVS_SQ8_WAVES 4
+struct LvsIvfSq8Args {
+    const uint8_t* codes;        // [n][ldc] codes in list order (position p of `rows`)
+    const float* rnorm;          // [n] |rhat|^2 per position (L2 only)
+    const float* vmin;           // [d]
+    const float* vdiff;          // [d]
+    const float* cent;           // [nlist][d] fp32 centroids (the stored scale)
+    const uint32_t* rows;        // [n] row numbers, list after list
+    const int64_t* offsets;      // [nlist + 1]
+    const void* xq;              // packed queries of this chunk [nq][ldq]
+    const uint32_t* pairs;       // [nq * nprobe] pair numbers q * nprobe + p, bucketed by list
+    const uint32_t* pair_offs;   // [nlist + 1]
+    const uint32_t* tile_offs;   // [nlist + 1] first 32-pair work item of every list (lvs_ivf_tiles_launch)
+    const uint32_t* item_list;   // [work items]
+    u64* out;                    // [nprobe][nq][k]
+    long long ldq;
+    int nq, nlist, nprobe, k, metric, d, ldc, qsplit, qdpad, kcap;
+};
+size_t lvs_ivf_sq8_lds_bytes(int ldc, int kcap);
+int lvs_ivf_sq8_ldc(int d);  // code bytes per row: d rounded up to a multiple of 64
+hipError_t lvs_ivf_sq8_encode_launch(const void* xb, int64_t ldb, int split, int xdpad, int64_t n, int d,
+                                     const int64_t* offsets, int nlist, const uint32_t* rows, const float* cent,
+                                     const float* vmin, const float* vdiff, uint8_t* codes, float* rnorm, hipStream_t stream);
+// launches 2 x max_items blocks (max_items: lvs_ivf_max_items of the 32-pair work items)
+hipError_t lvs_ivf_sq8_scan_launch(const LvsIvfSq8Args& a, int64_t max_items, hipStream_t stream);
+
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);
 int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, int* out_groups);

@@ -312,3 +312,69 @@ def read_ivf(index_dir: str, nlist: int, metric: int, pack_mode: int, d: int, n:
             or (n and int(rows.max(initial=0)) >= n)):
         return None
     return c, off, rows
+
+
+# ---- IVF-SQ8 sidecar ----------------------------------------------------------------------------------------------------
+# An IVF-SQ8 store (HipVS(factory_string="IVF<nlist>,SQ8")) writes everything an IVF-Flat store writes - ``ivf.npz`` included,
+# so an "IVF<nlist>,Flat" store of the same nlist reuses the lists - plus ``{dir}/ivf_sq8.npz``: the codec (vmin, vdiff, in
+# the stored scale of the recorded pack exponent) and the codes and residual norms in list order.  It is stamped like
+# ``ivf.npz`` and names the lists it was encoded against (``ivf_digest``), so it only counts together with that sidecar.
+IVF_SQ8_SIDECAR = "ivf_sq8.npz"
+IVF_SQ8_VERSION = 1
+
+
+def ivf_digest(centroids: np.ndarray, offsets: np.ndarray, rows: np.ndarray) -> str:
+    """Content digest of an IVF index's centroids and lists, as ``write_ivf`` stores them."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for a, dt in ((centroids, np.float32), (offsets, np.int64), (rows, np.uint32)):
+        h.update(np.ascontiguousarray(a, dtype=dt).tobytes())
+    return h.hexdigest()
+
+
+def write_ivf_sq8(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: int, vmin: np.ndarray, vdiff: np.ndarray,
+                  codes: np.ndarray, rnorm: np.ndarray, lists_digest: str) -> None:
+    """Write the SQ8 sidecar atomically (temporary file + rename)."""
+    n, d = int(codes.shape[0]), int(codes.shape[1])
+    header = {"version": IVF_SQ8_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
+              "d": d, "n": n, "lists": str(lists_digest), "written_with": _file_stamps(index_dir)}
+    import tempfile
+
+    fd, tmp = tempfile.mkstemp(prefix="ivf_sq8.", suffix=".npz.tmp", dir=index_dir)
+    try:
+        with os.fdopen(fd, "wb") as fp:
+            np.savez(fp, header=np.array(json.dumps(header)), vmin=np.ascontiguousarray(vmin, dtype=np.float32),
+                     vdiff=np.ascontiguousarray(vdiff, dtype=np.float32), codes=np.ascontiguousarray(codes, dtype=np.uint8),
+                     rnorm=np.ascontiguousarray(rnorm, dtype=np.float32))
+        os.replace(tmp, os.path.join(index_dir, IVF_SQ8_SIDECAR))
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
+
+def read_ivf_sq8(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: int, d: int, n: int, lists_digest: str):
+    """-> (vmin float32 [d], vdiff float32 [d], codes uint8 [n, d] in list order, rnorm float32 [n]) from a valid SQ8 sidecar
+    written for these lists (``ivf_digest``), nlist, metric, pack mode and exponent and shape, else None."""
+    path = os.path.join(index_dir, IVF_SQ8_SIDECAR)
+    if not os.path.exists(path):
+        return None
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            header = json.loads(str(z["header"]))
+            vmin, vdiff, codes, rnorm = np.array(z["vmin"]), np.array(z["vdiff"]), np.array(z["codes"]), np.array(z["rnorm"])
+    except (OSError, ValueError, KeyError, TypeError):
+        return None
+    want = {"version": IVF_SQ8_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
+            "d": int(d), "n": int(n), "lists": str(lists_digest)}
+    if not isinstance(header, dict) or any(header.get(key) != val for key, val in want.items()):
+        return None
+    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
+        return None
+    if (vmin.shape != (d,) or vdiff.shape != (d,) or vmin.dtype != np.float32 or vdiff.dtype != np.float32
+            or codes.shape != (n, d) or codes.dtype != np.uint8 or rnorm.shape != (n,) or rnorm.dtype != np.float32):
+        return None
+    return vmin, vdiff, codes, rnorm

@@ -17,7 +17,7 @@ Differences that are deliberate supersets (SURVEY.md section 8(a) edge-case tabl
     per-shard top-k lists are merged after one all-gather (RCCL over xGMI on GPUs);
   * ``factory_string="IVF<nlist>,Flat"`` builds the inverted-file index ``FaissVS`` advertises but cannot train
     (``faiss_vs.py:23-24`` calls ``add()`` without ``train()``): plain searches probe ``nprobe`` lists, everything else
-    stays exact (see ``HipVS``).
+    stays exact (see ``HipVS``); ``"IVF<nlist>,SQ8"`` adds faiss's 8-bit residual scalar quantizer on top of the same lists.
 """
 from __future__ import annotations
 
@@ -53,6 +53,7 @@ class _Resident:
     hi: int
     sig: Any = None  # store.signature() of the directory when it was loaded (None: never persisted)
     ivf: Any = None  # backend IvfLists over `packed` (IVF stores only): centroids, offsets, row numbers
+    sq8: Any = None  # backend IvfSq8Lists beside `ivf` (IVF-SQ8 stores only): codec and codes in list order
 
 
 def _serialised(fn):
@@ -102,6 +103,13 @@ class HipVS(VS):
             directory is written as for ``"Flat"`` plus an ``ivf.npz`` sidecar that a reload uses instead of retraining.
             Single GPU only: any ``shard`` but ``False`` is refused.  Rows too wide for the list scan's LDS image (hi|lo storage:
             d > 1088, fp16: d > 2240; ``HipBackend.ivf_fits``) and ``nprobe`` > 2 048 are searched exactly.
+            ``"IVF<nlist>,SQ8"`` - the same centroids and lists, with every row also kept as 8-bit codes of its residual
+            (faiss's ``ScalarQuantizer`` ``QT_8bit`` with ``by_residual``: per-dimension ranges trained on the residuals of
+            the k-means training rows, one byte per dimension): a plain search scores each probed row as its decoded value
+            ``c_l + rhat`` (``HipBackend.ivf_sq8_search``), up to d = 2368 whatever the storage; the exact fallbacks are
+            IVF-Flat's, against the full-precision rows, which stay resident.  The directory is written as for
+            ``"IVF<nlist>,Flat"`` (so such a store of the same nlist reuses its ``ivf.npz``) plus ``ivf_sq8.npz`` with the
+            codec and the codes; ``sq8_codes()`` returns them.
         nprobe: lists probed per query (faiss's default 1).
     """
 
@@ -110,13 +118,15 @@ class HipVS(VS):
                  normalize: bool = False, abi_exchange: bool = False, factory_string: str = "Flat", nprobe: int = 1,
                  ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256) -> None:
         super().__init__()
-        m = re.fullmatch(r"IVF([0-9]+),Flat", factory_string) if isinstance(factory_string, str) else None
+        m = re.fullmatch(r"IVF([0-9]+),(Flat|SQ8)", factory_string) if isinstance(factory_string, str) else None
         if factory_string != "Flat" and (m is None or int(m.group(1)) < 1):
-            raise ValueError(f"factory_string must be 'Flat' or 'IVF<nlist>,Flat' (nlist >= 1), got {factory_string!r}")
+            raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' (nlist >= 1), "
+                             f"got {factory_string!r}")
         self.factory_string = factory_string
         self._nlist = int(m.group(1)) if m is not None else None
+        self._sq8 = m is not None and m.group(2) == "SQ8"
         if self._nlist is not None and shard is not False:
-            raise ValueError("an IVF index is single-GPU: shard must be False with factory_string='IVF<nlist>,Flat'")
+            raise ValueError(f"an IVF index is single-GPU: shard must be False with factory_string={factory_string!r}")
         self.nprobe = self._check_nprobe(nprobe)
         self.ivf_niter = int(ivf_niter)
         self.ivf_max_points_per_centroid = ivf_max_points_per_centroid
@@ -348,7 +358,7 @@ class HipVS(VS):
         ent = self._install(index_dir, emb, stored=None if is_dev else emb,
                             sig=store.signature(index_dir) if persist else None)
         if self._nlist is not None:
-            ent.ivf = self._ivf_train(ent)
+            ent.ivf, ent.sq8 = self._ivf_train(ent)
             if persist:
                 self._ivf_write(index_dir, ent, best_effort=False)
         self.index_dir = index_dir
@@ -369,11 +379,18 @@ class HipVS(VS):
         ent = self._install(index_dir, rows, stored=None, sig=sig)
         if self._nlist is not None and ent.n:
             side = store.read_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, ent.d, ent.n)
-            if side is not None:
+            side8 = None
+            if side is not None and self._sq8:
+                side8 = store.read_ivf_sq8(index_dir, self._nlist, self.metric, ent.packed.mode, ent.packed.exp, ent.d, ent.n,
+                                           store.ivf_digest(*side))
+            if side is not None and (side8 is not None or not self._sq8):
                 c, off, rr = side
                 ent.ivf = self.backend.ivf_build(ent.packed, c, self.metric, offsets=off, rows=rr)
-            else:  # missing, stale or built for another nlist / metric: train again and try to leave a valid sidecar behind
-                ent.ivf = self._ivf_train(ent)
+                if side8 is not None:
+                    vmin, vdiff, codes, rnorm = side8
+                    ent.sq8 = self.backend.ivf_sq8_encode(ent.packed, ent.ivf, vmin, vdiff, codes=codes, rnorm=rnorm)
+            else:  # missing, stale or built for another nlist / metric: train again and try to leave valid sidecars behind
+                ent.ivf, ent.sq8 = self._ivf_train(ent)
                 self._ivf_write(index_dir, ent, best_effort=True)
         self.index_dir = index_dir
 
@@ -436,7 +453,9 @@ class HipVS(VS):
         # sem_search's K-doubling loop (sem_search.py:120-138) once the probed lists hold fewer than K rows
         nprobe = min(self._check_nprobe(kwargs.get("nprobe", self.nprobe)), ent.ivf.nlist) if ent.ivf is not None else 0
         use_ivf = (ent.ivf is not None and sub is None and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
-                   and qworld == 1 and nprobe <= _capi.MAX_K and be.ivf_fits(ent.d, K, ent.packed.mode))
+                   and qworld == 1 and nprobe <= _capi.MAX_K
+                   and (be.ivf_sq8_fits(ent.d, K, ent.packed.mode) if ent.sq8 is not None
+                        else be.ivf_fits(ent.d, K, ent.packed.mode)))
         q_all = nq
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
             per = -(-nq // qworld)
@@ -495,6 +514,8 @@ class HipVS(VS):
             if order is not None:
                 id_map = be.to_device(order)
             world = 1  # already complete on every rank: nothing left to merge
+        elif use_ivf and ent.sq8 is not None:
+            keys = be.ivf_sq8_search(ent.packed, ent.ivf, ent.sq8, queries, k_eff, self.metric, nprobe)
         elif use_ivf:
             keys = be.ivf_search(ent.packed, ent.ivf, queries, k_eff, self.metric, nprobe)
         elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
@@ -560,9 +581,11 @@ class HipVS(VS):
         return int(nprobe)
 
     def _ivf_train(self, ent: _Resident):
-        """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store; None without rows."""
+        """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store, and for an SQ8
+        store the codec trained on the residuals of the k-means training rows and the codes -> (lists, sq8 or None);
+        (None, None) without rows."""
         if ent.n == 0:
-            return None
+            return None, None
         from . import cluster
 
         be = self.backend
@@ -571,7 +594,11 @@ class HipVS(VS):
                              max_points_per_centroid=self.ivf_max_points_per_centroid, backend=be, packed=ent.packed,
                              final_assign=False)
         # rows go to their best centroid under the index's metric, against the final centroids (faiss's IVF quantizer)
-        return be.ivf_build(ent.packed, np.asarray(res.centroids, dtype=np.float32), self.metric)
+        lists = be.ivf_build(ent.packed, np.asarray(res.centroids, dtype=np.float32), self.metric)
+        if not self._sq8:
+            return lists, None
+        vmin, vdiff = be.ivf_sq8_train(ent.packed, lists, res.train_ids)
+        return lists, be.ivf_sq8_encode(ent.packed, lists, vmin, vdiff)
 
     def _ivf_write(self, index_dir: str, ent: _Resident, best_effort: bool) -> None:
         if ent.ivf is None:
@@ -579,6 +606,11 @@ class HipVS(VS):
         c, off, rows = self._ivf_host(ent.ivf)
         try:
             store.write_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, c, off, rows)
+            if ent.sq8 is not None:
+                sq = ent.sq8
+                store.write_ivf_sq8(index_dir, self._nlist, self.metric, ent.packed.mode, sq.exp,
+                                    sq.vmin.cpu().numpy(), sq.vdiff.cpu().numpy(), sq.codes[:, :ent.d].cpu().numpy(),
+                                    sq.rnorm.cpu().numpy(), store.ivf_digest(c, off, rows))
         except OSError:
             if not best_effort:
                 raise
@@ -616,12 +648,33 @@ class HipVS(VS):
         queries = be.pack(q, ent.packed.mode, normalize=self.normalize, exp=ent.packed.exp, check=True)
         if queries.n == 0:
             return np.zeros((0, nprobe), np.int32)
-        if be.ivf_fits(ent.d, 1, ent.packed.mode):
+        if ent.sq8 is not None and be.ivf_sq8_fits(ent.d, 1, ent.packed.mode):
+            _, probe = be.ivf_sq8_search(ent.packed, ent.ivf, ent.sq8, queries, 1, self.metric, nprobe, want_probe=True)
+            return probe.cpu().numpy()
+        if ent.sq8 is None and be.ivf_fits(ent.d, 1, ent.packed.mode):
             _, probe = be.ivf_search(ent.packed, ent.ivf, queries, 1, self.metric, nprobe, want_probe=True)
             return probe.cpu().numpy()
         # the coarse step on its own: lvs_flat_search_keys over the centroids, as inside lvs_ivf_search_keys
         keys = be.search_keys(ent.ivf.centroids, queries, nprobe, self.metric, one_pass=False).cpu().numpy().view(np.uint64)
         return np.where(keys == 0, -1, 0xFFFFFFFF - (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int32)
+
+    @_serialised
+    def sq8_codes(self):
+        """-> (vmin float32 [d], vdiff float32 [d], codes uint8 [n, d] in ROW order, residual norms float32 [n]) of an
+        IVF-SQ8 store, in the caller's units: row i decodes to ``c_l + vmin + (codes[i] + 0.5) * vdiff / 255`` (``l``: its
+        list in ``ivf_lists()``, ``c_l`` its centroid there), and ``norms[i]`` is ``|vmin + (codes[i] + 0.5) * vdiff / 255|^2``
+        as the device computed it in fp32."""
+        ent = self._ivf_current()
+        if ent.sq8 is None:
+            raise ValueError("the loaded index has no SQ8 codes (factory_string is not 'IVF<nlist>,SQ8')")
+        sq = ent.sq8
+        scale = np.float32(2.0) ** -sq.exp  # exact: the stored scale is a power of two
+        rows = ent.ivf.rows.cpu().numpy().view(np.uint32).astype(np.int64)
+        codes = np.empty((ent.n, ent.d), np.uint8)
+        codes[rows] = sq.codes[:, :ent.d].cpu().numpy()
+        rnorm = np.empty(ent.n, np.float32)
+        rnorm[rows] = sq.rnorm.cpu().numpy() * (scale * scale)
+        return sq.vmin.cpu().numpy() * scale, sq.vdiff.cpu().numpy() * scale, codes, rnorm
 
     @staticmethod
     def _fp32_path(ent, q) -> bool:
