@@ -12,10 +12,12 @@ Inputs are SURVEY.md 8(d)'s recipe (benchdata.py): numpy streams SeedSequence([2
 blocks, generated on the host - anyone can rebuild the inputs of a BENCH line.
 
 Prints ONE JSON line on rank 0 (see the contract in the task statement): value = Q * steps / time in queries/s.
-Extra objects:
+A plain run does only what that figure needs: inputs, warm-up, the timed steps, `--dump-outputs`, the line.  Its extra
+figures come from the last timed step and the timed steps' own events - `planted_neighbour_at_rank1` and:
   "roofline"      dominant kernel vs the dense fp16 MFMA peak, timed with HIP events on the launch stream;
                   `traffic` = HBM-side bytes per launch from the committed rocprofv3 PMC passes, reported only when the
-                  kernel sources are byte-identical to the ones the counters were collected on (else null);
+                  kernel sources are byte-identical to the ones the counters were collected on (else null).
+`--full` adds everything else, after the timed steps:
   "cpu_baseline"  (N=1) the CPU comparators (C + OpenMP twin and torch-MKL, both timed, the faster reported) on a bounded
                   sample of the same workload;
   "recall_at_k" / "id_mismatches_outside_near_ties" / "max_abs_score_err": the GPU result of the LAST timed step checked
@@ -26,7 +28,7 @@ Extra objects:
                   and the 8-way merge (`world8_rehearsal`), configs[3] (threshold self-join with planted duplicates),
                   configs[4] (k-means, full-data iteration and faiss-parity mode), fp32 embeddings, and T_call
                   (`HipVS.__call__` host ndarray -> host (D, I)).
-All GPU work runs first and back to back; the CPU-side checks and the CPU baseline follow.
+All GPU work of `--full` runs first and back to back; the CPU-side checks and the CPU baseline follow.
 
 The stdout line is kept below 6 KB (floats at 5 significant digits, one short object per leg, the figures that matter once
 more in a flat `legs_summary` printed LAST) so that a tail of the line still holds every leg; the verbose form of the same
@@ -92,6 +94,9 @@ def parse():
     ap.add_argument("--corpus", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle check, the CPU baseline and the secondary legs "
+                         "(--cpu-sample ... --kmeans-k shape them; a plain run ignores those options)")
     ap.add_argument("--cpu-sample", type=int, default=8192, help="queries timed on the CPU comparator (N=1 only)")
     ap.add_argument("--check-sample", type=int, default=512, help="queries re-checked against the CPU oracle (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -206,7 +211,7 @@ def main():
 
     be = HipBackend(device)
     n, d, nq, k = args.corpus, args.dim, args.queries, args.k
-    legs_on = world == 1 and not args.no_legs
+    legs_on = args.full and world == 1 and not args.no_legs
 
     # ---- inputs (host, numpy streams).  The other configs' rows are drawn by background threads while the GPU works on
     # the headline (numpy releases the GIL), so the GPU legs below run back to back ----
@@ -334,45 +339,46 @@ def main():
                          "csrc_sha": csrc_hash()},
         }
         details = {"gen_s": gen_s, "hbm_frac_secondary": alg_bytes / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBS}
-        n_chk = max(args.check_sample, args.cpu_sample if (world == 1 and not args.no_cpu_baseline) else 0, 1)
-        D_h, I_h = D[:n_chk].cpu().numpy(), I[:n_chk].cpu().numpy()
-        chk_rows = check_rows(np, nq, args.check_sample)
-        chk_dev = torch.from_numpy(chk_rows).to(device)
-        D_chk, I_chk = D[chk_dev].cpu().numpy(), I[chk_dev].cpu().numpy()
-        checks = []  # CPU-side work deferred until every GPU leg has run
-        legs = {}
-        if legs_on:
-            ctx = dict(np=np, torch=torch, be=be, _capi=_capi, xb_h=xb_h, xq_h=xq_h, corpus=corpus, queries=queries, k=k,
-                       d=d, keys=keys, args=args)
-            search_legs(ctx, legs)
-            node_plan_legs(ctx, legs)
-            world8_rehearsal(ctx, legs, checks)
-            for fut in (fut_dedup, fut_km):  # the legs below have the HOST in their timed region (T_call stages host memory
-                if fut is not None:          # with a few threads; the certified fp32 search reads one count back per call): let
-                    fut.result()             # the generators of the other configs' rows (up to 64 threads on a 16-CPU quota)
-            fp32_leg(ctx, legs)              # finish first - with them running the fp32 10 k x 1 M call measured 18.4 instead
-            t_call_leg(ctx, legs)            # of 16.1 ms on the same box (gpurun_out/r07d vs r07e)
-            t_op_leg(ctx, legs)
-            if fut_dedup is not None:
-                dedup_leg(ctx, legs, checks, fut_dedup)
-            if fut_km is not None:
-                kmeans_legs(ctx, legs, checks, fut_km)
-        be.synchronize()
-        # ---- CPU side ----
-        if args.check_sample > 0:
-            out.update(oracle_check(np, xb_h, xq_h, D_chk, I_chk, chk_rows, k))
-        for fn in checks:
-            fn()
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(np, xb_h, xq_h, args.cpu_sample, k, D_h, I_h)
-        if legs.get("t_call_host_to_host"):
-            # SURVEY.md 8(d) calls T_call - VS.__call__(host ndarray) -> host (D, I), corpus resident - "the queries/sec figure"; the
-            # bench contract wants `value` device-resident.  Both are on the line's top level
-            out["value_t_call"] = legs["t_call_host_to_host"]["queries_per_s"]
-            out["value_t_call_note"] = "host ndarray in -> host (D, I) out through HipVS.__call__ (PCIe + packing included), median of 5"
-        if legs:
-            out["legs"] = legs
-            out["legs_summary"] = legs_summary(out, legs)  # printed LAST: the tail of the line holds the figures that matter
+        if args.full:  # checks, CPU baseline and legs: after the timed steps, never in a plain run
+            n_chk = max(args.check_sample, args.cpu_sample if (world == 1 and not args.no_cpu_baseline) else 0, 1)
+            D_h, I_h = D[:n_chk].cpu().numpy(), I[:n_chk].cpu().numpy()
+            chk_rows = check_rows(np, nq, args.check_sample)
+            chk_dev = torch.from_numpy(chk_rows).to(device)
+            D_chk, I_chk = D[chk_dev].cpu().numpy(), I[chk_dev].cpu().numpy()
+            checks = []  # CPU-side work deferred until every GPU leg has run
+            legs = {}
+            if legs_on:
+                ctx = dict(np=np, torch=torch, be=be, _capi=_capi, xb_h=xb_h, xq_h=xq_h, corpus=corpus, queries=queries, k=k,
+                           d=d, keys=keys, args=args)
+                search_legs(ctx, legs)
+                node_plan_legs(ctx, legs)
+                world8_rehearsal(ctx, legs, checks)
+                for fut in (fut_dedup, fut_km):  # the legs below have the HOST in their timed region (T_call stages host memory
+                    if fut is not None:          # with a few threads; the certified fp32 search reads one count back per call): let
+                        fut.result()             # the generators of the other configs' rows (up to 64 threads on a 16-CPU quota)
+                fp32_leg(ctx, legs)              # finish first - with them running the fp32 10 k x 1 M call measured 18.4 instead
+                t_call_leg(ctx, legs)            # of 16.1 ms, two runs on the same box
+                t_op_leg(ctx, legs)
+                if fut_dedup is not None:
+                    dedup_leg(ctx, legs, checks, fut_dedup)
+                if fut_km is not None:
+                    kmeans_legs(ctx, legs, checks, fut_km)
+            be.synchronize()
+            # ---- CPU side ----
+            if args.check_sample > 0:
+                out.update(oracle_check(np, xb_h, xq_h, D_chk, I_chk, chk_rows, k))
+            for fn in checks:
+                fn()
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(np, xb_h, xq_h, args.cpu_sample, k, D_h, I_h)
+            if legs.get("t_call_host_to_host"):
+                # SURVEY.md 8(d) calls T_call - VS.__call__(host ndarray) -> host (D, I), corpus resident - "the queries/sec figure"; the
+                # bench contract wants `value` device-resident.  Both are on the line's top level
+                out["value_t_call"] = legs["t_call_host_to_host"]["queries_per_s"]
+                out["value_t_call_note"] = "host ndarray in -> host (D, I) out through HipVS.__call__ (PCIe + packing included), median of 5"
+            if legs:
+                out["legs"] = legs
+                out["legs_summary"] = legs_summary(out, legs)  # printed LAST: the tail of the line holds the figures that matter
         details["line"] = out
         print("BENCH_DETAILS " + json.dumps(sig(details, 7)), file=sys.stderr, flush=True)
         print(json.dumps(sig(compact(out))), flush=True)

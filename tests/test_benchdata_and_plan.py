@@ -207,6 +207,18 @@ def test_bench_dumps_the_last_steps_result_within_the_size_cap(tmp_path, monkeyp
     assert data_bytes <= bench.DUMP_MAX_BYTES
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain run is the headline only; the oracle check, the CPU baseline and the legs need --full."""
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True
+
+
 def test_bench_rejects_zero_timed_steps(monkeypatch):
     import sys
 

@@ -97,7 +97,7 @@ def test_bench_self_launches_its_ranks_and_prints_one_line(gpus, split, queries,
     # through the chunked register-resident path and pooled thresholds, and the query split with 2 560 queries per rank; RCCL
     # itself cannot run here - two ranks on one device are refused - so the transport under rehearsal is gloo)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-                        "--queries", str(queries), "--corpus", str(corpus), "--check-sample", "128", "--split", split],
+                        "--queries", str(queries), "--corpus", str(corpus), "--check-sample", "128", "--split", split, "--full"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -12,8 +12,8 @@ for w in $what; do
     pykm) timeout -k 10 900 python -m pytest tests/test_gpu_kmeans.py -m gpu -q --timeout 600 -p no:cacheprovider > $out/pytest_km.log 2>&1; tail -15 $out/pytest_km.log ;;
     pyacc) timeout -k 10 600 python -m pytest tests/test_gpu_kmeans.py -m gpu -q -k "accumulate or counting or objective or golden or bounds" --timeout 600 -p no:cacheprovider > $out/pytest_acc.log 2>&1; tail -3 $out/pytest_acc.log ;;
     pydur) timeout -k 10 900 python -m pytest tests/test_gpu_dist.py tests/test_gpu_parity.py -m gpu -q -k "rccl or ranking or rank_all or 2d_split" --durations=12 --timeout 600 -p no:cacheprovider > $out/pytest_dur.log 2>&1; tail -25 $out/pytest_dur.log ;;
-    bench) timeout -k 10 900 python bench.py > $out/bench.json 2> $out/bench.err; tail -c 1500 $out/bench.json; echo; tail -5 $out/bench.err ;;
-    benchq) timeout -k 10 600 python bench.py --dedup-rows 0 $BENCHQ_ARGS --no-cpu-baseline > $out/bench_quick.json 2> $out/bench_quick.err; tail -c 1500 $out/bench_quick.json; echo; tail -5 $out/bench_quick.err ;;
+    bench) timeout -k 10 900 python bench.py --full > $out/bench.json 2> $out/bench.err; tail -c 1500 $out/bench.json; echo; tail -5 $out/bench.err ;;
+    benchq) timeout -k 10 600 python bench.py --full --dedup-rows 0 $BENCHQ_ARGS --no-cpu-baseline > $out/bench_quick.json 2> $out/bench_quick.err; tail -c 1500 $out/bench_quick.json; echo; tail -5 $out/bench_quick.err ;;
     prof) SKIP_BENCH=1 timeout -k 10 1500 tools/profile_bench.sh $tag/prof > $out/prof.log 2>&1; tail -30 $out/prof.log ;;
     kern) timeout -k 10 1500 tools/profile_kernels.sh $tag/kern $KERN_SCEN > $out/kern.log 2>&1; tail -30 $out/kern.log ;;
     kmprof) timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kmprof -o km -- python tools/kmeans_iter_workload.py > $out/kmprof.log 2>&1; tail -5 $out/kmprof.log ;;
@@ -31,7 +31,7 @@ for w in $what; do
     overlap) timeout -k 10 600 python tools/overlap_probe.py > $out/overlap.log 2>&1; grep " ms" $out/overlap.log ;;
     seedpool) make -C lotus_amd/csrc tuning -j8 > $out/tuning_build.log 2>&1; timeout -k 10 600 python tools/seed_pool_sweep.py > $out/seedpool.log 2>&1; grep "tiles per shard" $out/seedpool.log ;;
     kmparts) timeout -k 10 600 python tools/km_parts_probe.py > $out/kmparts.log 2>&1; grep -v "^\[" $out/kmparts.log | tail -20 ;;
-    bench2) LOTUS_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 > $out/bench2.json 2> $out/bench2.err; tail -c 1800 $out/bench2.json; echo; tail -5 $out/bench2.err ;;
+    bench2) LOTUS_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --full > $out/bench2.json 2> $out/bench2.err; tail -c 1800 $out/bench2.json; echo; tail -5 $out/bench2.err ;;
     ab) for i in 1 2; do for l in lotus_amd/liblotus_hip.so lotus_amd/liblotus_hip_prevtile.so; do timeout -k 10 300 python tools/ab_probe.py $l 2>&1 | grep "fp16 100k" >> $out/ab.log; done; done; cat $out/ab.log ;;
     k12) timeout -k 10 200 python tools/fp32_k12_probe.py > $out/k12.log 2>&1; grep "per call" $out/k12.log ;;
     tcall) timeout -k 10 600 python tools/tcall_probe.py > $out/tcall.log 2>&1; cat $out/tcall.log ;;
@@ -43,7 +43,7 @@ for w in $what; do
     rq) timeout -k 10 600 python tools/rq_probe.py > $out/rq.log 2>&1; grep -v "^\[" $out/rq.log | tail -40 ;;
     rqg) timeout -k 10 900 python tools/rq_groups_probe.py > $out/rqg.log 2>&1; grep -v "^\[\|amdgpu.ids" $out/rqg.log | tail -50 ;;
     rqab) timeout -k 10 600 python tools/rq_ablate.py > $out/rqab.log 2>&1; grep -v "amdgpu.ids" $out/rqab.log | tail -30 ;;
-    bench2self) LOTUS_BENCH_REHEARSAL=1 timeout -k 10 900 python bench.py --gpus 2 --steps 3 --warmup 1 > $out/bench2.json 2> $out/bench2.err; tail -c 2500 $out/bench2.json; echo; grep -v "amdgpu.ids\|OMP_NUM\|\*\*\*" $out/bench2.err | tail -5 ;;
+    bench2self) LOTUS_BENCH_REHEARSAL=1 timeout -k 10 900 python bench.py --gpus 2 --steps 3 --warmup 1 --full > $out/bench2.json 2> $out/bench2.err; tail -c 2500 $out/bench2.json; echo; grep -v "amdgpu.ids\|OMP_NUM\|\*\*\*" $out/bench2.err | tail -5 ;;
     smoke) timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > $out/smoke.log 2>&1; tail -3 $out/smoke.log ;;
     *) echo "unknown step $w" ;;
   esac

@@ -1,4 +1,4 @@
-"""Re-fit the split planner's shipped tables (lotus_amd/plan_tables.json) from a bench.py line.
+"""Re-fit the split planner's shipped tables (lotus_amd/plan_tables.json) from a `bench.py --full` line (it needs the legs).
 usage: python tools/refit_plan.py gpurun_out/<tag>/bench.json [label]"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
