@@ -43,7 +43,8 @@ extern "C" {
                              7 + additive: IVF-Flat lists and search (lvs_ivf_build_workspace_bytes, lvs_ivf_build_lists,
                                 lvs_ivf_search_workspace_bytes, lvs_ivf_search_keys, LVS_KERNEL_IVF) - no existing entry changed;
                                 IVF-SQ8 codes and search (lvs_ivf_sq8_encode, lvs_ivf_sq8_search_workspace_bytes,
-                                lvs_ivf_sq8_search_keys, LVS_KERNEL_IVF_SQ8) */
+                                lvs_ivf_sq8_search_keys, LVS_KERNEL_IVF_SQ8); IVF-PQ codes and search (lvs_ivf_pq_encode,
+                                lvs_ivf_pq_search_workspace_bytes, lvs_ivf_pq_search_keys, LVS_KERNEL_IVF_PQ) */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -480,6 +481,42 @@ int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norm
                                 int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                 void* stream);
 
+/* ---- IVF-PQ: IVF-Flat's lists and coarse step, the rows scored from product-quantizer codes of their residuals (faiss
+ * "IVF<nlist>,PQ<M>": ProductQuantizer with 8-bit codes, by_residual).  dsub = d / M (d % M == 0), codebooks [M][ksub][dsub]
+ * fp32, 1 <= ksub <= 256, trained by the caller:
+ *   r = x - c_l,  code_m = argmin_{j < ksub} |r_m - codebooks[m][j]|^2 (fp32, ties to the smaller j),
+ *   rhat = concat_m codebooks[m][code_m],  beta = |rhat|^2 + 2 <c_l, rhat> (fp32).
+ * Every array is in the rows' stored scale (the packed values x 2^exp, as lvs_unpack_rows with the pack exponent).  Codes
+ * are kept in LIST order: position p of the `rows` array of lvs_ivf_build_lists, ldc = M rounded up to 16 bytes per row.
+ * ---- */
+/* codes of every list position: out_codes [n][ldc] uint8 (bytes past M are 0), out_beta [n] fp32.  xb: the packed image;
+ * offsets [nlist + 1] / rows [n]: the lists (n = offsets[nlist]); centroids [nlist][d] fp32.  Everything on `stream`, no
+ * synchronisation. */
+int32_t lvs_ivf_pq_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets, const uint32_t* rows,
+                          int32_t nlist, const float* centroids, int32_t M, int32_t ksub, const float* codebooks,
+                          uint8_t* out_codes, float* out_beta, void* stream);
+/* scratch of lvs_ivf_pq_search_keys (chunked: at most 512 MB, the per-query lookup tables of M KB included).  LVS_EUNSUPPORTED:
+ * the scan keeps one query's fp32 table (M x 256 x 4 bytes) and its list in LDS: M > 159, whatever d and k - search such
+ * shapes with lvs_flat_search_keys; lvs_ivf_pq_search_keys returns the same status for them.  LVS_EINVAL: bad arguments,
+ * d % M != 0 among them. */
+int64_t lvs_ivf_pq_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k,
+                                          int32_t pack);
+/* IVF-PQ search, everything on `stream`, no synchronisation:
+ *   1. coarse step: exactly lvs_ivf_search_keys's (centroids packed with c_pack, c_norms_sq) -> the same probes;
+ *   2. lvs_ivf_pq_lut_kernel: per query LUT[m][j] = <q_m, codebooks[m][j]> (fp32);
+ *   3. lvs_ivf_pq_scan_kernel: per query and range of its probes, the lists' codes looked up in the query's table; a row
+ *      scores as its decoded value c_l + rhat under `metric`: inner product <q, c_l> + sum_m LUT[m][code_m], squared L2
+ *      |q - c_l|^2 + beta - 2 sum_m LUT[m][code_m] (centroids_f32 [nlist][d]: the fp32 values of the packed centroids);
+ *   4. lvs_merge_keys -> out_keys [nq][k], keys as lvs_ivf_search_keys (global row numbers; rows with equal codes in one
+ *      list score alike and come out in ascending row order).  Slots past the probed lists' rows are key 0.
+ * out_probe (nullable): [nq][nprobe] int32 list ids of the probes.  1 <= nprobe <= nlist, 1 <= k <= 56. */
+int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M, int32_t ksub,
+                               const int64_t* offsets, const uint32_t* rows, int64_t nb, int32_t nlist, const void* centroids,
+                               int32_t c_pack, const float* c_norms_sq, const float* centroids_f32, const void* xq,
+                               int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe,
+                               int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+
 /* ---- measurement hook: average duration in ms of the dominant search kernel's launches since the last reset,
  * measured with HIP events on the launch stream (enabled with lvs_timing_enable(1)). ---- */
 int32_t lvs_timing_enable(int32_t on);
@@ -493,6 +530,8 @@ int32_t lvs_timing_read(double* out_total_ms, int64_t* out_launches);
 #define LVS_KERNEL_RJ 3     /* lvs_rj_kernel: 64 queries per wave resident in registers, one wave per SIMD */
 #define LVS_KERNEL_IVF 4    /* lvs_ivf_scan_kernel: one inverted list x up to 32 probing queries (lvs_ivf_search_keys) */
 #define LVS_KERNEL_IVF_SQ8 5 /* lvs_ivf_sq8_scan_kernel: one list's 8-bit codes x up to 16 probing queries (lvs_ivf_sq8_search_keys) */
+#define LVS_KERNEL_IVF_PQ 6 /* lvs_ivf_pq_lut_kernel + lvs_ivf_pq_scan_kernel: one query's table x its probed lists' PQ codes
+                               (lvs_ivf_pq_search_keys) */
 int32_t lvs_timing_read_calls(double* out_total_ms, int64_t* out_launches, int64_t* out_calls, int32_t* out_kernel);
 
 #ifdef __cplusplus

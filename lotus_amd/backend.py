@@ -57,6 +57,24 @@ def ivf_sq8_fits(d: int, k: int, mode: int) -> bool:
     return int(_capi.load().lvs_ivf_sq8_search_workspace_bytes(1, 1, 1, int(d), int(k), int(mode))) >= 0
 
 
+@dataclass
+class IvfPqLists:
+    """The product-quantizer codes of an IVF-PQ index beside its ``IvfLists``, all in the image's stored scale (values x 2^exp)."""
+
+    M: int               # subspaces (d % M == 0), dsub = d / M
+    ksub: int            # codebook entries per subspace (256, fewer with fewer training rows)
+    codebooks: "object"  # torch.Tensor float32 [M, ksub, dsub]
+    centroids: "object"  # torch.Tensor float32 [nlist, d]: the packed centroids' values
+    codes: "object"      # torch.Tensor uint8 [n, ldc] in LIST order (position p of IvfLists.rows), ldc = M rounded up to 16
+    beta: "object"       # torch.Tensor float32 [n]: |rhat|^2 + 2 <c_l, rhat> per list position
+    exp: int             # the image's pack exponent
+
+
+def ivf_pq_fits(d: int, M: int, k: int, mode: int) -> bool:
+    """Host-only query of the library: does ``lvs_ivf_pq_search_keys`` take this dimension, M, k and pack mode?"""
+    return int(_capi.load().lvs_ivf_pq_search_workspace_bytes(1, 1, 1, int(d), int(M), int(k), int(mode))) >= 0
+
+
 class _DevBytes:
     """A raw device pointer as something ``torch.as_tensor`` understands (the all-gather callback of ``lvs_search_sharded``)."""
 
@@ -1062,6 +1080,91 @@ class HipBackend:
                 int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
         return (keys, probe) if want_probe else keys
 
+    # ---- IVF-PQ ----
+    PQ_SEED = 1234          # faiss's ClusteringParameters default, the same for every subspace
+    PQ_NITER = 25           # faiss's ProductQuantizer training defaults
+    PQ_MAX_POINTS_PER_CENTROID = 256
+
+    def ivf_pq_train(self, packed: PackedRows, lists: IvfLists, train_ids, M: int):
+        """-> codebooks float32 [M, ksub, d / M] device tensor in the stored scale: per subspace one k-means (squared L2,
+        ``ksub = min(256, training rows)`` centroids, 25 iterations, fixed seed) over the sub-vectors of the residuals x - c_l
+        of the training rows ``train_ids`` (host int64).  The subsample of 256 points per centroid is drawn once, as every
+        subspace's k-means would draw it with the same seed."""
+        from . import cluster
+
+        torch = self.torch
+        d = packed.d
+        dsub = d // M
+        ids = np.asarray(train_ids, dtype=np.int64)
+        ksub = min(256, len(ids))
+        cap = ksub * self.PQ_MAX_POINTS_PER_CENTROID
+        if len(ids) > cap:
+            ids = ids[self.rand_perm(len(ids), self.PQ_SEED, cap)]
+        c = self.unpack(lists.centroids, raw=True)
+        where = self._list_of_rows(lists, packed.n)
+        idd = self.to_device(ids)
+        r = (self.unpack(packed, idd, raw=True) - c[where[idd]]).cpu().numpy()
+        books = np.empty((M, ksub, dsub), np.float32)
+        for m in range(M):
+            res = cluster.kmeans(np.ascontiguousarray(r[:, m * dsub:(m + 1) * dsub]), ksub, niter=self.PQ_NITER,
+                                 seed=self.PQ_SEED, max_points_per_centroid=self.PQ_MAX_POINTS_PER_CENTROID, backend=self,
+                                 final_assign=False)
+            books[m] = res.centroids
+        return torch.as_tensor(books, device=self.device)
+
+    def ivf_pq_encode(self, packed: PackedRows, lists: IvfLists, codebooks, codes=None, beta=None) -> IvfPqLists:
+        """Codes of every list position (``lvs_ivf_pq_encode``) against ``codebooks`` [M, ksub, dsub] (stored scale).
+        ``codes`` / ``beta`` (host arrays, list order, codes [n, M]): encoded before (a persisted sidecar) - only uploaded."""
+        torch = self.torch
+        d = packed.d
+        books = codebooks if torch.is_tensor(codebooks) else torch.as_tensor(np.asarray(codebooks, np.float32))
+        books = books.to(device=self.device, dtype=torch.float32).contiguous()
+        if books.ndim != 3 or books.shape[0] < 1 or d % books.shape[0] != 0 or books.shape[2] != d // books.shape[0]:
+            raise ValueError(f"codebooks of shape {tuple(books.shape)} do not split d={d} into equal subspaces")
+        M, ksub = int(books.shape[0]), int(books.shape[1])
+        if not 1 <= ksub <= 256:
+            raise ValueError(f"ksub={ksub} must be in [1, 256] (8-bit codes)")
+        ldc = -(-M // 16) * 16
+        c = self.unpack(lists.centroids, raw=True).contiguous()
+        n = int(lists.rows.numel())
+        if codes is not None:
+            out = torch.zeros((n, ldc), dtype=torch.uint8, device=self.device)
+            out[:, :M] = self.to_device(np.ascontiguousarray(codes, dtype=np.uint8))
+            bt = self.to_device(np.ascontiguousarray(beta, dtype=np.float32))
+        else:
+            out = torch.empty((n, ldc), dtype=torch.uint8, device=self.device)
+            bt = torch.empty((n,), dtype=torch.float32, device=self.device)
+            self._c("lvs_ivf_pq_encode", _ptr(packed.rows), packed.mode, n, d, _ptr(lists.offsets), _ptr(lists.rows),
+                    lists.nlist, _ptr(c), M, ksub, _ptr(books), _ptr(out), _ptr(bt), self._stream())
+        return IvfPqLists(M=M, ksub=ksub, codebooks=books, centroids=c, codes=out, beta=bt, exp=int(packed.exp))
+
+    def ivf_pq_fits(self, d: int, M: int, k: int, mode: int) -> bool:
+        """Can the PQ list scan serve this shape?  Its LDS image (one query's fp32 table, M KB) bounds M (M <= 159);
+        callers search the other shapes exactly."""
+        return ivf_pq_fits(d, M, k, mode)
+
+    def ivf_pq_search(self, corpus: PackedRows, lists: IvfLists, pq: IvfPqLists, queries: PackedRows, k: int, metric: int,
+                      nprobe: int, want_probe: bool = False):
+        """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
+        query's ``nprobe`` best lists (``lvs_ivf_pq_search_keys``); key 0 past those rows."""
+        torch = self.torch
+        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
+            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
+        nq = queries.n
+        keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
+        need = int(self.lib.lvs_ivf_pq_search_workspace_bytes(nq, lists.nlist, nprobe, corpus.d, pq.M, k, queries.mode))
+        if need < 0:
+            raise LotusHipError(f"lvs_ivf_pq_search_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe} "
+                                f"M={pq.M} k={k}")
+        ws = self._workspace(need)
+        cpk = lists.centroids
+        self._c("lvs_ivf_pq_search_keys", _ptr(pq.codes), _ptr(pq.beta), _ptr(pq.codebooks), pq.M, pq.ksub,
+                _ptr(lists.offsets), _ptr(lists.rows), corpus.n, lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms),
+                _ptr(pq.centroids), _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
+                int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
+        return (keys, probe) if want_probe else keys
+
     def merge_keys(self, parts):
         """parts int64 [P, nq, k] -> [nq, k]."""
         torch = self.torch
@@ -1325,7 +1428,7 @@ class HipBackend:
         _capi.check(self.lib.lvs_timing_enable(int(on)))
 
     KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel", 4: "lvs_ivf_scan_kernel",
-                    5: "lvs_ivf_sq8_scan_kernel"}
+                    5: "lvs_ivf_sq8_scan_kernel", 6: "lvs_ivf_pq_scan_kernel"}
 
     def timing_read(self):
         """-> (total ms of the dominant kernel's launches, searches that timed at least one): total / searches = kernel time per

@@ -2363,3 +2363,181 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
     }
     return LVS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// IVF-PQ (lvs_ivf_pq.hip): the IVF-Flat lists and coarse step, the rows scored from product-quantizer codes
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// does the PQ scan's LDS image (one query's fp32 table of M x 256 entries + its list) fit?  M <= 159, whatever d and k
+bool ivf_pq_fits(int32_t M, int32_t k) { return lvs_ivf_pq_lds_bytes(M, lvs_ivf_kcap(k)) <= 160 * 1024; }
+
+struct PqLayout {
+    int64_t chunk;  // queries per chunk
+    int64_t off_coarse, off_lut, off_parts, flat_bytes, total;
+};
+
+// scratch of a chunk of `c` queries: [flat search scratch | coarse keys [c][nprobe] | tables [c][M][256] fp32 |
+// parts [<= nprobe][c][k]]
+bool pq_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k, int32_t c_pack, int32_t xq_pack,
+               PqLayout& L) {
+    L.chunk = c;
+    L.flat_bytes = lvs_flat_search_workspace_bytes(c, nlist, d, nprobe, c_pack, xq_pack);
+    if (L.flat_bytes < 0) return false;
+    const int64_t npairs = c * nprobe;
+    int64_t off = lvs_round_up(L.flat_bytes, 256);
+    L.off_coarse = off;
+    off += lvs_round_up(npairs * 8, 256);
+    L.off_lut = off;
+    off += lvs_round_up(c * M * LVS_PQ_KSUB * 4, 256);
+    L.off_parts = off;
+    off += lvs_round_up(npairs * k * 8, 256);
+    L.total = off;
+    return true;
+}
+
+// the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits
+bool pq_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k, int32_t c_pack, int32_t xq_pack,
+             PqLayout& L) {
+    int64_t c = nq < IVF_CHUNK_MAX ? nq : IVF_CHUNK_MAX;
+    if (c < 1) c = 1;
+    for (;;) {
+        if (!pq_layout(c, nlist, nprobe, d, M, k, c_pack, xq_pack, L)) return false;
+        if (L.total <= IVF_WS_BUDGET || c == 1) return c * nprobe < 0xFFFFFFFFll;
+        c = (c + 1) / 2;
+    }
+}
+
+// probes per scan workgroup: enough for ~2 048 rows of the average list (the table's staging and the first insertions are
+// paid once per workgroup), but no fewer than ~512 workgroups per chunk while the probes allow it; at most LVS_PQ_MAXRANGE
+int32_t pq_prange(int64_t nb, int32_t nlist, int64_t cn, int32_t nprobe) {
+    const int64_t avg = nb / nlist > 0 ? nb / nlist : 1;
+    int64_t pr = (2048 + avg - 1) / avg;
+    const int64_t by_blocks = cn * nprobe / 512;
+    if (pr > by_blocks) pr = by_blocks;
+    if (pr > LVS_PQ_MAXRANGE) pr = LVS_PQ_MAXRANGE;
+    if (pr > nprobe) pr = nprobe;
+    return pr < 1 ? 1 : (int32_t)pr;
+}
+}  // namespace
+
+extern "C" int32_t lvs_ivf_pq_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets,
+                                     const uint32_t* rows, int32_t nlist, const float* centroids, int32_t M, int32_t ksub,
+                                     const float* codebooks, uint8_t* out_codes, float* out_beta, void* stream) {
+    LVS_REQUIRE(n >= 0 && n < 0xFFFFFFFFll && d > 0, "bad shape n=%lld d=%d", (long long)n, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
+    LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
+    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    if (n == 0) return LVS_OK;
+    LVS_REQUIRE(xb && offsets && rows && centroids && codebooks && out_codes && out_beta, "NULL buffer");
+    LVS_DEVICE_GUARD(stream);
+    const int64_t dpad = lvs_round_up(d, LVS_BK);
+    const int64_t ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
+    LVS_HIP_CHECK(lvs_ivf_pq_encode_launch(xb, ldb, xb_pack == LVS_PACK_SPLIT, (int)dpad, n, d, M, ksub, offsets, nlist, rows,
+                                           centroids, codebooks, out_codes, out_beta, (hipStream_t)stream));
+    return LVS_OK;
+}
+
+extern "C" int64_t lvs_ivf_pq_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k,
+                                                     int32_t pack) {
+    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
+        return LVS_EINVAL;
+    if (M < 1 || d % M != 0) return LVS_EINVAL;
+    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
+    if (!ivf_pq_fits(M, k)) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
+    PqLayout L;
+    if (!pq_plan(nq, nlist, nprobe, d, M, k, pack, pack, L)) return LVS_EINVAL;
+    return L.total;
+}
+
+extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M,
+                                          int32_t ksub, const int64_t* offsets, const uint32_t* rows, int64_t nb, int32_t nlist,
+                                          const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                          const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
+                                          const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                          uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
+    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
+                (long long)nq, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
+    LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
+    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
+                nlist, LVS_MAX_K);
+    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
+    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
+    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    if (nq == 0) return LVS_OK;
+    LVS_REQUIRE(codes && codebooks && offsets && rows && centroids && centroids_f32 && xq && out_keys && workspace,
+                "NULL buffer");
+    LVS_REQUIRE(metric != LVS_METRIC_L2 || (beta && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
+    if (!ivf_pq_fits(M, k)) {
+        lvs_set_error("M=%d with k=%d does not fit the PQ list scan's LDS (see lvs_ivf_pq_search_workspace_bytes)", M, k);
+        return LVS_EUNSUPPORTED;
+    }
+    PqLayout L;
+    LVS_REQUIRE(pq_plan(nq, nlist, nprobe, d, M, k, c_pack, xq_pack, L), "shape beyond the IVF search");
+    if (workspace_bytes < L.total) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
+        return LVS_ENOMEM;
+    }
+    LVS_DEVICE_GUARD(stream);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)workspace;
+    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
+    float* lut = (float*)(w + L.off_lut);
+    u64* parts = (u64*)(w + L.off_parts);
+    const int64_t qdpad = lvs_round_up(d, LVS_BK);
+    const int64_t ldq = xq_pack == LVS_PACK_SPLIT ? 2 * qdpad : qdpad;
+
+    LvsIvfPqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.codes = codes;
+    a.beta = beta;
+    a.cent = centroids_f32;
+    a.rows = rows;
+    a.offsets = offsets;
+    a.lut = lut;
+    a.coarse = (const u64*)coarse;
+    a.out = parts;
+    a.ldq = ldq;
+    a.nlist = nlist;
+    a.nprobe = nprobe;
+    a.k = k;
+    a.metric = metric;
+    a.d = d;
+    a.M = M;
+    a.ldc = lvs_ivf_pq_ldc(M);
+    a.qsplit = xq_pack == LVS_PACK_SPLIT;
+    a.qdpad = (int)qdpad;
+    a.kcap = lvs_ivf_kcap(k);
+    const size_t qrow_bytes = (size_t)ldq * 2;
+    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
+        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
+        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
+        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
+        // 1. coarse step: exactly lvs_ivf_search_keys's
+        {
+            TimingPause pause;
+            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq,
+                                                    qn_c, 0, nullptr, coarse, w, L.flat_bytes, stream);
+            if (rc != LVS_OK) return rc;
+        }
+        if (out_probe) LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, cn * nprobe, out_probe + q0 * nprobe, st));
+        // 2. + 3. the queries' tables, then the query-major scan: one part per range of probes
+        a.prange = pq_prange(nb, nlist, cn, nprobe);
+        const int32_t nranges = (nprobe + a.prange - 1) / a.prange;
+        a.xq = xq_c;
+        a.nq = (int)cn;
+        {
+            ScopedKernelTimer timer(st, LVS_KERNEL_IVF_PQ, q0 > 0);
+            LVS_HIP_CHECK(lvs_ivf_pq_lut_launch(xq_c, ldq, a.qsplit, a.qdpad, cn, d, M, ksub, codebooks, lut, st));
+            LVS_HIP_CHECK(lvs_ivf_pq_scan_launch(a, st));
+        }
+        // 4. merge the per-range lists
+        const int32_t rc = lvs_merge_keys((const uint64_t*)parts, nranges, cn, k, out_keys + q0 * k, stream);
+        if (rc != LVS_OK) return rc;
+    }
+    return LVS_OK;
+}

@@ -354,6 +354,34 @@ hipError_t lvs_ivf_sq8_encode_launch(const void* xb, int64_t ldb, int split, int
 // launches 2 x max_items blocks (max_items: lvs_ivf_max_items of the 32-pair work items)
 hipError_t lvs_ivf_sq8_scan_launch(const LvsIvfSq8Args& a, int64_t max_items, hipStream_t stream);
 
+// ---- lvs_ivf_pq.hip: the product-quantizer codec of IVF-PQ (8-bit codes) and its query-major list scan.  A workgroup is one
+// query and a range of up to LVS_PQ_MAXRANGE of its probes; the codes are in list order. ----
+#define LVS_PQ_KSUB 256      // lookup-table entries per subspace (8-bit codes; codebooks may hold fewer)
+#define LVS_PQ_WAVES 8
+#define LVS_PQ_MAXRANGE 16   // probes per workgroup of the scan
+struct LvsIvfPqArgs {
+    const uint8_t* codes;        // [n][ldc] codes in list order (position p of `rows`)
+    const float* beta;           // [n] |rhat|^2 + 2 <c_l, rhat> per position (L2 only)
+    const float* cent;           // [nlist][d] fp32 centroids (the stored scale)
+    const uint32_t* rows;        // [n] row numbers, list after list
+    const int64_t* offsets;      // [nlist + 1]
+    const void* xq;              // packed queries of this chunk [nq][ldq]
+    const float* lut;            // [nq][M][LVS_PQ_KSUB] lookup tables of this chunk
+    const u64* coarse;           // [nq][nprobe] coarse keys (lvs_flat_search_keys over the centroids)
+    u64* out;                    // [nranges][nq][k]
+    long long ldq;
+    int nq, nlist, nprobe, prange, k, metric, d, M, ldc, qsplit, qdpad, kcap;
+};
+size_t lvs_ivf_pq_lds_bytes(int M, int kcap);
+int lvs_ivf_pq_ldc(int M);  // code bytes per row: M rounded up to a multiple of 16
+hipError_t lvs_ivf_pq_encode_launch(const void* xb, int64_t ldb, int split, int xdpad, int64_t n, int d, int M, int ksub,
+                                    const int64_t* offsets, int nlist, const uint32_t* rows, const float* cent,
+                                    const float* codebooks, uint8_t* codes, float* beta, hipStream_t stream);
+hipError_t lvs_ivf_pq_lut_launch(const void* xq, int64_t ldq, int split, int qdpad, int64_t nq, int d, int M, int ksub,
+                                 const float* codebooks, float* lut, hipStream_t stream);
+// launches ceil(nprobe / prange) x nq workgroups
+hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream);
+
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);
 int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, int* out_groups);

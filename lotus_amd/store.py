@@ -378,3 +378,61 @@ def read_ivf_sq8(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: i
             or codes.shape != (n, d) or codes.dtype != np.uint8 or rnorm.shape != (n,) or rnorm.dtype != np.float32):
         return None
     return vmin, vdiff, codes, rnorm
+
+
+# ---- IVF-PQ sidecar -----------------------------------------------------------------------------------------------------
+# An IVF-PQ store (HipVS(factory_string="IVF<nlist>,PQ<M>")) writes everything an IVF-Flat store writes - ``ivf.npz``
+# included - plus ``{dir}/ivf_pq.npz``: the codebooks (in the stored scale of the recorded pack exponent) and the codes and
+# beta terms in list order.  Like ``ivf_sq8.npz`` it is stamped and names the lists it was encoded against (``ivf_digest``).
+IVF_PQ_SIDECAR = "ivf_pq.npz"
+IVF_PQ_VERSION = 1
+
+
+def write_ivf_pq(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: int, codebooks: np.ndarray, codes: np.ndarray,
+                 beta: np.ndarray, lists_digest: str) -> None:
+    """Write the PQ sidecar atomically (temporary file + rename)."""
+    M, ksub, dsub = (int(v) for v in codebooks.shape)
+    header = {"version": IVF_PQ_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
+              "d": M * dsub, "M": M, "ksub": ksub, "n": int(codes.shape[0]), "lists": str(lists_digest),
+              "written_with": _file_stamps(index_dir)}
+    import tempfile
+
+    fd, tmp = tempfile.mkstemp(prefix="ivf_pq.", suffix=".npz.tmp", dir=index_dir)
+    try:
+        with os.fdopen(fd, "wb") as fp:
+            np.savez(fp, header=np.array(json.dumps(header)), codebooks=np.ascontiguousarray(codebooks, dtype=np.float32),
+                     codes=np.ascontiguousarray(codes, dtype=np.uint8), beta=np.ascontiguousarray(beta, dtype=np.float32))
+        os.replace(tmp, os.path.join(index_dir, IVF_PQ_SIDECAR))
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
+
+def read_ivf_pq(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: int, d: int, M: int, n: int, lists_digest: str):
+    """-> (codebooks float32 [M, ksub, d / M], codes uint8 [n, M] in list order, beta float32 [n]) from a valid PQ sidecar
+    written for these lists (``ivf_digest``), nlist, metric, pack mode, exponent, M and shape, else None."""
+    path = os.path.join(index_dir, IVF_PQ_SIDECAR)
+    if not os.path.exists(path):
+        return None
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            header = json.loads(str(z["header"]))
+            books, codes, beta = np.array(z["codebooks"]), np.array(z["codes"]), np.array(z["beta"])
+    except (OSError, ValueError, KeyError, TypeError):
+        return None
+    want = {"version": IVF_PQ_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
+            "d": int(d), "M": int(M), "n": int(n), "lists": str(lists_digest)}
+    if not isinstance(header, dict) or any(header.get(key) != val for key, val in want.items()):
+        return None
+    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
+        return None
+    ksub = header.get("ksub")
+    if (not isinstance(ksub, int) or not 1 <= ksub <= 256 or M < 1 or d % M != 0
+            or books.shape != (M, ksub, d // M) or books.dtype != np.float32
+            or codes.shape != (n, M) or codes.dtype != np.uint8 or beta.shape != (n,) or beta.dtype != np.float32
+            or (n and int(codes.max(initial=0)) >= ksub)):
+        return None
+    return books, codes, beta

@@ -17,7 +17,8 @@ Differences that are deliberate supersets (SURVEY.md section 8(a) edge-case tabl
     per-shard top-k lists are merged after one all-gather (RCCL over xGMI on GPUs);
   * ``factory_string="IVF<nlist>,Flat"`` builds the inverted-file index ``FaissVS`` advertises but cannot train
     (``faiss_vs.py:23-24`` calls ``add()`` without ``train()``): plain searches probe ``nprobe`` lists, everything else
-    stays exact (see ``HipVS``); ``"IVF<nlist>,SQ8"`` adds faiss's 8-bit residual scalar quantizer on top of the same lists.
+    stays exact (see ``HipVS``); ``"IVF<nlist>,SQ8"`` adds faiss's 8-bit residual scalar quantizer on top of the same lists,
+    ``"IVF<nlist>,PQ<M>"`` faiss's residual product quantizer (8-bit codes, M bytes per row).
 """
 from __future__ import annotations
 
@@ -54,6 +55,7 @@ class _Resident:
     sig: Any = None  # store.signature() of the directory when it was loaded (None: never persisted)
     ivf: Any = None  # backend IvfLists over `packed` (IVF stores only): centroids, offsets, row numbers
     sq8: Any = None  # backend IvfSq8Lists beside `ivf` (IVF-SQ8 stores only): codec and codes in list order
+    pq: Any = None  # backend IvfPqLists beside `ivf` (IVF-PQ stores only): codebooks and codes in list order
 
 
 def _serialised(fn):
@@ -110,6 +112,16 @@ class HipVS(VS):
             IVF-Flat's, against the full-precision rows, which stay resident.  The directory is written as for
             ``"IVF<nlist>,Flat"`` (so such a store of the same nlist reuses its ``ivf.npz``) plus ``ivf_sq8.npz`` with the
             codec and the codes; ``sq8_codes()`` returns them.
+            ``"IVF<nlist>,PQ<M>"`` (or ``"PQ<M>x8"``) - the same centroids and lists, with every row also kept as M one-byte
+            codes of its residual (faiss's ``ProductQuantizer`` with 8-bit codes and ``by_residual``: d / M-dimensional
+            subspaces, one k-means codebook of ``min(256, training rows)`` entries per subspace, trained on the residuals of
+            the k-means training rows).  A plain search builds each query's lookup table once and scores each probed row as
+            its decoded value ``c_l + rhat`` from M table lookups (``HipBackend.ivf_pq_search``); the scan's cost follows M,
+            not d, so 3 072-dimensional rows are served.  ``index()`` / ``load_index()`` refuse rows whose d M does not
+            divide; M > 159 (the table outgrows LDS) is searched exactly, as are IVF-Flat's exact fallbacks, against the
+            full-precision rows, which stay resident.  The directory is written as for ``"IVF<nlist>,Flat"`` plus
+            ``ivf_pq.npz`` with the codebooks and the codes; ``pq_codes()`` returns them.  Other code sizes (``PQ<M>x4``,
+            ``x4fs``) are refused.
         nprobe: lists probed per query (faiss's default 1).
     """
 
@@ -118,13 +130,19 @@ class HipVS(VS):
                  normalize: bool = False, abi_exchange: bool = False, factory_string: str = "Flat", nprobe: int = 1,
                  ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256) -> None:
         super().__init__()
-        m = re.fullmatch(r"IVF([0-9]+),(Flat|SQ8)", factory_string) if isinstance(factory_string, str) else None
-        if factory_string != "Flat" and (m is None or int(m.group(1)) < 1):
-            raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' (nlist >= 1), "
-                             f"got {factory_string!r}")
+        m = (re.fullmatch(r"IVF([0-9]+),(Flat|SQ8|PQ([0-9]+)(?:x8)?)", factory_string) if isinstance(factory_string, str)
+             else None)
+        if factory_string != "Flat" and (m is None or int(m.group(1)) < 1 or (m.group(3) is not None and int(m.group(3)) < 1)):
+            raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' or 'IVF<nlist>,PQ<M>[x8]' "
+                             f"(nlist >= 1, M >= 1, 8-bit codes), got {factory_string!r}")
+        # an injected backend without the IVF-PQ codec (a test double of an earlier mode) cannot build such a store
+        if m is not None and m.group(3) is not None and backend is not None and not hasattr(backend, "ivf_pq_search"):
+            raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' with a backend that has "
+                             f"no IVF-PQ codec ({type(backend).__name__}), got {factory_string!r}")
         self.factory_string = factory_string
         self._nlist = int(m.group(1)) if m is not None else None
         self._sq8 = m is not None and m.group(2) == "SQ8"
+        self._pq_m = int(m.group(3)) if m is not None and m.group(3) is not None else None  # M of an IVF-PQ store
         if self._nlist is not None and shard is not False:
             raise ValueError(f"an IVF index is single-GPU: shard must be False with factory_string={factory_string!r}")
         self.nprobe = self._check_nprobe(nprobe)
@@ -343,6 +361,7 @@ class HipVS(VS):
         device image).  Rank 0 writes the reference's two files plus the mappable row store (``lotus_amd/store.py``);
         ``persist=False`` skips the disk entirely, ``raw=False`` writes the reference's files only."""
         emb = self._as_matrix(embeddings, "embeddings")
+        self._check_pq_width(int(emb.shape[1]))
         rank, world = self._group()  # under the query split every rank holds the whole corpus, but only ONE may write it
         persist = bool(kwargs.get("persist", True))
         is_dev = self._is_device_tensor(emb)
@@ -358,7 +377,8 @@ class HipVS(VS):
         ent = self._install(index_dir, emb, stored=None if is_dev else emb,
                             sig=store.signature(index_dir) if persist else None)
         if self._nlist is not None:
-            ent.ivf, ent.sq8 = self._ivf_train(ent)
+            ent.ivf, codec = self._ivf_train(ent)
+            ent.sq8, ent.pq = (None, codec) if self._pq_m is not None else (codec, None)
             if persist:
                 self._ivf_write(index_dir, ent, best_effort=False)
         self.index_dir = index_dir
@@ -376,6 +396,7 @@ class HipVS(VS):
         sig = store.signature(index_dir)
         rows, _ = store.open_device_rows(index_dir)
         rows = self._as_matrix(rows, "stored vectors")
+        self._check_pq_width(int(rows.shape[1]))
         ent = self._install(index_dir, rows, stored=None, sig=sig)
         if self._nlist is not None and ent.n:
             side = store.read_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, ent.d, ent.n)
@@ -383,14 +404,22 @@ class HipVS(VS):
             if side is not None and self._sq8:
                 side8 = store.read_ivf_sq8(index_dir, self._nlist, self.metric, ent.packed.mode, ent.packed.exp, ent.d, ent.n,
                                            store.ivf_digest(*side))
-            if side is not None and (side8 is not None or not self._sq8):
+            sidepq = None
+            if side is not None and self._pq_m is not None:
+                sidepq = store.read_ivf_pq(index_dir, self._nlist, self.metric, ent.packed.mode, ent.packed.exp, ent.d,
+                                           self._pq_m, ent.n, store.ivf_digest(*side))
+            if side is not None and (side8 is not None or not self._sq8) and (sidepq is not None or self._pq_m is None):
                 c, off, rr = side
                 ent.ivf = self.backend.ivf_build(ent.packed, c, self.metric, offsets=off, rows=rr)
                 if side8 is not None:
                     vmin, vdiff, codes, rnorm = side8
                     ent.sq8 = self.backend.ivf_sq8_encode(ent.packed, ent.ivf, vmin, vdiff, codes=codes, rnorm=rnorm)
+                if sidepq is not None:
+                    books, codes, beta = sidepq
+                    ent.pq = self.backend.ivf_pq_encode(ent.packed, ent.ivf, books, codes=codes, beta=beta)
             else:  # missing, stale or built for another nlist / metric: train again and try to leave valid sidecars behind
-                ent.ivf, ent.sq8 = self._ivf_train(ent)
+                ent.ivf, codec = self._ivf_train(ent)
+                ent.sq8, ent.pq = (None, codec) if self._pq_m is not None else (codec, None)
                 self._ivf_write(index_dir, ent, best_effort=True)
         self.index_dir = index_dir
 
@@ -455,6 +484,7 @@ class HipVS(VS):
         use_ivf = (ent.ivf is not None and sub is None and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
                    and qworld == 1 and nprobe <= _capi.MAX_K
                    and (be.ivf_sq8_fits(ent.d, K, ent.packed.mode) if ent.sq8 is not None
+                        else be.ivf_pq_fits(ent.d, ent.pq.M, K, ent.packed.mode) if ent.pq is not None
                         else be.ivf_fits(ent.d, K, ent.packed.mode)))
         q_all = nq
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
@@ -516,6 +546,8 @@ class HipVS(VS):
             world = 1  # already complete on every rank: nothing left to merge
         elif use_ivf and ent.sq8 is not None:
             keys = be.ivf_sq8_search(ent.packed, ent.ivf, ent.sq8, queries, k_eff, self.metric, nprobe)
+        elif use_ivf and ent.pq is not None:
+            keys = be.ivf_pq_search(ent.packed, ent.ivf, ent.pq, queries, k_eff, self.metric, nprobe)
         elif use_ivf:
             keys = be.ivf_search(ent.packed, ent.ivf, queries, k_eff, self.metric, nprobe)
         elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
@@ -582,8 +614,8 @@ class HipVS(VS):
 
     def _ivf_train(self, ent: _Resident):
         """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store, and for an SQ8
-        store the codec trained on the residuals of the k-means training rows and the codes -> (lists, sq8 or None);
-        (None, None) without rows."""
+        store the codec trained on the residuals of the k-means training rows and the codes -> (lists, sq8 or None); for
+        a PQ store likewise its codebooks and codes -> (lists, pq); (None, None) without rows."""
         if ent.n == 0:
             return None, None
         from . import cluster
@@ -595,6 +627,9 @@ class HipVS(VS):
                              final_assign=False)
         # rows go to their best centroid under the index's metric, against the final centroids (faiss's IVF quantizer)
         lists = be.ivf_build(ent.packed, np.asarray(res.centroids, dtype=np.float32), self.metric)
+        if self._pq_m is not None:
+            books = be.ivf_pq_train(ent.packed, lists, res.train_ids, self._pq_m)
+            return lists, be.ivf_pq_encode(ent.packed, lists, books)
         if not self._sq8:
             return lists, None
         vmin, vdiff = be.ivf_sq8_train(ent.packed, lists, res.train_ids)
@@ -611,6 +646,10 @@ class HipVS(VS):
                 store.write_ivf_sq8(index_dir, self._nlist, self.metric, ent.packed.mode, sq.exp,
                                     sq.vmin.cpu().numpy(), sq.vdiff.cpu().numpy(), sq.codes[:, :ent.d].cpu().numpy(),
                                     sq.rnorm.cpu().numpy(), store.ivf_digest(c, off, rows))
+            if ent.pq is not None:
+                pq = ent.pq
+                store.write_ivf_pq(index_dir, self._nlist, self.metric, ent.packed.mode, pq.exp, pq.codebooks.cpu().numpy(),
+                                   pq.codes[:, :pq.M].cpu().numpy(), pq.beta.cpu().numpy(), store.ivf_digest(c, off, rows))
         except OSError:
             if not best_effort:
                 raise
@@ -651,7 +690,10 @@ class HipVS(VS):
         if ent.sq8 is not None and be.ivf_sq8_fits(ent.d, 1, ent.packed.mode):
             _, probe = be.ivf_sq8_search(ent.packed, ent.ivf, ent.sq8, queries, 1, self.metric, nprobe, want_probe=True)
             return probe.cpu().numpy()
-        if ent.sq8 is None and be.ivf_fits(ent.d, 1, ent.packed.mode):
+        if ent.pq is not None and be.ivf_pq_fits(ent.d, ent.pq.M, 1, ent.packed.mode):
+            _, probe = be.ivf_pq_search(ent.packed, ent.ivf, ent.pq, queries, 1, self.metric, nprobe, want_probe=True)
+            return probe.cpu().numpy()
+        if ent.sq8 is None and ent.pq is None and be.ivf_fits(ent.d, 1, ent.packed.mode):
             _, probe = be.ivf_search(ent.packed, ent.ivf, queries, 1, self.metric, nprobe, want_probe=True)
             return probe.cpu().numpy()
         # the coarse step on its own: lvs_flat_search_keys over the centroids, as inside lvs_ivf_search_keys
@@ -675,6 +717,29 @@ class HipVS(VS):
         rnorm = np.empty(ent.n, np.float32)
         rnorm[rows] = sq.rnorm.cpu().numpy() * (scale * scale)
         return sq.vmin.cpu().numpy() * scale, sq.vdiff.cpu().numpy() * scale, codes, rnorm
+
+    @_serialised
+    def pq_codes(self):
+        """-> (codebooks float32 [M, ksub, d / M], codes uint8 [n, M] in ROW order, beta float32 [n]) of an IVF-PQ store, in
+        the caller's units: row i decodes to ``c_l + concat_m codebooks[m, codes[i, m]]`` (``l``: its list in
+        ``ivf_lists()``, ``c_l`` its centroid there), and ``beta[i]`` is ``|rhat|^2 + 2 <c_l, rhat>`` of that decoded residual
+        as the device computed it in fp32."""
+        ent = self._ivf_current()
+        if ent.pq is None:
+            raise ValueError("the loaded index has no PQ codes (factory_string is not 'IVF<nlist>,PQ<M>')")
+        pq = ent.pq
+        scale = np.float32(2.0) ** -pq.exp  # exact: the stored scale is a power of two
+        rows = ent.ivf.rows.cpu().numpy().view(np.uint32).astype(np.int64)
+        codes = np.empty((ent.n, pq.M), np.uint8)
+        codes[rows] = pq.codes[:, :pq.M].cpu().numpy()
+        beta = np.empty(ent.n, np.float32)
+        beta[rows] = pq.beta.cpu().numpy() * (scale * scale)
+        return pq.codebooks.cpu().numpy() * scale, codes, beta
+
+    def _check_pq_width(self, d: int) -> None:
+        """faiss asserts d % M == 0 for a product quantizer: rows of another width cannot back an IVF-PQ store."""
+        if self._pq_m is not None and d % self._pq_m != 0:
+            raise ValueError(f"factory_string={self.factory_string!r} needs a dimension divisible by M={self._pq_m}, got d={d}")
 
     @staticmethod
     def _fp32_path(ent, q) -> bool:

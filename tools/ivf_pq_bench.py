@@ -1,0 +1,160 @@
+"""IVF-PQ against IVF-SQ8, IVF-Flat and the exact path on one MI355X: 1 M rows, nlist 4 096, M = 64, nprobe in {8, 32, 128},
+k = 10, for d = 768 and d = 3072 (text-embedding-3-large's width) stored as hi|lo.
+
+Per workload, column (exact, IVF-Flat and IVF-SQ8 where their list scans take the width, IVF-PQ) and nprobe, for 1 and
+10 000 queries:
+  * wall ms per call: host clock around a call that ends with the results on the host, median of the timed calls;
+  * kernel ms per call: lvs_timing_read_calls (HIP events around the dominant kernel: for IVF-PQ the table kernel and
+    lvs_ivf_pq_scan_kernel together, for the others their list scan or the flat path's search kernel; the split between the
+    two PQ kernels comes from a rocprofv3 --kernel-trace --stats run of this tool);
+  * hbm_share: bytes of the probed rows as the scan reads them (PQ: M code bytes per row; SQ8: d; IVF-Flat: 2 or 4 bytes
+    per dimension) over 8 TB/s, over kernel time - 1 query: every probed row once; 10 000 queries: the union of the probed
+    lists once (a lower bound);
+  * recall@10 against the exact search on benchdata's configs[2] rows (uniform: the worst case for IVF) and on a seeded
+    clustered set (benchdata.blobs).
+Prints one JSON document (and writes it to --out)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_BPS = 8e12
+
+
+def timed(vs, q, k, reps, warmup, **kw):
+    be = vs.backend
+    for _ in range(warmup):
+        vs(q, k, **kw)
+    be.synchronize()
+    be.timing_enable(True)
+    walls = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        vs(q, k, **kw)
+        walls.append((time.perf_counter() - t0) * 1e3)
+    t = be.timing_read_full()
+    be.timing_enable(False)
+    return {"wall_ms": float(np.median(walls)), "kernel_ms": t["total_ms"] / max(1, t["calls"]), "kernel": t["kernel"]}
+
+
+def probed_rows(vs, q, nprobe):
+    """(sum over queries of the rows of their probed lists, rows of the union over all queries)."""
+    _, off, _ = vs.ivf_lists()
+    sizes = np.diff(off)
+    probe = vs.ivf_probe(q, nprobe)
+    return int(sizes[probe].sum()), int(sizes[np.unique(probe)].sum())
+
+
+def recall(a, b):
+    return float(np.mean([len(set(x) & set(y)) / len(x) for x, y in zip(a, b)]))
+
+
+def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
+    from lotus_amd import _capi
+
+    k = 10
+    mode = _capi.PACK_F16 if storage == "fp16" else _capi.PACK_SPLIT
+    dtype = np.float16 if storage == "fp16" else np.float32
+    res = {"n": a.n, "d": d, "storage": storage, "nlist": a.nlist, "k": k}
+    xb = benchdata.corpus(benchdata.CFG_SEARCH, a.n, d, dtype=dtype)
+    xq, _ = benchdata.queries(benchdata.CFG_SEARCH, xb, a.big, dtype=dtype)
+    exact = HipVS(storage=storage, device="cuda:0")
+    exact.index(None, xb, "bench-exact", persist=False)
+    kinds = {"pq": f"PQ{a.M}"}
+    if exact.backend.ivf_sq8_fits(d, k, mode):
+        kinds["sq8"] = "SQ8"
+    if exact.backend.ivf_fits(d, k, mode):
+        kinds["ivf_flat"] = "Flat"
+    res["M"] = a.M
+    stores = {}
+    for name, kind in kinds.items():
+        vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        vs.index(None, xb, f"bench-{name}", persist=False)
+        torch.cuda.synchronize()
+        res[f"{name}_build_s"] = time.perf_counter() - t0
+        stores[name] = vs
+    q1, qb = xq[:1], xq[:a.big]
+    res["exact"] = {"q1": timed(exact, q1, k, a.reps1, 5), f"q{a.big}": timed(exact, qb, k, a.repsbig, 1)}
+    ref = exact(xq[:a.recall_queries], k).indices
+    row_bytes = {"pq": a.M, "sq8": d, "ivf_flat": d * (2 if storage == "fp16" else 4)}
+    for name, vs in stores.items():
+        col = {}
+        for nprobe in a.nprobe:
+            r = {"q1": timed(vs, q1, k, a.reps1, 5, nprobe=nprobe), f"q{a.big}": timed(vs, qb, k, a.repsbig, 1, nprobe=nprobe)}
+            rows1, _ = probed_rows(vs, q1, nprobe)
+            pairs, union = probed_rows(vs, qb, nprobe)
+            r["q1"]["probed_rows"] = rows1
+            r["q1"]["hbm_share"] = rows1 * row_bytes[name] / HBM_BPS / (r["q1"]["kernel_ms"] * 1e-3)
+            r[f"q{a.big}"]["query_row_pairs"] = pairs
+            r[f"q{a.big}"]["union_rows"] = union
+            r[f"q{a.big}"]["hbm_share"] = union * row_bytes[name] / HBM_BPS / (r[f"q{a.big}"]["kernel_ms"] * 1e-3)
+            r["recall10_uniform"] = recall(vs(xq[:a.recall_queries], k, nprobe=nprobe).indices, ref)
+            r["speedup_q1_kernel_vs_exact"] = res["exact"]["q1"]["kernel_ms"] / r["q1"]["kernel_ms"]
+            r[f"speedup_q{a.big}_kernel_vs_exact"] = res["exact"][f"q{a.big}"]["kernel_ms"] / r[f"q{a.big}"]["kernel_ms"]
+            col[str(nprobe)] = r
+        res[name] = col
+    del exact, stores
+    torch.cuda.empty_cache()
+    if not a.skip_clustered:
+        xc, _ = benchdata.blobs(benchdata.CFG_KMEANS, a.n, d, a.nlist, dtype=dtype)
+        qc, _ = benchdata.queries(benchdata.CFG_KMEANS, xc, a.recall_queries, dtype=dtype)
+        exact = HipVS(storage=storage, device="cuda:0")
+        exact.index(None, xc, "bench-exact-c", persist=False)
+        ref = exact(qc, k).indices
+        del exact
+        for name, kind in kinds.items():
+            vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}")
+            vs.index(None, xc, f"bench-{name}-c", persist=False)
+            for nprobe in a.nprobe:
+                res[name][str(nprobe)]["recall10_clustered"] = recall(vs(qc, k, nprobe=nprobe).indices, ref)
+            del vs
+        torch.cuda.empty_cache()
+    return res
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--nlist", type=int, default=4096)
+    ap.add_argument("--nprobe", type=int, nargs="+", default=[8, 32, 128])
+    ap.add_argument("--M", type=int, default=64)
+    ap.add_argument("--workloads", nargs="+", default=["768:fp32", "3072:fp32"],
+                    help="d:storage pairs (storage fp16 or fp32 = hi|lo)")
+    ap.add_argument("--big", type=int, default=10_000)
+    ap.add_argument("--reps1", type=int, default=30)
+    ap.add_argument("--repsbig", type=int, default=5)
+    ap.add_argument("--recall-queries", type=int, default=1000)
+    ap.add_argument("--skip-clustered", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import torch
+
+    import benchdata
+    from lotus_amd import HipVS
+
+    if not torch.cuda.is_available():
+        raise SystemExit("ivf_pq_bench needs a GPU")
+    out = {"device": torch.cuda.get_device_name(0), "workloads": []}
+    for wl in a.workloads:
+        d, storage = wl.split(":")
+        out["workloads"].append(run_workload(int(d), storage, a, HipVS, benchdata, torch))
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fp:
+            fp.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
