@@ -987,21 +987,29 @@ class HipBackend:
                    want_probe: bool = False):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] list ids of the probes, best first): the exact
         top k over the rows of each query's ``nprobe`` best lists (``lvs_ivf_search_keys``); key 0 past those rows."""
+        cpk = lists.centroids
+        head = (_ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets), _ptr(lists.rows), lists.nlist,
+                _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms))
+        return self._ivf_search("lvs_ivf_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe)
+
+    def _ivf_search(self, entry: str, ws_extra: tuple, head: tuple, corpus: PackedRows, lists: IvfLists, queries: PackedRows,
+                    k: int, metric: int, nprobe: int, want_probe: bool):
+        """What the three IVF searches share: ``<entry>_keys`` with its scratch from ``<entry>_workspace_bytes``.
+        ``ws_extra``: the workspace function's arguments between d and k (PQ: M); ``head``: the entry point's arguments
+        ahead of the queries."""
         torch = self.torch
         if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
             raise ValueError("squared L2 needs both operands packed with the same scale exponent")
         nq = queries.n
         keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
-        need = int(self.lib.lvs_ivf_search_workspace_bytes(nq, lists.nlist, nprobe, corpus.d, k, queries.mode))
+        need = int(getattr(self.lib, entry + "_workspace_bytes")(nq, lists.nlist, nprobe, corpus.d, *ws_extra, k, queries.mode))
         if need < 0:
-            raise LotusHipError(f"lvs_ivf_search_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe} k={k}")
+            m = f" M={ws_extra[0]}" if ws_extra else ""
+            raise LotusHipError(f"{entry}_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe}{m} k={k}")
         ws = self._workspace(need)
-        cpk = lists.centroids
-        self._c("lvs_ivf_search_keys", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets),
-                _ptr(lists.rows), lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(queries.rows), queries.mode, nq,
-                _ptr(queries.norms), corpus.d, metric, int(nprobe), int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()),
-                self._stream())
+        self._c(entry + "_keys", *head, _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
+                int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
         return (keys, probe) if want_probe else keys
 
     # ---- IVF-SQ8 ----
@@ -1063,22 +1071,10 @@ class HipBackend:
                        nprobe: int, want_probe: bool = False):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
         query's ``nprobe`` best lists (``lvs_ivf_sq8_search_keys``); key 0 past those rows."""
-        torch = self.torch
-        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
-            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
-        nq = queries.n
-        keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
-        need = int(self.lib.lvs_ivf_sq8_search_workspace_bytes(nq, lists.nlist, nprobe, corpus.d, k, queries.mode))
-        if need < 0:
-            raise LotusHipError(f"lvs_ivf_sq8_search_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe} k={k}")
-        ws = self._workspace(need)
         cpk = lists.centroids
-        self._c("lvs_ivf_sq8_search_keys", _ptr(sq8.codes), _ptr(sq8.rnorm), _ptr(sq8.vmin), _ptr(sq8.vdiff),
-                _ptr(lists.offsets), _ptr(lists.rows), corpus.n, lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms),
-                _ptr(sq8.centroids), _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
-                int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
-        return (keys, probe) if want_probe else keys
+        head = (_ptr(sq8.codes), _ptr(sq8.rnorm), _ptr(sq8.vmin), _ptr(sq8.vdiff), _ptr(lists.offsets), _ptr(lists.rows), corpus.n,
+                lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(sq8.centroids))
+        return self._ivf_search("lvs_ivf_sq8_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe)
 
     # ---- IVF-PQ ----
     PQ_SEED = 1234          # faiss's ClusteringParameters default, the same for every subspace
@@ -1147,23 +1143,10 @@ class HipBackend:
                       nprobe: int, want_probe: bool = False):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
         query's ``nprobe`` best lists (``lvs_ivf_pq_search_keys``); key 0 past those rows."""
-        torch = self.torch
-        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
-            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
-        nq = queries.n
-        keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
-        need = int(self.lib.lvs_ivf_pq_search_workspace_bytes(nq, lists.nlist, nprobe, corpus.d, pq.M, k, queries.mode))
-        if need < 0:
-            raise LotusHipError(f"lvs_ivf_pq_search_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe} "
-                                f"M={pq.M} k={k}")
-        ws = self._workspace(need)
         cpk = lists.centroids
-        self._c("lvs_ivf_pq_search_keys", _ptr(pq.codes), _ptr(pq.beta), _ptr(pq.codebooks), pq.M, pq.ksub,
-                _ptr(lists.offsets), _ptr(lists.rows), corpus.n, lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms),
-                _ptr(pq.centroids), _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
-                int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
-        return (keys, probe) if want_probe else keys
+        head = (_ptr(pq.codes), _ptr(pq.beta), _ptr(pq.codebooks), pq.M, pq.ksub, _ptr(lists.offsets), _ptr(lists.rows), corpus.n,
+                lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(pq.centroids))
+        return self._ivf_search("lvs_ivf_pq_search", (pq.M,), head, corpus, lists, queries, k, metric, nprobe, want_probe)
 
     def merge_keys(self, parts):
         """parts int64 [P, nq, k] -> [nq, k]."""

@@ -2013,8 +2013,11 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
     return LVS_OK;
 }
 
+
 // ---------------------------------------------------------------------------------------------------------------
-// IVF-Flat (lvs_ivf.hip): inverted lists over the flat packed image, searched by probing nprobe lists per query
+// IVF: inverted lists over the flat packed image, searched by probing nprobe lists per query.  Three modes share the lists,
+// the coarse step and the host driver below and differ in how a list's rows are scored: IVF-Flat (lvs_ivf.hip) from the
+// rows themselves, IVF-SQ8 (lvs_ivf_sq8.hip) from 8-bit residual codes, IVF-PQ (lvs_ivf_pq.hip) from product-quantizer codes
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 // the timing hook reports the list scan: the coarse step's own flat search is not timed
@@ -2038,34 +2041,47 @@ bool ivf_fits(int32_t d, int32_t k, int32_t xq_pack) {
     const int nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper;
     return lvs_ivf_lds_bytes(nbfrag, lvs_ivf_kcap(k)) <= 160 * 1024;
 }
+// does the SQ8 scan's LDS image (the tile's w fragments, hi|lo whatever the query's pack mode, + its lists) fit?
+bool ivf_sq8_fits(int32_t d, int32_t k) {
+    return lvs_ivf_sq8_lds_bytes(lvs_ivf_sq8_ldc(d), lvs_ivf_kcap(k)) <= 160 * 1024;
+}
+// does the PQ scan's LDS image (one query's fp32 table of M x 256 entries + its list) fit?  M <= 159, whatever d and k
+bool ivf_pq_fits(int32_t M, int32_t k) { return lvs_ivf_pq_lds_bytes(M, lvs_ivf_kcap(k)) <= 160 * 1024; }
 
 constexpr int64_t IVF_WS_BUDGET = 512ll << 20;  // scratch of one call; more queries go through in chunks
 constexpr int64_t IVF_CHUNK_MAX = 16384;
 
 struct IvfLayout {
     int64_t chunk;  // queries per chunk
-    int64_t off_coarse, off_sort, off_tiles, off_items, off_parts, flat_bytes, sort_bytes, max_items, total;
+    int64_t off_coarse, off_extra, off_sort, off_tiles, off_items, off_parts, flat_bytes, sort_bytes, max_items, total;
 };
 
-// scratch of a chunk of `c` queries: [flat search scratch | coarse keys [c][nprobe] | bucket sort | tile offsets | work items
-// | parts [nprobe][c][k]]
-bool ivf_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack, IvfLayout& L) {
+// scratch of a chunk of `c` queries: [flat search scratch | coarse keys [c][nprobe] | the mode's own region, extra_per_q
+// bytes per query (PQ: tables [c][M][256] fp32) | tiled modes (Flat, SQ8): bucket sort | tile offsets | work items
+// | parts [<= nprobe][c][k]]
+bool ivf_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
+                int64_t extra_per_q, bool tiled, IvfLayout& L) {
     L.chunk = c;
     L.flat_bytes = lvs_flat_search_workspace_bytes(c, nlist, d, nprobe, c_pack, xq_pack);
     if (L.flat_bytes < 0) return false;
     const int64_t npairs = c * nprobe;
-    L.sort_bytes = lvs_bucket_workspace_bytes(npairs, nlist);
-    if (L.sort_bytes < 0) return false;
-    L.max_items = lvs_ivf_max_items(npairs, nlist);
     int64_t off = lvs_round_up(L.flat_bytes, 256);
     L.off_coarse = off;
     off += lvs_round_up(npairs * 8, 256);
-    L.off_sort = off;
-    off += lvs_round_up(L.sort_bytes, 256);
-    L.off_tiles = off;
-    off += lvs_round_up((int64_t)(nlist + 1) * 4, 256);
-    L.off_items = off;
-    off += lvs_round_up(L.max_items * 4, 256);
+    L.off_extra = off;
+    off += lvs_round_up(c * extra_per_q, 256);
+    L.off_sort = L.off_tiles = L.off_items = off;
+    L.sort_bytes = L.max_items = 0;
+    if (tiled) {
+        L.sort_bytes = lvs_bucket_workspace_bytes(npairs, nlist);
+        if (L.sort_bytes < 0) return false;
+        L.max_items = lvs_ivf_max_items(npairs, nlist);
+        off += lvs_round_up(L.sort_bytes, 256);
+        L.off_tiles = off;
+        off += lvs_round_up((int64_t)(nlist + 1) * 4, 256);
+        L.off_items = off;
+        off += lvs_round_up(L.max_items * 4, 256);
+    }
     L.off_parts = off;
     off += lvs_round_up(npairs * k * 8, 256);
     L.total = off;
@@ -2073,14 +2089,142 @@ bool ivf_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, 
 }
 
 // the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits
-bool ivf_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack, IvfLayout& L) {
+bool ivf_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
+              int64_t extra_per_q, bool tiled, IvfLayout& L) {
     int64_t c = nq < IVF_CHUNK_MAX ? nq : IVF_CHUNK_MAX;
     if (c < 1) c = 1;
     for (;;) {
-        if (!ivf_layout(c, nlist, nprobe, d, k, c_pack, xq_pack, L)) return false;
+        if (!ivf_layout(c, nlist, nprobe, d, k, c_pack, xq_pack, extra_per_q, tiled, L)) return false;
         if (L.total <= IVF_WS_BUDGET || c == 1) return c * nprobe < 0xFFFFFFFFll;
         c = (c + 1) / 2;
     }
+}
+
+// what the three *_search_workspace_bytes share.  M: PQ's subspaces (1 otherwise); fits: the mode's LDS check
+int64_t ivf_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k, int32_t pack, bool fits,
+                            int64_t extra_per_q, bool tiled) {
+    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
+        return LVS_EINVAL;
+    if (M < 1 || d % M != 0) return LVS_EINVAL;
+    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
+    if (!fits) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
+    IvfLayout L;
+    if (!ivf_plan(nq, nlist, nprobe, d, k, pack, pack, extra_per_q, tiled, L)) return LVS_EINVAL;
+    return L.total;
+}
+
+// the argument checks of the three searches, in the order they are reported.  A mode without rows of its own passes
+// xb_pack = LVS_PACK_F16, a mode without a product quantizer M = ksub = 1: those checks then always hold
+int32_t ivf_check_search(int32_t metric, int64_t nb, int64_t nq, int32_t d, int32_t nlist, int32_t M, int32_t ksub,
+                         int32_t nprobe, int32_t k, int32_t xb_pack, int32_t xq_pack, int32_t c_pack) {
+    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
+    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
+                (long long)nq, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
+    LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
+    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
+                nlist, LVS_MAX_K);
+    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
+    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
+    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    return LVS_OK;
+}
+
+// the arguments the three searches hand to the driver unchanged
+struct IvfSearch {
+    int32_t nlist;
+    const void* centroids;
+    int32_t c_pack;
+    const float* c_norms_sq;
+    const void* xq;
+    int32_t xq_pack;
+    int64_t nq;
+    const float* xq_norms_sq;
+    int32_t d, metric, nprobe, k;
+    uint64_t* out_keys;
+    int32_t* out_probe;
+    void* workspace;
+    int64_t workspace_bytes;
+    void* stream;
+};
+
+// The host driver of the three searches: plan the scratch, then per chunk of queries the coarse step (the nprobe best
+// centroids of every query under the index's metric), the probe ids, the mode's scan and the merge of its parts.
+// scan(L, w, q0, cn, xq_c, qn_c, coarse, parts, nparts) launches the scan of queries [q0, q0 + cn) under its own
+// ScopedKernelTimer (q0 > 0: a continuation) and may lower nparts, the lists per query that it fills (nprobe on entry).
+template <class Scan>
+int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, Scan scan) {
+    IvfLayout L;
+    LVS_REQUIRE(ivf_plan(s.nq, s.nlist, s.nprobe, s.d, s.k, s.c_pack, s.xq_pack, extra_per_q, tiled, L),
+                "shape beyond the IVF search");
+    if (s.workspace_bytes < L.total) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
+        return LVS_ENOMEM;
+    }
+    LVS_DEVICE_GUARD(s.stream);
+    hipStream_t st = (hipStream_t)s.stream;
+    char* w = (char*)s.workspace;
+    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
+    u64* parts = (u64*)(w + L.off_parts);
+    const size_t qrow_bytes = (size_t)lvs_round_up(s.d, LVS_BK) * (s.xq_pack == LVS_PACK_SPLIT ? 2 : 1) * 2;
+    for (int64_t q0 = 0; q0 < s.nq; q0 += L.chunk) {
+        const int64_t cn = s.nq - q0 < L.chunk ? s.nq - q0 : L.chunk;
+        const void* xq_c = (const char*)s.xq + (size_t)q0 * qrow_bytes;
+        const float* qn_c = s.xq_norms_sq ? s.xq_norms_sq + q0 : nullptr;
+        {
+            TimingPause pause;
+            const int32_t rc = lvs_flat_search_keys(s.centroids, s.c_pack, s.nlist, xq_c, s.xq_pack, cn, s.d, s.metric, s.nprobe,
+                                                    s.c_norms_sq, qn_c, 0, nullptr, coarse, w, L.flat_bytes, s.stream);
+            if (rc != LVS_OK) return rc;
+        }
+        if (s.out_probe)
+            LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, cn * s.nprobe, s.out_probe + q0 * s.nprobe, st));
+        int32_t nparts = s.nprobe;
+        int32_t rc = scan(L, w, q0, cn, xq_c, qn_c, coarse, parts, nparts);
+        if (rc != LVS_OK) return rc;
+        rc = lvs_merge_keys((const uint64_t*)parts, nparts, cn, s.k, s.out_keys + q0 * s.k, s.stream);
+        if (rc != LVS_OK) return rc;
+    }
+    return LVS_OK;
+}
+
+// Flat and SQ8: invert a chunk's (query, probe) pairs - pair numbers q * nprobe + p grouped by list -, cut every list's
+// pairs into work items of 32 (the SQ8 scan halves them) and zero the parts (a pair whose probe named no list - never
+// with nprobe <= nlist - keeps empty slots)
+int32_t ivf_group_pairs(const IvfLayout& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t nlist, int32_t k, u64* parts,
+                        hipStream_t st, const uint32_t** pairs, const uint32_t** pair_offs) {
+    const int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, w + L.off_sort, L.sort_bytes, st, pairs, pair_offs);
+    if (rc != LVS_OK) return rc;
+    LVS_HIP_CHECK(lvs_ivf_tiles_launch(*pair_offs, nlist, (uint32_t*)(w + L.off_tiles), (uint32_t*)(w + L.off_items), st));
+    LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+    return LVS_OK;
+}
+
+// what the two encoders share: the checks up to the pack mode; ldb and dpad of the packed rows
+int32_t ivf_check_encode(int64_t n, int32_t d, int32_t nlist, int32_t M, int32_t ksub, int32_t xb_pack, int64_t& ldb,
+                         int& dpad) {
+    LVS_REQUIRE(n >= 0 && n < 0xFFFFFFFFll && d > 0, "bad shape n=%lld d=%d", (long long)n, d);
+    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
+    LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
+    LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
+    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    dpad = (int)lvs_round_up(d, LVS_BK);
+    ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
+    return LVS_OK;
+}
+
+// probes per PQ scan workgroup: enough for ~2 048 rows of the average list (the table's staging and the first insertions
+// are paid once per workgroup), but no fewer than ~512 workgroups per chunk while the probes allow it; at most LVS_PQ_MAXRANGE
+int32_t pq_prange(int64_t nb, int32_t nlist, int64_t cn, int32_t nprobe) {
+    const int64_t avg = nb / nlist > 0 ? nb / nlist : 1;
+    int64_t pr = (2048 + avg - 1) / avg;
+    const int64_t by_blocks = cn * nprobe / 512;
+    if (pr > by_blocks) pr = by_blocks;
+    if (pr > LVS_PQ_MAXRANGE) pr = LVS_PQ_MAXRANGE;
+    if (pr > nprobe) pr = nprobe;
+    return pr < 1 ? 1 : (int32_t)pr;
 }
 }  // namespace
 
@@ -2116,14 +2260,9 @@ extern "C" int32_t lvs_ivf_build_lists(const int64_t* assign, int64_t n, int32_t
     return LVS_OK;
 }
 
+// ---- IVF-Flat
 extern "C" int64_t lvs_ivf_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t pack) {
-    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
-        return LVS_EINVAL;
-    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    if (!ivf_fits(d, k, pack)) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
-    IvfLayout L;
-    if (!ivf_plan(nq, nlist, nprobe, d, k, pack, pack, L)) return LVS_EINVAL;
-    return L.total;
+    return ivf_workspace_bytes(nq, nlist, nprobe, d, 1, k, pack, ivf_fits(d, k, pack), 0, true);
 }
 
 extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
@@ -2132,49 +2271,23 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
                                        const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
                                        uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                        void* stream) {
-    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
-    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
-                (long long)nq, d);
-    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
-    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
-                nlist, LVS_MAX_K);
-    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
-    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
-    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
-    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, 1, 1, nprobe, k, xb_pack, xq_pack, c_pack);
+    if (ok != LVS_OK) return ok;
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(xb && offsets && rows && centroids && xq && out_keys && workspace, "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
     Plan p;
     LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, k, p) == LVS_OK, "bad plan");
-    const int jper = p.dpad / 16;
-    const int nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper;
-    const int kcap = lvs_ivf_kcap(k);
     if (!ivf_fits(d, k, xq_pack)) {
         lvs_set_error("d=%d with k=%d does not fit the list scan's LDS (see lvs_ivf_search_workspace_bytes)", d, k);
         return LVS_EUNSUPPORTED;
     }
-    IvfLayout L;
-    LVS_REQUIRE(ivf_plan(nq, nlist, nprobe, d, k, c_pack, xq_pack, L), "shape beyond the IVF search");
-    if (workspace_bytes < L.total) {
-        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
-        return LVS_ENOMEM;
-    }
-    LVS_DEVICE_GUARD(stream);
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
-    uint32_t* tile_offs = (uint32_t*)(w + L.off_tiles);
-    uint32_t* items = (uint32_t*)(w + L.off_items);
-    u64* parts = (u64*)(w + L.off_parts);
-
     LvsIvfArgs a;
     memset(&a, 0, sizeof(a));
     a.xb = xb;
     a.bn = xb_norms_sq;
     a.rows = rows;
     a.offsets = offsets;
-    a.out = parts;
     a.nb = nb;
     a.ldb = p.ldb;
     a.ldq = p.ldq;
@@ -2182,88 +2295,52 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
     a.nprobe = nprobe;
     a.k = k;
     a.metric = metric;
-    a.jper = jper;
+    a.jper = p.dpad / 16;
     a.nseg = p.nseg;
-    a.nbfrag = nbfrag;
-    a.kcap = kcap;
-    a.tile_offs = tile_offs;
-    a.item_list = items;
+    a.nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * a.jper;
+    a.kcap = lvs_ivf_kcap(k);
     for (int i = 0; i < 3; ++i) {
         a.seg_c[i] = p.seg_c[i];
-        a.seg_b[i] = p.seg_q[i] == 0 ? 0 : jper;
+        a.seg_b[i] = p.seg_q[i] == 0 ? 0 : a.jper;
     }
-    const size_t qrow_bytes = (size_t)p.ldq * 2;
-    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
-        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
-        const int64_t npairs = cn * nprobe;
-        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
-        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
-        // 1. coarse step: the nprobe best centroids of every query under the index's metric
-        {
-            TimingPause pause;
-            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq,
-                                                    qn_c, 0, nullptr, coarse, w, L.flat_bytes, stream);
-            if (rc != LVS_OK) return rc;
-        }
-        if (out_probe) LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, npairs, out_probe + q0 * nprobe, st));
-        // 2. invert the (query, probe) pairs: pair numbers q * nprobe + p grouped by list, then work items per list
-        const uint32_t *pairs = nullptr, *pair_offs = nullptr;
-        int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, w + L.off_sort, L.sort_bytes, st, &pairs, &pair_offs);
+    const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
+                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream};
+    return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
+                                             const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
+        hipStream_t st = (hipStream_t)stream;
+        const int32_t rc = ivf_group_pairs(L, w, coarse, cn * nprobe, nlist, k, parts, st, &a.pairs, &a.pair_offs);
         if (rc != LVS_OK) return rc;
-        LVS_HIP_CHECK(lvs_ivf_tiles_launch(pair_offs, nlist, tile_offs, items, st));
-        // 3. the list scan (a pair whose probe named no list - never with nprobe <= nlist - keeps empty slots)
-        LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+        a.tile_offs = (const uint32_t*)(w + L.off_tiles);
+        a.item_list = (const uint32_t*)(w + L.off_items);
+        a.out = parts;
         a.xq = xq_c;
         a.qn = qn_c;
         a.nq = (int)cn;
-        a.pairs = pairs;
-        a.pair_offs = pair_offs;
-        {
-            ScopedKernelTimer timer(st, LVS_KERNEL_IVF, q0 > 0);
-            LVS_HIP_CHECK(lvs_ivf_scan_launch(a, lvs_ivf_max_items(npairs, nlist), st));
-        }
-        // 4. merge the per-probe lists
-        rc = lvs_merge_keys((const uint64_t*)parts, nprobe, cn, k, out_keys + q0 * k, stream);
-        if (rc != LVS_OK) return rc;
-    }
-    return LVS_OK;
+        ScopedKernelTimer timer(st, LVS_KERNEL_IVF, q0 > 0);
+        LVS_HIP_CHECK(lvs_ivf_scan_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
+        return LVS_OK;
+    });
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// IVF-SQ8 (lvs_ivf_sq8.hip): the IVF-Flat lists and coarse step, the rows scored from 8-bit residual codes
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-// does the SQ8 scan's LDS image (the tile's w fragments, hi|lo whatever the query's pack mode, + its lists) fit?
-bool ivf_sq8_fits(int32_t d, int32_t k) {
-    return lvs_ivf_sq8_lds_bytes(lvs_ivf_sq8_ldc(d), lvs_ivf_kcap(k)) <= 160 * 1024;
-}
-}  // namespace
-
+// ---- IVF-SQ8: the rows scored from 8-bit residual codes
 extern "C" int32_t lvs_ivf_sq8_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets,
                                       const uint32_t* rows, int32_t nlist, const float* centroids, const float* vmin,
                                       const float* vdiff, uint8_t* out_codes, float* out_residual_norms_sq, void* stream) {
-    LVS_REQUIRE(n >= 0 && n < 0xFFFFFFFFll && d > 0, "bad shape n=%lld d=%d", (long long)n, d);
-    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
-    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    int64_t ldb;
+    int dpad;
+    const int32_t ok = ivf_check_encode(n, d, nlist, 1, 1, xb_pack, ldb, dpad);
+    if (ok != LVS_OK) return ok;
     if (n == 0) return LVS_OK;
     LVS_REQUIRE(xb && offsets && rows && centroids && vmin && vdiff && out_codes && out_residual_norms_sq, "NULL buffer");
     LVS_DEVICE_GUARD(stream);
-    const int64_t dpad = lvs_round_up(d, LVS_BK);
-    const int64_t ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
-    LVS_HIP_CHECK(lvs_ivf_sq8_encode_launch(xb, ldb, xb_pack == LVS_PACK_SPLIT, (int)dpad, n, d, offsets, nlist, rows, centroids,
-                                            vmin, vdiff, out_codes, out_residual_norms_sq, (hipStream_t)stream));
+    LVS_HIP_CHECK(lvs_ivf_sq8_encode_launch(xb, ldb, xb_pack == LVS_PACK_SPLIT, dpad, n, d, offsets, nlist, rows, centroids, vmin,
+                                            vdiff, out_codes, out_residual_norms_sq, (hipStream_t)stream));
     return LVS_OK;
 }
 
 extern "C" int64_t lvs_ivf_sq8_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k,
                                                       int32_t pack) {
-    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
-        return LVS_EINVAL;
-    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    if (!ivf_sq8_fits(d, k)) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
-    IvfLayout L;
-    if (!ivf_plan(nq, nlist, nprobe, d, k, pack, pack, L)) return LVS_EINVAL;
-    return L.total;
+    return ivf_workspace_bytes(nq, nlist, nprobe, d, 1, k, pack, ivf_sq8_fits(d, k), 0, true);
 }
 
 extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norms_sq, const float* vmin,
@@ -2273,15 +2350,8 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
                                            const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
                                            uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                            void* stream) {
-    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
-    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
-                (long long)nq, d);
-    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
-    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
-                nlist, LVS_MAX_K);
-    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
-    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
-    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, 1, 1, nprobe, k, LVS_PACK_F16, xq_pack, c_pack);
+    if (ok != LVS_OK) return ok;
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(codes && vmin && vdiff && offsets && rows && centroids && centroids_f32 && xq && out_keys && workspace,
                 "NULL buffer");
@@ -2290,22 +2360,6 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
         lvs_set_error("d=%d with k=%d does not fit the SQ8 list scan's LDS (see lvs_ivf_sq8_search_workspace_bytes)", d, k);
         return LVS_EUNSUPPORTED;
     }
-    IvfLayout L;
-    LVS_REQUIRE(ivf_plan(nq, nlist, nprobe, d, k, c_pack, xq_pack, L), "shape beyond the IVF search");
-    if (workspace_bytes < L.total) {
-        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
-        return LVS_ENOMEM;
-    }
-    LVS_DEVICE_GUARD(stream);
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
-    uint32_t* tile_offs = (uint32_t*)(w + L.off_tiles);
-    uint32_t* items = (uint32_t*)(w + L.off_items);
-    u64* parts = (u64*)(w + L.off_parts);
-    const int64_t qdpad = lvs_round_up(d, LVS_BK);
-    const int64_t ldq = xq_pack == LVS_PACK_SPLIT ? 2 * qdpad : qdpad;
-
     LvsIvfSq8Args a;
     memset(&a, 0, sizeof(a));
     a.codes = codes;
@@ -2315,10 +2369,6 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
     a.cent = centroids_f32;
     a.rows = rows;
     a.offsets = offsets;
-    a.tile_offs = tile_offs;
-    a.item_list = items;
-    a.out = parts;
-    a.ldq = ldq;
     a.nlist = nlist;
     a.nprobe = nprobe;
     a.k = k;
@@ -2326,128 +2376,46 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
     a.d = d;
     a.ldc = lvs_ivf_sq8_ldc(d);
     a.qsplit = xq_pack == LVS_PACK_SPLIT;
-    a.qdpad = (int)qdpad;
+    a.qdpad = (int)lvs_round_up(d, LVS_BK);
+    a.ldq = a.qsplit ? 2 * a.qdpad : a.qdpad;
     a.kcap = lvs_ivf_kcap(k);
-    const size_t qrow_bytes = (size_t)ldq * 2;
-    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
-        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
-        const int64_t npairs = cn * nprobe;
-        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
-        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
-        // 1. coarse step: exactly lvs_ivf_search_keys's
-        {
-            TimingPause pause;
-            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq,
-                                                    qn_c, 0, nullptr, coarse, w, L.flat_bytes, stream);
-            if (rc != LVS_OK) return rc;
-        }
-        if (out_probe) LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, npairs, out_probe + q0 * nprobe, st));
-        // 2. the (query, probe) pairs grouped by list, 32-pair work items per list (the SQ8 scan halves them)
-        const uint32_t *pairs = nullptr, *pair_offs = nullptr;
-        int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, w + L.off_sort, L.sort_bytes, st, &pairs, &pair_offs);
+    const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
+                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream};
+    return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
+                                             const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
+        hipStream_t st = (hipStream_t)stream;
+        const int32_t rc = ivf_group_pairs(L, w, coarse, cn * nprobe, nlist, k, parts, st, &a.pairs, &a.pair_offs);
         if (rc != LVS_OK) return rc;
-        LVS_HIP_CHECK(lvs_ivf_tiles_launch(pair_offs, nlist, tile_offs, items, st));
-        // 3. the SQ8 list scan
-        LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+        a.tile_offs = (const uint32_t*)(w + L.off_tiles);
+        a.item_list = (const uint32_t*)(w + L.off_items);
+        a.out = parts;
         a.xq = xq_c;
         a.nq = (int)cn;
-        a.pairs = pairs;
-        a.pair_offs = pair_offs;
-        {
-            ScopedKernelTimer timer(st, LVS_KERNEL_IVF_SQ8, q0 > 0);
-            LVS_HIP_CHECK(lvs_ivf_sq8_scan_launch(a, lvs_ivf_max_items(npairs, nlist), st));
-        }
-        // 4. merge the per-probe lists
-        rc = lvs_merge_keys((const uint64_t*)parts, nprobe, cn, k, out_keys + q0 * k, stream);
-        if (rc != LVS_OK) return rc;
-    }
-    return LVS_OK;
+        ScopedKernelTimer timer(st, LVS_KERNEL_IVF_SQ8, q0 > 0);
+        LVS_HIP_CHECK(lvs_ivf_sq8_scan_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
+        return LVS_OK;
+    });
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// IVF-PQ (lvs_ivf_pq.hip): the IVF-Flat lists and coarse step, the rows scored from product-quantizer codes
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-// does the PQ scan's LDS image (one query's fp32 table of M x 256 entries + its list) fit?  M <= 159, whatever d and k
-bool ivf_pq_fits(int32_t M, int32_t k) { return lvs_ivf_pq_lds_bytes(M, lvs_ivf_kcap(k)) <= 160 * 1024; }
-
-struct PqLayout {
-    int64_t chunk;  // queries per chunk
-    int64_t off_coarse, off_lut, off_parts, flat_bytes, total;
-};
-
-// scratch of a chunk of `c` queries: [flat search scratch | coarse keys [c][nprobe] | tables [c][M][256] fp32 |
-// parts [<= nprobe][c][k]]
-bool pq_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k, int32_t c_pack, int32_t xq_pack,
-               PqLayout& L) {
-    L.chunk = c;
-    L.flat_bytes = lvs_flat_search_workspace_bytes(c, nlist, d, nprobe, c_pack, xq_pack);
-    if (L.flat_bytes < 0) return false;
-    const int64_t npairs = c * nprobe;
-    int64_t off = lvs_round_up(L.flat_bytes, 256);
-    L.off_coarse = off;
-    off += lvs_round_up(npairs * 8, 256);
-    L.off_lut = off;
-    off += lvs_round_up(c * M * LVS_PQ_KSUB * 4, 256);
-    L.off_parts = off;
-    off += lvs_round_up(npairs * k * 8, 256);
-    L.total = off;
-    return true;
-}
-
-// the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits
-bool pq_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k, int32_t c_pack, int32_t xq_pack,
-             PqLayout& L) {
-    int64_t c = nq < IVF_CHUNK_MAX ? nq : IVF_CHUNK_MAX;
-    if (c < 1) c = 1;
-    for (;;) {
-        if (!pq_layout(c, nlist, nprobe, d, M, k, c_pack, xq_pack, L)) return false;
-        if (L.total <= IVF_WS_BUDGET || c == 1) return c * nprobe < 0xFFFFFFFFll;
-        c = (c + 1) / 2;
-    }
-}
-
-// probes per scan workgroup: enough for ~2 048 rows of the average list (the table's staging and the first insertions are
-// paid once per workgroup), but no fewer than ~512 workgroups per chunk while the probes allow it; at most LVS_PQ_MAXRANGE
-int32_t pq_prange(int64_t nb, int32_t nlist, int64_t cn, int32_t nprobe) {
-    const int64_t avg = nb / nlist > 0 ? nb / nlist : 1;
-    int64_t pr = (2048 + avg - 1) / avg;
-    const int64_t by_blocks = cn * nprobe / 512;
-    if (pr > by_blocks) pr = by_blocks;
-    if (pr > LVS_PQ_MAXRANGE) pr = LVS_PQ_MAXRANGE;
-    if (pr > nprobe) pr = nprobe;
-    return pr < 1 ? 1 : (int32_t)pr;
-}
-}  // namespace
-
+// ---- IVF-PQ: the rows scored from product-quantizer codes
 extern "C" int32_t lvs_ivf_pq_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets,
                                      const uint32_t* rows, int32_t nlist, const float* centroids, int32_t M, int32_t ksub,
                                      const float* codebooks, uint8_t* out_codes, float* out_beta, void* stream) {
-    LVS_REQUIRE(n >= 0 && n < 0xFFFFFFFFll && d > 0, "bad shape n=%lld d=%d", (long long)n, d);
-    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
-    LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
-    LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
-    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    int64_t ldb;
+    int dpad;
+    const int32_t ok = ivf_check_encode(n, d, nlist, M, ksub, xb_pack, ldb, dpad);
+    if (ok != LVS_OK) return ok;
     if (n == 0) return LVS_OK;
     LVS_REQUIRE(xb && offsets && rows && centroids && codebooks && out_codes && out_beta, "NULL buffer");
     LVS_DEVICE_GUARD(stream);
-    const int64_t dpad = lvs_round_up(d, LVS_BK);
-    const int64_t ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
-    LVS_HIP_CHECK(lvs_ivf_pq_encode_launch(xb, ldb, xb_pack == LVS_PACK_SPLIT, (int)dpad, n, d, M, ksub, offsets, nlist, rows,
+    LVS_HIP_CHECK(lvs_ivf_pq_encode_launch(xb, ldb, xb_pack == LVS_PACK_SPLIT, dpad, n, d, M, ksub, offsets, nlist, rows,
                                            centroids, codebooks, out_codes, out_beta, (hipStream_t)stream));
     return LVS_OK;
 }
 
 extern "C" int64_t lvs_ivf_pq_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k,
                                                      int32_t pack) {
-    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
-        return LVS_EINVAL;
-    if (M < 1 || d % M != 0) return LVS_EINVAL;
-    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    if (!ivf_pq_fits(M, k)) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
-    PqLayout L;
-    if (!pq_plan(nq, nlist, nprobe, d, M, k, pack, pack, L)) return LVS_EINVAL;
-    return L.total;
+    return ivf_workspace_bytes(nq, nlist, nprobe, d, M, k, pack, ivf_pq_fits(M, k), (int64_t)M * LVS_PQ_KSUB * 4, false);
 }
 
 extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M,
@@ -2457,17 +2425,8 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
                                           const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
                                           uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                           void* stream) {
-    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
-    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && d > 0, "bad shape nb=%lld nq=%lld d=%d", (long long)nb,
-                (long long)nq, d);
-    LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
-    LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
-    LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
-    LVS_REQUIRE(nprobe >= 1 && nprobe <= nlist && nprobe <= LVS_MAX_K, "nprobe=%d must be in [1, min(nlist=%d, %d)]", nprobe,
-                nlist, LVS_MAX_K);
-    LVS_REQUIRE(k >= 1 && k <= LVS_KPASS, "k=%d must be in [1, %d] (one pass of the list scan)", k, LVS_KPASS);
-    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
-    LVS_REQUIRE(c_pack == LVS_PACK_F16 || c_pack == LVS_PACK_SPLIT, "bad c_pack");
+    const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, M, ksub, nprobe, k, LVS_PACK_F16, xq_pack, c_pack);
+    if (ok != LVS_OK) return ok;
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(codes && codebooks && offsets && rows && centroids && centroids_f32 && xq && out_keys && workspace,
                 "NULL buffer");
@@ -2476,21 +2435,6 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
         lvs_set_error("M=%d with k=%d does not fit the PQ list scan's LDS (see lvs_ivf_pq_search_workspace_bytes)", M, k);
         return LVS_EUNSUPPORTED;
     }
-    PqLayout L;
-    LVS_REQUIRE(pq_plan(nq, nlist, nprobe, d, M, k, c_pack, xq_pack, L), "shape beyond the IVF search");
-    if (workspace_bytes < L.total) {
-        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
-        return LVS_ENOMEM;
-    }
-    LVS_DEVICE_GUARD(stream);
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
-    float* lut = (float*)(w + L.off_lut);
-    u64* parts = (u64*)(w + L.off_parts);
-    const int64_t qdpad = lvs_round_up(d, LVS_BK);
-    const int64_t ldq = xq_pack == LVS_PACK_SPLIT ? 2 * qdpad : qdpad;
-
     LvsIvfPqArgs a;
     memset(&a, 0, sizeof(a));
     a.codes = codes;
@@ -2498,10 +2442,6 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
     a.cent = centroids_f32;
     a.rows = rows;
     a.offsets = offsets;
-    a.lut = lut;
-    a.coarse = (const u64*)coarse;
-    a.out = parts;
-    a.ldq = ldq;
     a.nlist = nlist;
     a.nprobe = nprobe;
     a.k = k;
@@ -2510,34 +2450,27 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
     a.M = M;
     a.ldc = lvs_ivf_pq_ldc(M);
     a.qsplit = xq_pack == LVS_PACK_SPLIT;
-    a.qdpad = (int)qdpad;
+    a.qdpad = (int)lvs_round_up(d, LVS_BK);
+    a.ldq = a.qsplit ? 2 * a.qdpad : a.qdpad;
     a.kcap = lvs_ivf_kcap(k);
-    const size_t qrow_bytes = (size_t)ldq * 2;
-    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
-        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
-        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
-        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
-        // 1. coarse step: exactly lvs_ivf_search_keys's
-        {
-            TimingPause pause;
-            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq,
-                                                    qn_c, 0, nullptr, coarse, w, L.flat_bytes, stream);
-            if (rc != LVS_OK) return rc;
-        }
-        if (out_probe) LVS_HIP_CHECK(lvs_ivf_probe_ids_launch((const u64*)coarse, cn * nprobe, out_probe + q0 * nprobe, st));
-        // 2. + 3. the queries' tables, then the query-major scan: one part per range of probes
+    const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
+                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream};
+    // the queries' tables, then the query-major scan: one part per range of probes
+    return ivf_search_chunks(s, (int64_t)M * LVS_PQ_KSUB * 4, false,
+                             [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
+                                 const uint64_t* coarse, u64* parts, int32_t& nparts) -> int32_t {
+        hipStream_t st = (hipStream_t)stream;
+        float* lut = (float*)(w + L.off_extra);
         a.prange = pq_prange(nb, nlist, cn, nprobe);
-        const int32_t nranges = (nprobe + a.prange - 1) / a.prange;
+        nparts = (nprobe + a.prange - 1) / a.prange;
+        a.lut = lut;
+        a.coarse = (const u64*)coarse;
+        a.out = parts;
         a.xq = xq_c;
         a.nq = (int)cn;
-        {
-            ScopedKernelTimer timer(st, LVS_KERNEL_IVF_PQ, q0 > 0);
-            LVS_HIP_CHECK(lvs_ivf_pq_lut_launch(xq_c, ldq, a.qsplit, a.qdpad, cn, d, M, ksub, codebooks, lut, st));
-            LVS_HIP_CHECK(lvs_ivf_pq_scan_launch(a, st));
-        }
-        // 4. merge the per-range lists
-        const int32_t rc = lvs_merge_keys((const uint64_t*)parts, nranges, cn, k, out_keys + q0 * k, stream);
-        if (rc != LVS_OK) return rc;
-    }
-    return LVS_OK;
+        ScopedKernelTimer timer(st, LVS_KERNEL_IVF_PQ, q0 > 0);
+        LVS_HIP_CHECK(lvs_ivf_pq_lut_launch(xq_c, a.ldq, a.qsplit, a.qdpad, cn, d, M, ksub, codebooks, lut, st));
+        LVS_HIP_CHECK(lvs_ivf_pq_scan_launch(a, st));
+        return LVS_OK;
+    });
 }

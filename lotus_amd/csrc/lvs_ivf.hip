@@ -12,7 +12,7 @@
 //   * each wave takes every fourth 32-row block of the list: v_mfma_f32_32x32x16_f16 on 32 rows x 32 queries per K step,
 //     hi|lo operands as the K segments hi.hi + hi.lo + lo.hi (fp32-accurate, like the flat path); the fragments of the next
 //     K step are loaded while the current ones are multiplied;
-//   * hits go through the wave-cooperative sorted insertion of the other list kernels into per-query lists in LDS (one
+//   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_tile.h) into per-query lists in LDS (one
 //     lock per query: the four waves share the tile).  Keys carry the GLOBAL row number, so ties between rows of different
 //     lists keep the oracle's total order when the per-probe lists are merged (lvs_merge_keys);
 //   * the work item writes its k keys per pair to the part of the pair's probe rank: parts [nprobe][nq][k].
@@ -25,8 +25,6 @@
 #include "lvs_tile.h"
 
 namespace {
-
-__device__ inline float ivf_tau(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
 
 template <int U>
 __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const LvsIvfArgs a) {
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
         }
         {
             const uint32_t lo = (uint32_t)(lists[qs * KCAP + k - 1] >> 32);
-            tauf = fmaxf(tauf, ivf_tau(lo));
+            tauf = fmaxf(tauf, lvs_tau(lo));
         }
         float best = -INFINITY;
 #pragma unroll
@@ -134,37 +132,7 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
             const uint32_t id = (uint32_t)__shfl((int)rid, (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), 64);
             const bool pending = th && brow0 + (r & 3) + 8 * (r >> 2) < len && acc[r] >= tauf;
             const u64 key = pending ? lvs_pack_key(acc[r], id) : 0ull;
-            unsigned long long pm = __ballot(pending);
-            while (pm) {  // wave-cooperative sorted insertion (as lvs_stream_kernel)
-                const int src = __ffsll((long long)pm) - 1;
-                pm &= pm - 1;
-                const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src);
-                const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), src);
-                const u64 ukey = ((u64)khi << 32) | klo;
-                const int uq = __builtin_amdgcn_readlane(qs, src);
-                u64* UL = lists + uq * KCAP;
-                u64 mine = 0, prev = ~0ull;
-                for (;;) {
-                    uint32_t seen = 0;
-                    if (lane == 0)
-                        __hip_atomic_compare_exchange_strong(&locks[uq], &seen, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_WORKGROUP);
-                    asm volatile("" ::: "memory");
-                    if (lane < k) {
-                        mine = UL[lane];
-                        if (lane > 0) prev = UL[lane - 1];
-                    }
-                    if (__builtin_amdgcn_readfirstlane(seen) == 0) break;
-                }
-                u64 newv = 0;
-                if (lane < k) newv = mine > ukey ? mine : (prev > ukey ? ukey : prev);
-                __builtin_amdgcn_wave_barrier();
-                if (lane < k) UL[lane] = newv;
-                const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
-                asm volatile("" ::: "memory");  // slot writes stay ahead of the unlock (LDS is in-order per wave)
-                if (lane == 0) __hip_atomic_store(&locks[uq], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (qs == uq) tauf = fmaxf(tauf, ivf_tau(ntau));
-            }
+            lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
     }
     __syncthreads();

@@ -15,8 +15,8 @@
 //   squared L2:     |q - c_l|^2 + beta - 2 sum_m LUT_q[m][code_m]
 // lvs_ivf_pq_scan_kernel is query-major: a workgroup takes one query and a range of its probed lists, stages the query's
 // fp32 table (M KB) in LDS, and every lane scores one row of the concatenated lists from its M code bytes (16-byte loads,
-// then M ds_read_b32 lookups summed in the order m = 0 .. M-1).  Hits go through the wave-cooperative sorted insertion of
-// the other IVF scans into the workgroup's one list in LDS; keys carry the GLOBAL row number; parts [nranges][nq][k] are
+// then M ds_read_b32 lookups summed in the order m = 0 .. M-1).  Hits go through the wave-cooperative sorted insertion
+// (the text of lvs_list_insert, lvs_tile.h) into the workgroup's one list in LDS; keys carry the GLOBAL row number; parts [nranges][nq][k] are
 // merged by lvs_merge_keys.  LDS: M KB of table + the list: M <= 159 (lvs_ivf_pq_lds_bytes), whatever d.
 #include "lvs_common.h"
 #include "lvs_tile.h"
@@ -27,14 +27,6 @@ constexpr int PQ_THREADS = LVS_PQ_WAVES * 64;
 constexpr int PQ_KS = LVS_PQ_KSUB;
 constexpr int LUT_QB = 16;  // queries per workgroup of the table kernel
 constexpr int LUT_T = 64;   // dimensions of a query tile staged in LDS
-
-__device__ inline float pq_tau(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
-
-__device__ inline float pq_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // the fp32 value of dimension j of a packed query / row (hi, plus lo at +dpad for hi|lo)
 __device__ inline float pq_val(const _Float16* __restrict__ p, int j, int split, int dpad) {
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
             const float qv = pq_val(qrow, j, a.qsplit, a.qdpad), cv = cl[j];
             s += l2 ? (qv - cv) * (qv - cv) : qv * cv;
         }
-        s = pq_wave_sum(s);
+        s = lvs_wave_sum(s);
         if (lane == 0) cst[p] = s;
     }
     __syncthreads();
@@ -164,7 +156,7 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
         const uint32_t rid = a.rows[pos];
         {
             const uint32_t lo = (uint32_t)(list[k - 1] >> 32);
-            tauf = fmaxf(tauf, pq_tau(lo));
+            tauf = fmaxf(tauf, lvs_tau(lo));
         }
         bool pending = valid && score >= tauf;
         const u64 key = pending ? lvs_pack_key(score, rid) : 0ull;
@@ -181,7 +173,8 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
             pending = pending && ord >= kth;
             pm = __ballot(pending);
         }
-        while (pm) {  // wave-cooperative sorted insertion (as lvs_ivf_scan_kernel), one list per workgroup
+        // the text of lvs_list_insert (lvs_tile.h) for one list and one lock: calling it here changes this kernel's instructions
+        while (pm) {
             const int srcl = __ffsll((long long)pm) - 1;
             pm &= pm - 1;
             const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, srcl);
@@ -207,7 +200,7 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
             const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
             asm volatile("" ::: "memory");  // slot writes stay ahead of the unlock (LDS is in-order per wave)
             if (lane == 0) __hip_atomic_store(&lock[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            tauf = fmaxf(tauf, pq_tau(ntau));
+            tauf = fmaxf(tauf, lvs_tau(ntau));
         }
     }
     __syncthreads();
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(256) void lvs_ivf_pq_encode_kernel(const _Float16* 
         }
     }
     for (int m = M + lane; m < ldc; m += 64) out[m] = 0;
-    bsum = pq_wave_sum(bsum);
+    bsum = lvs_wave_sum(bsum);
     if (lane == 0) beta[pos] = bsum;
 }
 

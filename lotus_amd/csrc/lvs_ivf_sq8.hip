@@ -22,7 +22,7 @@
 //     64 kb + 16 g + 8 s + t, and the B fragments are staged with the same permutation.  A code byte becomes an exact fp16
 //     by v_perm_b32 (0x64XX = 1024 + code) and v_pk_add_f16 (-1024);
 //   * acc = codes x w_hi + codes x w_lo (fp32 accumulation of exact products: fp32-accurate);
-//   * hits go through the wave-cooperative sorted insertion of lvs_ivf_scan_kernel into per-pair lists in LDS, keys carry
+//   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_tile.h) into per-pair lists in LDS, keys carry
 //     the GLOBAL row number, parts [nprobe][nq][k] are merged by lvs_merge_keys.
 // LDS: 2 x (ldc / 32) fragments of 1 KB + 16 lists of kcap keys: ldc <= 2368 (d = 1536: 96 KB + 8 KB); wider rows are not
 // served (lvs_ivf_sq8_fits).
@@ -33,8 +33,6 @@ namespace {
 
 constexpr int SQ8_TQ = LVS_SQ8_TILEQ;
 constexpr int SQ8_THREADS = LVS_SQ8_WAVES * 64;
-
-__device__ inline float sq8_tau(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
 
 // 8 consecutive floats p[j .. j + 8) of a row of length d (zeros past d); vector loads when the row allows them
 __device__ inline void sq8_load8(const float* __restrict__ p, int j, int d, bool vec, float (&v)[8]) {
@@ -74,17 +72,6 @@ __device__ inline void sq8_w8(const float (&qv)[8], const float (&cv)[8], const 
         s2 += u * a;
         mx = fmaxf(mx, fabsf(w[t]));
     }
-}
-
-__device__ inline float sq8_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ inline float sq8_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -164,9 +151,9 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
             sq8_load8(a.vdiff, j, d, vec, dv);
             sq8_w8(qv, cv, mv, dv, l2, w, s1, s2, mx);
         }
-        s1 = sq8_wave_sum(s1);
-        s2 = sq8_wave_sum(s2);
-        mx = sq8_wave_max(mx);
+        s1 = lvs_wave_sum(s1);
+        s2 = lvs_wave_sum(s2);
+        mx = lvs_wave_max(mx);
         if (lane == 0) {
             cst[n] = l2 ? s1 - 2.0f * s2 : s1 + s2;
             int e = 0;
@@ -263,7 +250,7 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
         }
         {
             const uint32_t lo = (uint32_t)(lists[qs * KCAP + k - 1] >> 32);
-            tauf = fmaxf(tauf, sq8_tau(lo));
+            tauf = fmaxf(tauf, lvs_tau(lo));
         }
         float best = -INFINITY;
 #pragma unroll
@@ -275,37 +262,7 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
             const uint32_t id = (uint32_t)__shfl((int)rid, 4 * (lane >> 4) + r, 64);
             const bool pending = th && brow0 + r < len && acc[r] >= tauf;
             const u64 key = pending ? lvs_pack_key(acc[r], id) : 0ull;
-            unsigned long long pm = __ballot(pending);
-            while (pm) {  // wave-cooperative sorted insertion (as lvs_ivf_scan_kernel)
-                const int src = __ffsll((long long)pm) - 1;
-                pm &= pm - 1;
-                const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src);
-                const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), src);
-                const u64 ukey = ((u64)khi << 32) | klo;
-                const int uq = __builtin_amdgcn_readlane(qs, src);
-                u64* UL = lists + uq * KCAP;
-                u64 mine = 0, prev = ~0ull;
-                for (;;) {
-                    uint32_t seen = 0;
-                    if (lane == 0)
-                        __hip_atomic_compare_exchange_strong(&locks[uq], &seen, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_WORKGROUP);
-                    asm volatile("" ::: "memory");
-                    if (lane < k) {
-                        mine = UL[lane];
-                        if (lane > 0) prev = UL[lane - 1];
-                    }
-                    if (__builtin_amdgcn_readfirstlane(seen) == 0) break;
-                }
-                u64 newv = 0;
-                if (lane < k) newv = mine > ukey ? mine : (prev > ukey ? ukey : prev);
-                __builtin_amdgcn_wave_barrier();
-                if (lane < k) UL[lane] = newv;
-                const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
-                asm volatile("" ::: "memory");  // slot writes stay ahead of the unlock (LDS is in-order per wave)
-                if (lane == 0) __hip_atomic_store(&locks[uq], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (qs == uq) tauf = fmaxf(tauf, sq8_tau(ntau));
-            }
+            lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
     }
     __syncthreads();
@@ -352,7 +309,7 @@ __global__ __launch_bounds__(256) void lvs_ivf_sq8_encode_kernel(const _Float16*
         }
         out[j] = (uint8_t)code;
     }
-    nn = sq8_wave_sum(nn);
+    nn = lvs_wave_sum(nn);
     if (lane == 0) rnorm[pos] = nn;
 }
 

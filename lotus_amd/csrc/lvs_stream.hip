@@ -38,8 +38,6 @@ constexpr int SQ = 32;          // queries per query block (MFMA N)
 // that the branch-free fast path exists for every row length whose fragment count per K segment is a multiple of 8:
 //   16 (d = 256, 512, 768, 1024, ...), 24 (d = 384 - BASELINE configs[0]'s dimension -, 1152), 8 (d = 128, 640, ...)
 
-__device__ inline float tau_float(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
-
 // scores are finite or -inf, never NaN: v_max3_f32 without fmaxf's canonicalisation (8 instructions for 16 values)
 __device__ inline float max3(float a, float b, float c) {
     float r;
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
         tauf[qb] = -INFINITY;
         // start from the shared threshold: zero on a fresh call, the k-th best score of the sample on a seeded one
         gord[qb] = (!SEED && qvalid[qb]) ? a.gtau[qbase + qi[qb]] : 0u;
-        tauf[qb] = tau_float(gord[qb]);
+        tauf[qb] = lvs_tau(gord[qb]);
         qnv[qb] = (a.metric == LVS_METRIC_L2 && qvalid[qb]) ? a.qn[qbase + qi[qb]] : 0.f;
     }
 
@@ -259,7 +257,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
             }
             {
                 const uint32_t lo = (uint32_t)(lists[q * KCAP + k - 1] >> 32);
-                tauf[qb] = fmaxf(tauf[qb], tau_float(lo));
+                tauf[qb] = fmaxf(tauf[qb], lvs_tau(lo));
             }
             const bool th = qvalid[qb] && (max16(acc[qb]) >= tauf[qb]);
             if (__any(th)) {
@@ -277,7 +275,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
                         }
                     }
                     unsigned long long pm = __ballot(pending);
-                    while (pm) {  // wave-cooperative sorted insertion (see lvs_tile.hip)
+                    // the text of lvs_list_insert (lvs_tile.h): calling it here renames registers of the fragment loop
+                    while (pm) {
                         const int src = __ffsll((long long)pm) - 1;
                         pm &= pm - 1;
                         const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src);
@@ -305,7 +304,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
                         const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
                         asm volatile("" ::: "memory");  // slot writes stay ahead of the unlock (LDS is in-order per wave)
                         if (lane == 0) __hip_atomic_store(&locks[uq], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (q == uq) tauf[qb] = fmaxf(tauf[qb], tau_float(ntau));
+                        if (q == uq) tauf[qb] = fmaxf(tauf[qb], lvs_tau(ntau));
                     }
                 }
             }
@@ -323,7 +322,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
             }
             const uint32_t gl = __shfl(gord[qb], lane & 31, 64);  // lanes l and l+32 share the query
             gord[qb] = gl > gord[qb] ? gl : gord[qb];
-            tauf[qb] = fmaxf(tauf[qb], tau_float(gord[qb]));
+            tauf[qb] = fmaxf(tauf[qb], lvs_tau(gord[qb]));
         }
     }
     if constexpr (SEED) {

@@ -382,6 +382,58 @@ hipError_t lvs_ivf_pq_lut_launch(const void* xq, int64_t ldq, int split, int qdp
 // launches ceil(nprobe / prange) x nq workgroups
 hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream);
 
+// ---- device helpers shared by lvs_stream.hip and the three IVF files ----
+// the score a list's last slot stands for: an empty slot (ord 0) admits everything
+__device__ __forceinline__ float lvs_tau(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
+__device__ __forceinline__ float lvs_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float lvs_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// Wave-cooperative sorted insertion into descending lists of k keys in LDS (lists [slots][KCAP], one lock per slot: the
+// waves of a workgroup share the lists).  pm is the ballot of the lanes that hold a key; every such key goes, one at a time,
+// into the list of its lane's slot: the key and slot are broadcast, lane 0 takes the list's lock, lane j < k reads slots j
+// and j - 1 and writes the shifted slot j, lane 0 unlocks; lanes of the same slot raise their threshold tauf to the list's
+// new last slot.  lvs_stream_kernel and lvs_ivf_pq_scan_kernel carry the same text in place (the call changes their code).
+__device__ __forceinline__ void lvs_list_insert(unsigned long long pm, u64 key, int slot, u64* lists, int KCAP, uint32_t* locks,
+                                                int k, int lane, float& tauf) {
+    while (pm) {
+        const int src = __ffsll((long long)pm) - 1;
+        pm &= pm - 1;
+        const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src);
+        const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), src);
+        const u64 ukey = ((u64)khi << 32) | klo;
+        const int uq = __builtin_amdgcn_readlane(slot, src);
+        u64* UL = lists + uq * KCAP;
+        u64 mine = 0, prev = ~0ull;
+        for (;;) {
+            uint32_t seen = 0;
+            if (lane == 0)
+                __hip_atomic_compare_exchange_strong(&locks[uq], &seen, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+            asm volatile("" ::: "memory");
+            if (lane < k) {
+                mine = UL[lane];
+                if (lane > 0) prev = UL[lane - 1];
+            }
+            if (__builtin_amdgcn_readfirstlane(seen) == 0) break;
+        }
+        u64 newv = 0;
+        if (lane < k) newv = mine > ukey ? mine : (prev > ukey ? ukey : prev);
+        __builtin_amdgcn_wave_barrier();
+        if (lane < k) UL[lane] = newv;
+        const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
+        asm volatile("" ::: "memory");  // slot writes stay ahead of the unlock (LDS is in-order per wave)
+        if (lane == 0) __hip_atomic_store(&locks[uq], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (slot == uq) tauf = fmaxf(tauf, lvs_tau(ntau));
+    }
+}
+
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);
 int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, int* out_groups);

@@ -59,6 +59,101 @@ def test_host_side_entry_points_without_a_gpu():
     assert lib.lvs_search_sharded_rccl(None, None, 0, 10, None, 0, 10, 8, 0, 3, None, None, 0, 0, None, None, 0, None) != 0
 
 
+def _ivf_search_calls(lib):
+    """name -> call(nq, d, metric, nprobe, k, M) of the three IVF searches with NULL buffers, nb = 1000, nlist = 64, fp16"""
+    def flat(nq, d, metric, nprobe, k, M):
+        return lib.lvs_ivf_search_keys(None, 0, 1000, None, None, None, 64, None, 0, None, None, 0, nq, None, d, metric, nprobe, k,
+                                       None, None, None, 0, None)
+
+    def sq8(nq, d, metric, nprobe, k, M):
+        return lib.lvs_ivf_sq8_search_keys(None, None, None, None, None, None, 1000, 64, None, 0, None, None, None, 0, nq, None, d,
+                                           metric, nprobe, k, None, None, None, 0, None)
+
+    def pq(nq, d, metric, nprobe, k, M):
+        return lib.lvs_ivf_pq_search_keys(None, None, None, M, 256, None, None, 1000, 64, None, 0, None, None, None, 0, nq, None,
+                                          d, metric, nprobe, k, None, None, None, 0, None)
+
+    return {"flat": flat, "sq8": sq8, "pq": pq}
+
+
+def test_ivf_search_argument_checks_without_a_gpu():
+    # every answer below is decided before the NULL-buffer check and before a device is touched
+    lib = _capi.load()
+    for name, call in _ivf_search_calls(lib).items():
+        assert call(10, 64, 5, 8, 10, 8) == _capi.EINVAL and b"metric" in lib.lvs_last_error(), name
+        assert call(10, 64, 0, 65, 10, 8) == _capi.EINVAL and b"nprobe=65" in lib.lvs_last_error(), name  # nprobe > nlist
+        assert call(10, 64, 0, 8, 57, 8) == _capi.EINVAL and b"k=57" in lib.lvs_last_error(), name
+        assert call(10, 64, 0, 8, 56, 8) == _capi.EINVAL and b"NULL buffer" in lib.lvs_last_error(), name  # the checks passed
+        assert call(0, 64, 0, 8, 10, 8) == _capi.OK, name  # no queries: nothing to do
+        assert call(0, 64, 5, 8, 10, 8) == _capi.EINVAL, name  # ... but the arguments are still checked
+    pq = _ivf_search_calls(lib)["pq"]
+    assert pq(10, 64, 0, 8, 10, 7) == _capi.EINVAL and b"divide" in lib.lvs_last_error()  # M does not divide d
+    assert pq(10, 64, 0, 65, 10, 7) == _capi.EINVAL and b"divide" in lib.lvs_last_error()  # M is reported ahead of nprobe
+    assert pq(10, 64, 0, 8, 10, 0) == _capi.EINVAL and b"M=0" in lib.lvs_last_error()
+
+
+# recorded from the library before the three searches shared their layout code; negative: LVS_EINVAL (-1) / LVS_EUNSUPPORTED (-4)
+IVF_WORKSPACE_BYTES = {
+    "flat": [
+        ((1, 64, 8, 768, 10, 0), 24576),
+        ((100, 4096, 32, 768, 16, 0), 7994368),
+        ((16384, 4096, 32, 768, 17, 1), 83019776),
+        ((100000, 4096, 2048, 1088, 56, 0), 486691584),
+        ((100000, 64, 32, 2240, 16, 0), 77744384),
+        ((0, 1, 1, 64, 1, 0), 8448),
+        ((100, 64, 65, 768, 10, 0), -1),
+        ((100, 64, 8, 768, 57, 0), -1),
+        ((100, 64, 8, 768, 10, 2), -1),
+        ((100, 64, 8, 1152, 16, 1), 2121728),
+        ((100, 64, 8, 1152, 17, 1), 2128128),
+        ((100, 64, 8, 2368, 56, 0), -4),
+        ((100, 64, 8, 2432, 16, 0), 2121728),
+        ((100, 64, 8, 3072, 10, 0), -4),
+    ],
+    "sq8": [
+        ((1, 64, 8, 768, 10, 0), 24576),
+        ((100, 4096, 32, 768, 16, 0), 7994368),
+        ((16384, 4096, 32, 768, 17, 1), 83019776),
+        ((100000, 4096, 2048, 1088, 56, 0), 486691584),
+        ((100000, 64, 32, 2240, 16, 0), 77744384),
+        ((0, 1, 1, 64, 1, 0), 8448),
+        ((100, 64, 65, 768, 10, 0), -1),
+        ((100, 64, 8, 768, 57, 0), -1),
+        ((100, 64, 8, 768, 10, 2), -1),
+        ((100, 64, 8, 1152, 16, 1), 2121728),
+        ((100, 64, 8, 1152, 17, 1), 2128128),
+        ((100, 64, 8, 2368, 56, 0), 2377728),
+        ((100, 64, 8, 2432, 16, 0), 2121728),
+        ((100, 64, 8, 3072, 10, 0), -4),
+    ],
+    "pq": [
+        ((1, 64, 8, 768, 64, 10, 0), 87552),
+        ((100, 4096, 32, 768, 64, 16, 0), 14468096),
+        ((16384, 4096, 32, 768, 96, 17, 1), 422592768),
+        ((100000, 4096, 2048, 1088, 64, 56, 0), 513771776),
+        ((100000, 64, 32, 1272, 159, 16, 0), 342892800),
+        ((100, 64, 8, 1600, 160, 10, 0), -4),
+        ((100, 64, 8, 768, 7, 10, 0), -1),
+        ((100, 64, 8, 768, 0, 10, 0), -1),
+        ((100, 64, 65, 768, 64, 10, 0), -1),
+        ((0, 1, 1, 64, 1, 1, 0), 7936),
+    ],
+}
+
+
+def test_ivf_workspace_sizes_without_a_gpu():
+    # scratch sizes are part of the contract with callers that size their own buffers: (nq, nlist, nprobe, d, k, pack) -> bytes
+    lib = _capi.load()
+    flat, sq8, pq = (lib.lvs_ivf_search_workspace_bytes, lib.lvs_ivf_sq8_search_workspace_bytes,
+                     lib.lvs_ivf_pq_search_workspace_bytes)
+    for args, want in IVF_WORKSPACE_BYTES["flat"]:
+        assert flat(*args) == want, args
+    for args, want in IVF_WORKSPACE_BYTES["sq8"]:
+        assert sq8(*args) == want, args
+    for args, want in IVF_WORKSPACE_BYTES["pq"]:  # (nq, nlist, nprobe, d, M, k, pack)
+        assert pq(*args) == want, args
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     import pytest
 
