@@ -45,3 +45,27 @@ def compare_topk(D_ref, I_ref, D, I, atol=1e-5, tie_gap=2e-5):
     inter = sum(len(set(a[a >= 0]) & set(b[b >= 0])) for a, b in zip(I_ref, I))
     denom = max(1, int(valid.sum()))
     return float(err), int(hard), inter / denom
+
+
+def check_ids_by_rescoring(score_fn, D, I, allowed_ids_per_query, bar):
+    """What compare_topk cannot see: it excuses an id mismatch at the last rank and inside near-tie groups, so a search
+    that returns the right score beside a wrong row number passes it (at k = 1 in every slot).  Here every returned slot
+    with I >= 0 must name one of the query's allowed rows (``allowed_ids_per_query[q]``: the rows of its probed lists), no
+    id may repeat within a query, and the float64 score of that very row, ``score_fn(q, ids)`` recomputed on the CPU over
+    the stored (Flat) or decoded (SQ8, PQ) rows, must lie within ``bar`` of the returned D.  Returns the largest
+    difference seen."""
+    D, I = np.asarray(D, np.float64), np.asarray(I)
+    worst = 0.0
+    for q in range(I.shape[0]):
+        at = I[q] >= 0
+        ids = I[q][at].astype(np.int64)
+        if ids.size == 0:
+            continue
+        assert np.unique(ids).size == ids.size, f"query {q}: an id repeats: {ids.tolist()}"
+        ok = np.isin(ids, np.asarray(allowed_ids_per_query[q]).astype(np.int64))
+        assert ok.all(), f"query {q}: ids {ids[~ok].tolist()} are in none of its probed lists"
+        diff = np.abs(np.asarray(score_fn(q, ids), np.float64) - D[q][at])
+        bad = diff > bar
+        assert not bad.any(), f"query {q}: ids {ids[bad].tolist()} rescore {diff[bad].tolist()} away from D (bar {bar})"
+        worst = max(worst, float(diff.max()))
+    return worst

@@ -6,6 +6,7 @@ import pytest
 
 import oracle
 import synth
+from ivf_edge_cases import rescoring_args
 from ivf_oracle_backend import ivf_reference
 from lotus_amd import HipVS, METRIC_INNER_PRODUCT, METRIC_L2, _capi
 
@@ -50,10 +51,15 @@ def _search(be, xb, xq, c, k, mode, metric, nprobe):
     return D.cpu().numpy(), I.cpu().numpy(), probe.cpu().numpy(), off, rows, cdev
 
 
-def _check(D_ref, I_ref, D, I):
+def _check(D_ref, I_ref, D, I, rescore=None):
+    """rescore = (rows scored: stored or decoded, queries, metric, offsets, rows, probe): every returned id is one of the
+    query's probed rows, unrepeated, and its float64 score is the returned one (synth.check_ids_by_rescoring)."""
     err, hard, _ = synth.compare_topk(D_ref, I_ref, D, I)
     assert err <= 1e-5 and hard == 0, (err, hard)
     assert np.array_equal(I == -1, I_ref == -1)
+    if rescore is not None:
+        score_fn, allowed = rescoring_args(*rescore)
+        synth.check_ids_by_rescoring(score_fn, D, I, allowed, 1e-5)
 
 
 def _check_lists(xb_s, cdev, off, rows, metric):
@@ -92,7 +98,7 @@ def test_all_lists_probed_is_exact_search(hip_backend, nb, d, nq, k, mode, metri
     D, I, probe, off, rows, cdev = _search(hip_backend, xb, xq, c, k, mode, metric, nlist)
     _check_lists(xb_s, cdev, off, rows, metric)
     D_ref, I_ref = oracle.flat_search(xb_s, xq_s, k, metric)
-    _check(D_ref, I_ref, D, I)
+    _check(D_ref, I_ref, D, I, rescore=(xb_s, xq_s, metric, off, rows, probe))
 
 
 # 2. + 3. nprobe < nlist: exact over the probed lists, and the probes are the nprobe best centroids
@@ -115,7 +121,7 @@ def test_partial_probe_is_exact_over_probed_lists(hip_backend, nb, d, nq, k, mod
     err, hard, _ = synth.compare_topk(Dp, Ip, Dp, probe)
     assert hard == 0
     D_ref, I_ref = ivf_reference(xb_s, xq_s, k, metric, cdev, off, rows, probe)
-    _check(D_ref, I_ref, D, I)
+    _check(D_ref, I_ref, D, I, rescore=(xb_s, xq_s, metric, off, rows, probe))
     if k == 56 and nlist == 200:
         assert (I == -1).any()
 
@@ -252,7 +258,7 @@ def test_full_size_1m_x_768(hip_backend):
     probe = vs.ivf_probe(xq[pick], 32)
     xq_s = xq[pick].astype(np.float32)
     D_ref, I_ref = ivf_reference(xb, xq_s, 10, IP, c, off, rows, probe)
-    _check(D_ref, I_ref, out.distances[pick], out.indices[pick])
+    _check(D_ref, I_ref, out.distances[pick], out.indices[pick], rescore=(xb, xq_s, IP, off, rows, probe))
 
 
 def test_queries_beyond_one_chunk(hip_backend):
@@ -268,7 +274,7 @@ def test_queries_beyond_one_chunk(hip_backend):
         Dp, Ip = oracle.flat_search(cdev, xq_s[pick], nprobe, metric)
         assert synth.compare_topk(Dp, Ip, Dp, probe[pick])[1] == 0
         D_ref, I_ref = ivf_reference(xb_s, xq_s[pick], k, metric, cdev, off, rows, probe[pick])
-        _check(D_ref, I_ref, D[pick], I[pick])
+        _check(D_ref, I_ref, D[pick], I[pick], rescore=(xb_s, xq_s[pick], metric, off, rows, probe[pick]))
 
 
 def test_fp32_rows_of_1536_dims(hip_backend, tmp_path):
@@ -294,5 +300,6 @@ def test_fp32_rows_of_1536_dims(hip_backend, tmp_path):
     assert t["kernel"] == "lvs_ivf_scan_kernel"
     x16, q16 = xb.astype(np.float16).astype(np.float32), xq.astype(np.float16).astype(np.float32)
     c, off, rows = h.ivf_lists()
-    D_ref, I_ref = ivf_reference(x16, q16, 10, IP, c, off, rows, h.ivf_probe(xq, 2))
-    _check(D_ref, I_ref, out.distances, out.indices)
+    probe = h.ivf_probe(xq, 2)
+    D_ref, I_ref = ivf_reference(x16, q16, 10, IP, c, off, rows, probe)
+    _check(D_ref, I_ref, out.distances, out.indices, rescore=(x16, q16, IP, off, rows, probe))

@@ -6,6 +6,7 @@ import pytest
 
 import oracle
 import synth
+from ivf_edge_cases import rescoring_args
 from ivf_oracle_backend import ivf_reference
 from ivf_pq_oracle_backend import list_of_rows, pq_decode, pq_encode, pq_margin, pq_reference
 from lotus_amd import HipVS, METRIC_INNER_PRODUCT, METRIC_L2, _capi
@@ -92,10 +93,15 @@ def _search(be, packed, lists, pq, xq, mode, k, metric, nprobe):
     return D.cpu().numpy(), I.cpu().numpy(), probe.cpu().numpy()
 
 
-def _check(D_ref, I_ref, D, I):
+def _check(D_ref, I_ref, D, I, rescore=None):
+    """rescore = (rows scored: stored or decoded, queries, metric, offsets, rows, probe): every returned id is one of the
+    query's probed rows, unrepeated, and its float64 score is the returned one (synth.check_ids_by_rescoring)."""
     err, hard, _ = synth.compare_topk(D_ref, I_ref, D, I)
     assert err <= 1e-5 and hard == 0, (err, hard)
     assert np.array_equal(I == -1, I_ref == -1)
+    if rescore is not None:
+        score_fn, allowed = rescoring_args(*rescore)
+        synth.check_ids_by_rescoring(score_fn, D, I, allowed, 1e-5)
 
 
 CASES = [
@@ -133,7 +139,7 @@ def test_codes_and_search_match_the_reference(hip_backend, nb, d, M, ksub, nq, k
     assert synth.compare_topk(Dp, Ip, Dp, probe)[1] == 0
     xhat = pq_decode(h["c"], h["where"], books, codes)
     D_ref, I_ref = pq_reference(xhat, xq_s, k, metric, h["off"], h["rows"], probe)
-    _check(D_ref, I_ref, D, I)
+    _check(D_ref, I_ref, D, I, rescore=(xhat, xq_s, metric, h["off"], h["rows"], probe))
     if nlist == 200:
         assert (I == -1).any()
 
@@ -158,7 +164,7 @@ def test_queries_beyond_one_chunk(hip_backend):
         assert synth.compare_topk(Dp, Ip, Dp, probe[pick])[1] == 0
         xhat = pq_decode(h["c"], h["where"], books, codes)
         D_ref, I_ref = pq_reference(xhat, xq_s[pick], k, metric, h["off"], h["rows"], probe[pick])
-        _check(D_ref, I_ref, D[pick], I[pick])
+        _check(D_ref, I_ref, D[pick], I[pick], rescore=(xhat, xq_s[pick], metric, h["off"], h["rows"], probe[pick]))
 
 
 @pytest.mark.parametrize("metric", [IP, L2])
@@ -186,7 +192,7 @@ def test_planted_lossless_rows(hip_backend, metric, d, M):
     for nprobe in (1, 3, nlist):
         D, I, probe = _search(be, packed, lists, pq, xq, SPLIT, k, metric, nprobe)
         D_ref, I_ref = ivf_reference(xb, xq, k, metric, c, h["off"], h["rows"], probe)
-        _check(D_ref, I_ref, D, I)
+        _check(D_ref, I_ref, D, I, rescore=(xb, xq, metric, h["off"], h["rows"], probe))
 
 
 @pytest.mark.parametrize("metric", [IP, L2])
@@ -235,7 +241,9 @@ def _reference_of(vs, xq, k, nprobe):
     c, off, rows = vs.ivf_lists()
     books, codes, _ = vs.pq_codes()
     xhat = pq_decode(c, list_of_rows(off, rows, codes.shape[0]), books, codes)
-    return pq_reference(xhat, np.asarray(xq, np.float32), k, vs.metric, off, rows, vs.ivf_probe(xq, nprobe))
+    probe = vs.ivf_probe(xq, nprobe)
+    D, I = pq_reference(xhat, np.asarray(xq, np.float32), k, vs.metric, off, rows, probe)
+    return D, I, (xhat, np.asarray(xq, np.float32), vs.metric, off, rows, probe)
 
 
 @pytest.mark.parametrize("metric", [METRIC_INNER_PRODUCT, METRIC_L2])
@@ -255,8 +263,8 @@ def test_hipvs_3072_dims_from_float64(hip_backend, tmp_path, monkeypatch, metric
     t = vs.backend.timing_read_full()
     vs.backend.timing_enable(False)
     assert t["kernel"] == "lvs_ivf_pq_scan_kernel" and t["calls"] == 1
-    D_ref, I_ref = _reference_of(vs, xq, 10, 4)
-    _check(D_ref, I_ref, out.distances, out.indices)
+    D_ref, I_ref, rescore = _reference_of(vs, xq, 10, 4)
+    _check(D_ref, I_ref, out.distances, out.indices, rescore=rescore)
 
     monkeypatch.setattr(cluster, "kmeans", lambda *a, **k: pytest.fail("k-means was called"))
     r2 = HipVS(factory_string="IVF16,PQ32x8", nprobe=4, metric=metric, device="cuda:0")

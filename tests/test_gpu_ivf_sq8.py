@@ -6,6 +6,7 @@ import pytest
 
 import oracle
 import synth
+from ivf_edge_cases import rescoring_args
 from ivf_sq8_oracle_backend import list_of_rows, sq8_boundary_distance, sq8_decode, sq8_encode, sq8_reference, sq8_train
 from lotus_amd import HipVS, METRIC_INNER_PRODUCT, METRIC_L2, _capi
 
@@ -76,10 +77,15 @@ def _search(be, packed, lists, sq, xq, mode, k, metric, nprobe):
     return D.cpu().numpy(), I.cpu().numpy(), probe.cpu().numpy()
 
 
-def _check(D_ref, I_ref, D, I):
+def _check(D_ref, I_ref, D, I, rescore=None):
+    """rescore = (rows scored: stored or decoded, queries, metric, offsets, rows, probe): every returned id is one of the
+    query's probed rows, unrepeated, and its float64 score is the returned one (synth.check_ids_by_rescoring)."""
     err, hard, _ = synth.compare_topk(D_ref, I_ref, D, I)
     assert err <= 1e-5 and hard == 0, (err, hard)
     assert np.array_equal(I == -1, I_ref == -1)
+    if rescore is not None:
+        score_fn, allowed = rescoring_args(*rescore)
+        synth.check_ids_by_rescoring(score_fn, D, I, allowed, 1e-5)
 
 
 CASES = [
@@ -111,7 +117,7 @@ def test_codes_and_search_match_the_reference(hip_backend, nb, d, nq, k, mode, m
     assert synth.compare_topk(Dp, Ip, Dp, probe)[1] == 0
     xhat = sq8_decode(h["c"], h["where"], h["vmin"], h["vdiff"], h["codes"])
     D_ref, I_ref = sq8_reference(xhat, xq_s, k, metric, h["off"], h["rows"], probe)
-    _check(D_ref, I_ref, D, I)
+    _check(D_ref, I_ref, D, I, rescore=(xhat, xq_s, metric, h["off"], h["rows"], probe))
     if nlist == 200:
         assert (I == -1).any()
 
@@ -131,7 +137,7 @@ def test_queries_beyond_one_chunk(hip_backend):
         assert synth.compare_topk(Dp, Ip, Dp, probe[pick])[1] == 0
         xhat = sq8_decode(h["c"], h["where"], h["vmin"], h["vdiff"], h["codes"])
         D_ref, I_ref = sq8_reference(xhat, xq_s[pick], k, metric, h["off"], h["rows"], probe[pick])
-        _check(D_ref, I_ref, D[pick], I[pick])
+        _check(D_ref, I_ref, D[pick], I[pick], rescore=(xhat, xq_s[pick], metric, h["off"], h["rows"], probe[pick]))
 
 
 @pytest.mark.parametrize("metric", [IP, L2])
@@ -165,7 +171,9 @@ def _reference_of(vs, xq, k, nprobe):
     c, off, rows = vs.ivf_lists()
     vmin, vdiff, codes, _ = vs.sq8_codes()
     xhat = sq8_decode(c, list_of_rows(off, rows, codes.shape[0]), vmin, vdiff, codes)
-    return sq8_reference(xhat, np.asarray(xq, np.float32), k, vs.metric, off, rows, vs.ivf_probe(xq, nprobe))
+    probe = vs.ivf_probe(xq, nprobe)
+    D, I = sq8_reference(xhat, np.asarray(xq, np.float32), k, vs.metric, off, rows, probe)
+    return D, I, (xhat, np.asarray(xq, np.float32), vs.metric, off, rows, probe)
 
 
 @pytest.mark.parametrize("metric", [METRIC_INNER_PRODUCT, METRIC_L2])
@@ -184,8 +192,8 @@ def test_hipvs_1536_dims_from_float64(hip_backend, tmp_path, monkeypatch, metric
     t = vs.backend.timing_read_full()
     vs.backend.timing_enable(False)
     assert t["kernel"] == "lvs_ivf_sq8_scan_kernel" and t["calls"] == 1
-    D_ref, I_ref = _reference_of(vs, xq, 10, 2)
-    _check(D_ref, I_ref, out.distances, out.indices)
+    D_ref, I_ref, rescore = _reference_of(vs, xq, 10, 2)
+    _check(D_ref, I_ref, out.distances, out.indices, rescore=rescore)
 
     monkeypatch.setattr(cluster, "kmeans", lambda *a, **k: pytest.fail("k-means was called"))
     r2 = HipVS(factory_string="IVF16,SQ8", nprobe=2, metric=metric, device="cuda:0")
