@@ -1024,18 +1024,20 @@ class HipBackend:
         out[lists.rows.to(torch.int64) & 0xFFFFFFFF] = lid
         return out
 
+    def _train_residuals(self, packed: PackedRows, lists: IvfLists, ids_dev):
+        """float32 [len(ids_dev), d], stored scale: the residuals x - c_l of the rows ``ids_dev`` against their lists' centroids."""
+        c = self.unpack(lists.centroids, raw=True)
+        return self.unpack(packed, ids_dev, raw=True) - c[self._list_of_rows(lists, packed.n)[ids_dev]]
+
     def ivf_sq8_train(self, packed: PackedRows, lists: IvfLists, train_ids):
         """-> (vmin, vdiff) float32 [d] device tensors in the stored scale: per-dimension range of the residuals x - c_l of the
         training rows ``train_ids`` (host int64; faiss trains the scalar quantizer on the coarse quantizer's training set)."""
         torch = self.torch
-        c = self.unpack(lists.centroids, raw=True)
-        where = self._list_of_rows(lists, packed.n)
         ids = np.asarray(train_ids, dtype=np.int64)
         vmin = torch.full((packed.d,), float("inf"), dtype=torch.float32, device=self.device)
         vmax = torch.full((packed.d,), float("-inf"), dtype=torch.float32, device=self.device)
         for r0 in range(0, len(ids), self.SQ8_TRAIN_CHUNK_ROWS):
-            idd = self.to_device(ids[r0:r0 + self.SQ8_TRAIN_CHUNK_ROWS])
-            r = self.unpack(packed, idd, raw=True) - c[where[idd]]
+            r = self._train_residuals(packed, lists, self.to_device(ids[r0:r0 + self.SQ8_TRAIN_CHUNK_ROWS]))
             vmin = torch.minimum(vmin, r.amin(dim=0))
             vmax = torch.maximum(vmax, r.amax(dim=0))
         return vmin, vmax - vmin
@@ -1096,10 +1098,7 @@ class HipBackend:
         cap = ksub * self.PQ_MAX_POINTS_PER_CENTROID
         if len(ids) > cap:
             ids = ids[self.rand_perm(len(ids), self.PQ_SEED, cap)]
-        c = self.unpack(lists.centroids, raw=True)
-        where = self._list_of_rows(lists, packed.n)
-        idd = self.to_device(ids)
-        r = (self.unpack(packed, idd, raw=True) - c[where[idd]]).cpu().numpy()
+        r = self._train_residuals(packed, lists, self.to_device(ids)).cpu().numpy()
         books = np.empty((M, ksub, dsub), np.float32)
         for m in range(M):
             res = cluster.kmeans(np.ascontiguousarray(r[:, m * dsub:(m + 1) * dsub]), ksub, niter=self.PQ_NITER,

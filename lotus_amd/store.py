@@ -251,26 +251,52 @@ IVF_SIDECAR = "ivf.npz"
 IVF_VERSION = 1
 
 
-def write_ivf(index_dir: str, nlist: int, metric: int, pack_mode: int, centroids: np.ndarray, offsets: np.ndarray,
-              rows: np.ndarray) -> None:
-    """Write the sidecar atomically (temporary file + rename)."""
-    n, d = int(rows.shape[0]), int(centroids.shape[1])
-    header = {"version": IVF_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "d": d, "n": n,
-              "written_with": _file_stamps(index_dir)}
+def _write_sidecar(index_dir: str, name: str, header: dict, arrays: dict) -> None:
+    """Write ``{dir}/{name}`` atomically (temporary file + rename): the header, stamped with the content stamp of ``index`` /
+    ``vecs`` as they are now, as a JSON string beside the arrays."""
     import tempfile
 
-    fd, tmp = tempfile.mkstemp(prefix="ivf.", suffix=".npz.tmp", dir=index_dir)
+    header = dict(header, written_with=_file_stamps(index_dir))
+    fd, tmp = tempfile.mkstemp(prefix=os.path.splitext(name)[0] + ".", suffix=".npz.tmp", dir=index_dir)
     try:
         with os.fdopen(fd, "wb") as fp:
-            np.savez(fp, header=np.array(json.dumps(header)), centroids=np.ascontiguousarray(centroids, dtype=np.float32),
-                     offsets=np.ascontiguousarray(offsets, dtype=np.int64), rows=np.ascontiguousarray(rows, dtype=np.uint32))
-        os.replace(tmp, os.path.join(index_dir, IVF_SIDECAR))
+            np.savez(fp, header=np.array(json.dumps(header)), **arrays)
+        os.replace(tmp, os.path.join(index_dir, name))
     except BaseException:
         try:
             os.unlink(tmp)
         except OSError:
             pass
         raise
+
+
+def _read_sidecar(index_dir: str, name: str, want: dict, keys: tuple):
+    """-> (header, [the arrays ``keys``]) of ``{dir}/{name}``, or None when it is missing or unreadable, its header is not
+    what ``want`` names, or ``index`` / ``vecs`` changed since it was written."""
+    path = os.path.join(index_dir, name)
+    if not os.path.exists(path):
+        return None
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            header = json.loads(str(z["header"]))
+            arrays = [np.array(z[key]) for key in keys]
+    except (OSError, ValueError, KeyError, TypeError):
+        return None
+    if not isinstance(header, dict) or any(header.get(key) != val for key, val in want.items()):
+        return None
+    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
+        return None
+    return header, arrays
+
+
+def write_ivf(index_dir: str, nlist: int, metric: int, pack_mode: int, centroids: np.ndarray, offsets: np.ndarray,
+              rows: np.ndarray) -> None:
+    """Write the sidecar atomically (temporary file + rename)."""
+    n, d = int(rows.shape[0]), int(centroids.shape[1])
+    header = {"version": IVF_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "d": d, "n": n}
+    _write_sidecar(index_dir, IVF_SIDECAR, header, {
+        "centroids": np.ascontiguousarray(centroids, dtype=np.float32), "offsets": np.ascontiguousarray(offsets, dtype=np.int64),
+        "rows": np.ascontiguousarray(rows, dtype=np.uint32)})
 
 
 def _ivf_stamps_valid(index_dir: str, stamps) -> bool:
@@ -292,20 +318,11 @@ def _ivf_stamps_valid(index_dir: str, stamps) -> bool:
 def read_ivf(index_dir: str, nlist: int, metric: int, pack_mode: int, d: int, n: int):
     """-> (centroids float32 [nlist_eff, d], offsets int64 [nlist_eff + 1], rows uint32 [n]) from a valid sidecar written for
     this nlist, metric, pack mode and shape, else None (missing, unreadable, stale or built otherwise)."""
-    path = os.path.join(index_dir, IVF_SIDECAR)
-    if not os.path.exists(path):
-        return None
-    try:
-        with np.load(path, allow_pickle=False) as z:
-            header = json.loads(str(z["header"]))
-            c, off, rows = np.array(z["centroids"]), np.array(z["offsets"]), np.array(z["rows"])
-    except (OSError, ValueError, KeyError, TypeError):
-        return None
     want = {"version": IVF_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "d": int(d), "n": int(n)}
-    if any(header.get(key) != val for key, val in want.items()):
+    side = _read_sidecar(index_dir, IVF_SIDECAR, want, ("centroids", "offsets", "rows"))
+    if side is None:
         return None
-    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
-        return None
+    c, off, rows = side[1]
     m = int(c.shape[0]) if c.ndim == 2 else -1
     if (m < 1 or c.shape[1] != d or c.dtype != np.float32 or off.shape != (m + 1,) or off.dtype != np.int64
             or rows.shape != (n,) or rows.dtype != np.uint32 or off[0] != 0 or off[-1] > n or (np.diff(off) < 0).any()
@@ -338,42 +355,21 @@ def write_ivf_sq8(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: 
     """Write the SQ8 sidecar atomically (temporary file + rename)."""
     n, d = int(codes.shape[0]), int(codes.shape[1])
     header = {"version": IVF_SQ8_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
-              "d": d, "n": n, "lists": str(lists_digest), "written_with": _file_stamps(index_dir)}
-    import tempfile
-
-    fd, tmp = tempfile.mkstemp(prefix="ivf_sq8.", suffix=".npz.tmp", dir=index_dir)
-    try:
-        with os.fdopen(fd, "wb") as fp:
-            np.savez(fp, header=np.array(json.dumps(header)), vmin=np.ascontiguousarray(vmin, dtype=np.float32),
-                     vdiff=np.ascontiguousarray(vdiff, dtype=np.float32), codes=np.ascontiguousarray(codes, dtype=np.uint8),
-                     rnorm=np.ascontiguousarray(rnorm, dtype=np.float32))
-        os.replace(tmp, os.path.join(index_dir, IVF_SQ8_SIDECAR))
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
+              "d": d, "n": n, "lists": str(lists_digest)}
+    _write_sidecar(index_dir, IVF_SQ8_SIDECAR, header, {
+        "vmin": np.ascontiguousarray(vmin, dtype=np.float32), "vdiff": np.ascontiguousarray(vdiff, dtype=np.float32),
+        "codes": np.ascontiguousarray(codes, dtype=np.uint8), "rnorm": np.ascontiguousarray(rnorm, dtype=np.float32)})
 
 
 def read_ivf_sq8(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: int, d: int, n: int, lists_digest: str):
     """-> (vmin float32 [d], vdiff float32 [d], codes uint8 [n, d] in list order, rnorm float32 [n]) from a valid SQ8 sidecar
     written for these lists (``ivf_digest``), nlist, metric, pack mode and exponent and shape, else None."""
-    path = os.path.join(index_dir, IVF_SQ8_SIDECAR)
-    if not os.path.exists(path):
-        return None
-    try:
-        with np.load(path, allow_pickle=False) as z:
-            header = json.loads(str(z["header"]))
-            vmin, vdiff, codes, rnorm = np.array(z["vmin"]), np.array(z["vdiff"]), np.array(z["codes"]), np.array(z["rnorm"])
-    except (OSError, ValueError, KeyError, TypeError):
-        return None
     want = {"version": IVF_SQ8_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
             "d": int(d), "n": int(n), "lists": str(lists_digest)}
-    if not isinstance(header, dict) or any(header.get(key) != val for key, val in want.items()):
+    side = _read_sidecar(index_dir, IVF_SQ8_SIDECAR, want, ("vmin", "vdiff", "codes", "rnorm"))
+    if side is None:
         return None
-    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
-        return None
+    vmin, vdiff, codes, rnorm = side[1]
     if (vmin.shape != (d,) or vdiff.shape != (d,) or vmin.dtype != np.float32 or vdiff.dtype != np.float32
             or codes.shape != (n, d) or codes.dtype != np.uint8 or rnorm.shape != (n,) or rnorm.dtype != np.float32):
         return None
@@ -393,43 +389,21 @@ def write_ivf_pq(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: i
     """Write the PQ sidecar atomically (temporary file + rename)."""
     M, ksub, dsub = (int(v) for v in codebooks.shape)
     header = {"version": IVF_PQ_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
-              "d": M * dsub, "M": M, "ksub": ksub, "n": int(codes.shape[0]), "lists": str(lists_digest),
-              "written_with": _file_stamps(index_dir)}
-    import tempfile
-
-    fd, tmp = tempfile.mkstemp(prefix="ivf_pq.", suffix=".npz.tmp", dir=index_dir)
-    try:
-        with os.fdopen(fd, "wb") as fp:
-            np.savez(fp, header=np.array(json.dumps(header)), codebooks=np.ascontiguousarray(codebooks, dtype=np.float32),
-                     codes=np.ascontiguousarray(codes, dtype=np.uint8), beta=np.ascontiguousarray(beta, dtype=np.float32))
-        os.replace(tmp, os.path.join(index_dir, IVF_PQ_SIDECAR))
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
+              "d": M * dsub, "M": M, "ksub": ksub, "n": int(codes.shape[0]), "lists": str(lists_digest)}
+    _write_sidecar(index_dir, IVF_PQ_SIDECAR, header, {
+        "codebooks": np.ascontiguousarray(codebooks, dtype=np.float32), "codes": np.ascontiguousarray(codes, dtype=np.uint8),
+        "beta": np.ascontiguousarray(beta, dtype=np.float32)})
 
 
 def read_ivf_pq(index_dir: str, nlist: int, metric: int, pack_mode: int, exp: int, d: int, M: int, n: int, lists_digest: str):
     """-> (codebooks float32 [M, ksub, d / M], codes uint8 [n, M] in list order, beta float32 [n]) from a valid PQ sidecar
     written for these lists (``ivf_digest``), nlist, metric, pack mode, exponent, M and shape, else None."""
-    path = os.path.join(index_dir, IVF_PQ_SIDECAR)
-    if not os.path.exists(path):
-        return None
-    try:
-        with np.load(path, allow_pickle=False) as z:
-            header = json.loads(str(z["header"]))
-            books, codes, beta = np.array(z["codebooks"]), np.array(z["codes"]), np.array(z["beta"])
-    except (OSError, ValueError, KeyError, TypeError):
-        return None
     want = {"version": IVF_PQ_VERSION, "nlist": int(nlist), "metric": int(metric), "pack": int(pack_mode), "exp": int(exp),
             "d": int(d), "M": int(M), "n": int(n), "lists": str(lists_digest)}
-    if not isinstance(header, dict) or any(header.get(key) != val for key, val in want.items()):
+    side = _read_sidecar(index_dir, IVF_PQ_SIDECAR, want, ("codebooks", "codes", "beta"))
+    if side is None:
         return None
-    if not _ivf_stamps_valid(index_dir, header.get("written_with")):
-        return None
-    ksub = header.get("ksub")
+    ksub, (books, codes, beta) = side[0].get("ksub"), side[1]
     if (not isinstance(ksub, int) or not 1 <= ksub <= 256 or M < 1 or d % M != 0
             or books.shape != (M, ksub, d // M) or books.dtype != np.float32
             or codes.shape != (n, M) or codes.dtype != np.uint8 or beta.shape != (n,) or beta.dtype != np.float32

@@ -54,8 +54,92 @@ class _Resident:
     hi: int
     sig: Any = None  # store.signature() of the directory when it was loaded (None: never persisted)
     ivf: Any = None  # backend IvfLists over `packed` (IVF stores only): centroids, offsets, row numbers
-    sq8: Any = None  # backend IvfSq8Lists beside `ivf` (IVF-SQ8 stores only): codec and codes in list order
-    pq: Any = None  # backend IvfPqLists beside `ivf` (IVF-PQ stores only): codebooks and codes in list order
+    codes: Any = None  # beside `ivf`, the codec and codes in list order: backend IvfSq8Lists / IvfPqLists (None: IVF-Flat)
+
+
+@dataclass(frozen=True)
+class _IvfMode:
+    """The mode of an IVF store, parsed once from its factory string: all that differs between IVF-Flat, IVF-SQ8 and IVF-PQ.
+    ``ent``: the store's ``_Resident``, whose ``codes`` this mode's ``train`` or ``upload`` made."""
+
+    kind: str  # "Flat" | "SQ8" | "PQ"
+    M: int | None = None  # subspaces of a PQ store
+
+    @property
+    def requires(self):  # the method an injected backend must have to build such a store: asked of the newest mode only
+        return "ivf_pq_search" if self.kind == "PQ" else None
+
+    def check_width(self, d: int, factory_string: str) -> None:
+        """faiss asserts d % M == 0 for a product quantizer: rows of another width cannot back an IVF-PQ store."""
+        if self.kind == "PQ" and d % self.M != 0:
+            raise ValueError(f"factory_string={factory_string!r} needs a dimension divisible by M={self.M}, got d={d}")
+
+    def fits(self, be, ent, k: int) -> bool:
+        if self.kind == "SQ8":
+            return be.ivf_sq8_fits(ent.d, k, ent.packed.mode)
+        if self.kind == "PQ":
+            return be.ivf_pq_fits(ent.d, self.M, k, ent.packed.mode)
+        return be.ivf_fits(ent.d, k, ent.packed.mode)
+
+    def search(self, be, ent, queries, k: int, metric: int, nprobe: int, want_probe: bool = False):
+        if self.kind == "SQ8":
+            return be.ivf_sq8_search(ent.packed, ent.ivf, ent.codes, queries, k, metric, nprobe, want_probe)
+        if self.kind == "PQ":
+            return be.ivf_pq_search(ent.packed, ent.ivf, ent.codes, queries, k, metric, nprobe, want_probe)
+        return be.ivf_search(ent.packed, ent.ivf, queries, k, metric, nprobe, want_probe)
+
+    def train(self, be, packed, lists, train_ids):
+        """-> the codec trained on the residuals of the k-means training rows, with every row's codes (IVF-Flat: None)."""
+        if self.kind == "SQ8":
+            return be.ivf_sq8_encode(packed, lists, *be.ivf_sq8_train(packed, lists, train_ids))
+        if self.kind == "PQ":
+            return be.ivf_pq_encode(packed, lists, be.ivf_pq_train(packed, lists, train_ids, self.M))
+        return None
+
+    def read(self, index_dir: str, nlist: int, metric: int, ent, lists_host):
+        """-> the arrays of the codes' sidecar, as ``upload`` takes them (IVF-Flat has none: ()), or None when it is not valid
+        for the lists ``lists_host`` (what ``store.read_ivf`` gave)."""
+        head = (index_dir, nlist, metric, ent.packed.mode, ent.packed.exp, ent.d)
+        if self.kind == "SQ8":
+            return store.read_ivf_sq8(*head, ent.n, store.ivf_digest(*lists_host))
+        if self.kind == "PQ":
+            return store.read_ivf_pq(*head, self.M, ent.n, store.ivf_digest(*lists_host))
+        return ()
+
+    def upload(self, be, packed, lists, side):
+        """``side`` follows the encode call's arguments: the codec, then ``codes=`` and the per-row term - only uploaded."""
+        if self.kind == "SQ8":
+            return be.ivf_sq8_encode(packed, lists, *side)
+        return be.ivf_pq_encode(packed, lists, *side) if self.kind == "PQ" else None
+
+    def write(self, index_dir: str, nlist: int, metric: int, ent, lists_host) -> None:
+        cd, head = ent.codes, (index_dir, nlist, metric, ent.packed.mode)
+        if self.kind == "SQ8":
+            store.write_ivf_sq8(*head, cd.exp, _host(cd.vmin), _host(cd.vdiff), _host(cd.codes[:, :ent.d]), _host(cd.rnorm),
+                                store.ivf_digest(*lists_host))
+        if self.kind == "PQ":
+            store.write_ivf_pq(*head, cd.exp, _host(cd.codebooks), _host(cd.codes[:, :cd.M]), _host(cd.beta),
+                               store.ivf_digest(*lists_host))
+
+    def export(self, ent):
+        """The codec and the codes in ROW order, in the caller's units (``HipVS.sq8_codes`` / ``pq_codes``)."""
+        cd = ent.codes
+        scale = np.float32(2.0) ** -cd.exp  # exact: the stored scale is a power of two
+        rows = _host(ent.ivf.rows).view(np.uint32).astype(np.int64)
+
+        def by_row(t):  # list order (position p holds row rows[p]) -> row order
+            a = _host(t)
+            out = np.empty(a.shape, a.dtype)
+            out[rows] = a
+            return out
+
+        if self.kind == "SQ8":
+            return _host(cd.vmin) * scale, _host(cd.vdiff) * scale, by_row(cd.codes[:, :ent.d]), by_row(cd.rnorm) * (scale * scale)
+        return _host(cd.codebooks) * scale, by_row(cd.codes[:, :cd.M]), by_row(cd.beta) * (scale * scale)
+
+
+def _host(t) -> np.ndarray:
+    return t.cpu().numpy()
 
 
 def _serialised(fn):
@@ -135,14 +219,15 @@ class HipVS(VS):
         if factory_string != "Flat" and (m is None or int(m.group(1)) < 1 or (m.group(3) is not None and int(m.group(3)) < 1)):
             raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' or 'IVF<nlist>,PQ<M>[x8]' "
                              f"(nlist >= 1, M >= 1, 8-bit codes), got {factory_string!r}")
+        self._nlist = int(m.group(1)) if m is not None else None
+        # None for "Flat"; an IVF store's mode makes every call that differs between IVF-Flat, IVF-SQ8 and IVF-PQ
+        self._mode = None if m is None else _IvfMode("PQ", int(m.group(3))) if m.group(3) is not None else _IvfMode(m.group(2))
         # an injected backend without the IVF-PQ codec (a test double of an earlier mode) cannot build such a store
-        if m is not None and m.group(3) is not None and backend is not None and not hasattr(backend, "ivf_pq_search"):
+        needs = self._mode.requires if self._mode is not None and backend is not None else None
+        if needs is not None and not hasattr(backend, needs):
             raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' with a backend that has "
                              f"no IVF-PQ codec ({type(backend).__name__}), got {factory_string!r}")
         self.factory_string = factory_string
-        self._nlist = int(m.group(1)) if m is not None else None
-        self._sq8 = m is not None and m.group(2) == "SQ8"
-        self._pq_m = int(m.group(3)) if m is not None and m.group(3) is not None else None  # M of an IVF-PQ store
         if self._nlist is not None and shard is not False:
             raise ValueError(f"an IVF index is single-GPU: shard must be False with factory_string={factory_string!r}")
         self.nprobe = self._check_nprobe(nprobe)
@@ -361,7 +446,7 @@ class HipVS(VS):
         device image).  Rank 0 writes the reference's two files plus the mappable row store (``lotus_amd/store.py``);
         ``persist=False`` skips the disk entirely, ``raw=False`` writes the reference's files only."""
         emb = self._as_matrix(embeddings, "embeddings")
-        self._check_pq_width(int(emb.shape[1]))
+        self._check_width(int(emb.shape[1]))
         rank, world = self._group()  # under the query split every rank holds the whole corpus, but only ONE may write it
         persist = bool(kwargs.get("persist", True))
         is_dev = self._is_device_tensor(emb)
@@ -377,8 +462,7 @@ class HipVS(VS):
         ent = self._install(index_dir, emb, stored=None if is_dev else emb,
                             sig=store.signature(index_dir) if persist else None)
         if self._nlist is not None:
-            ent.ivf, codec = self._ivf_train(ent)
-            ent.sq8, ent.pq = (None, codec) if self._pq_m is not None else (codec, None)
+            ent.ivf, ent.codes = self._ivf_train(ent)
             if persist:
                 self._ivf_write(index_dir, ent, best_effort=False)
         self.index_dir = index_dir
@@ -396,30 +480,17 @@ class HipVS(VS):
         sig = store.signature(index_dir)
         rows, _ = store.open_device_rows(index_dir)
         rows = self._as_matrix(rows, "stored vectors")
-        self._check_pq_width(int(rows.shape[1]))
+        self._check_width(int(rows.shape[1]))
         ent = self._install(index_dir, rows, stored=None, sig=sig)
         if self._nlist is not None and ent.n:
             side = store.read_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, ent.d, ent.n)
-            side8 = None
-            if side is not None and self._sq8:
-                side8 = store.read_ivf_sq8(index_dir, self._nlist, self.metric, ent.packed.mode, ent.packed.exp, ent.d, ent.n,
-                                           store.ivf_digest(*side))
-            sidepq = None
-            if side is not None and self._pq_m is not None:
-                sidepq = store.read_ivf_pq(index_dir, self._nlist, self.metric, ent.packed.mode, ent.packed.exp, ent.d,
-                                           self._pq_m, ent.n, store.ivf_digest(*side))
-            if side is not None and (side8 is not None or not self._sq8) and (sidepq is not None or self._pq_m is None):
+            side_codes = self._mode.read(index_dir, self._nlist, self.metric, ent, side) if side is not None else None
+            if side_codes is not None:
                 c, off, rr = side
                 ent.ivf = self.backend.ivf_build(ent.packed, c, self.metric, offsets=off, rows=rr)
-                if side8 is not None:
-                    vmin, vdiff, codes, rnorm = side8
-                    ent.sq8 = self.backend.ivf_sq8_encode(ent.packed, ent.ivf, vmin, vdiff, codes=codes, rnorm=rnorm)
-                if sidepq is not None:
-                    books, codes, beta = sidepq
-                    ent.pq = self.backend.ivf_pq_encode(ent.packed, ent.ivf, books, codes=codes, beta=beta)
+                ent.codes = self._mode.upload(self.backend, ent.packed, ent.ivf, side_codes)
             else:  # missing, stale or built for another nlist / metric: train again and try to leave valid sidecars behind
-                ent.ivf, codec = self._ivf_train(ent)
-                ent.sq8, ent.pq = (None, codec) if self._pq_m is not None else (codec, None)
+                ent.ivf, ent.codes = self._ivf_train(ent)
                 self._ivf_write(index_dir, ent, best_effort=True)
         self.index_dir = index_dir
 
@@ -482,10 +553,7 @@ class HipVS(VS):
         # sem_search's K-doubling loop (sem_search.py:120-138) once the probed lists hold fewer than K rows
         nprobe = min(self._check_nprobe(kwargs.get("nprobe", self.nprobe)), ent.ivf.nlist) if ent.ivf is not None else 0
         use_ivf = (ent.ivf is not None and sub is None and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
-                   and qworld == 1 and nprobe <= _capi.MAX_K
-                   and (be.ivf_sq8_fits(ent.d, K, ent.packed.mode) if ent.sq8 is not None
-                        else be.ivf_pq_fits(ent.d, ent.pq.M, K, ent.packed.mode) if ent.pq is not None
-                        else be.ivf_fits(ent.d, K, ent.packed.mode)))
+                   and qworld == 1 and nprobe <= _capi.MAX_K and self._mode.fits(be, ent, K))
         q_all = nq
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
             per = -(-nq // qworld)
@@ -544,12 +612,8 @@ class HipVS(VS):
             if order is not None:
                 id_map = be.to_device(order)
             world = 1  # already complete on every rank: nothing left to merge
-        elif use_ivf and ent.sq8 is not None:
-            keys = be.ivf_sq8_search(ent.packed, ent.ivf, ent.sq8, queries, k_eff, self.metric, nprobe)
-        elif use_ivf and ent.pq is not None:
-            keys = be.ivf_pq_search(ent.packed, ent.ivf, ent.pq, queries, k_eff, self.metric, nprobe)
         elif use_ivf:
-            keys = be.ivf_search(ent.packed, ent.ivf, queries, k_eff, self.metric, nprobe)
+            keys = self._mode.search(be, ent, queries, k_eff, self.metric, nprobe)
         elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
             # the same row-sharded search with its two exchanges issued from INSIDE the C ABI (lvs_search_sharded): the transport
             # is this process group's all-gather, handed over as a callback
@@ -613,9 +677,9 @@ class HipVS(VS):
         return int(nprobe)
 
     def _ivf_train(self, ent: _Resident):
-        """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store, and for an SQ8
-        store the codec trained on the residuals of the k-means training rows and the codes -> (lists, sq8 or None); for
-        a PQ store likewise its codebooks and codes -> (lists, pq); (None, None) without rows."""
+        """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store, and for an SQ8 or
+        PQ store the codec trained on the residuals of the k-means training rows and the codes -> (lists, codes or None);
+        (None, None) without rows."""
         if ent.n == 0:
             return None, None
         from . import cluster
@@ -627,29 +691,15 @@ class HipVS(VS):
                              final_assign=False)
         # rows go to their best centroid under the index's metric, against the final centroids (faiss's IVF quantizer)
         lists = be.ivf_build(ent.packed, np.asarray(res.centroids, dtype=np.float32), self.metric)
-        if self._pq_m is not None:
-            books = be.ivf_pq_train(ent.packed, lists, res.train_ids, self._pq_m)
-            return lists, be.ivf_pq_encode(ent.packed, lists, books)
-        if not self._sq8:
-            return lists, None
-        vmin, vdiff = be.ivf_sq8_train(ent.packed, lists, res.train_ids)
-        return lists, be.ivf_sq8_encode(ent.packed, lists, vmin, vdiff)
+        return lists, self._mode.train(be, ent.packed, lists, res.train_ids)
 
     def _ivf_write(self, index_dir: str, ent: _Resident, best_effort: bool) -> None:
         if ent.ivf is None:
             return
-        c, off, rows = self._ivf_host(ent.ivf)
+        lists_host = self._ivf_host(ent.ivf)
         try:
-            store.write_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, c, off, rows)
-            if ent.sq8 is not None:
-                sq = ent.sq8
-                store.write_ivf_sq8(index_dir, self._nlist, self.metric, ent.packed.mode, sq.exp,
-                                    sq.vmin.cpu().numpy(), sq.vdiff.cpu().numpy(), sq.codes[:, :ent.d].cpu().numpy(),
-                                    sq.rnorm.cpu().numpy(), store.ivf_digest(c, off, rows))
-            if ent.pq is not None:
-                pq = ent.pq
-                store.write_ivf_pq(index_dir, self._nlist, self.metric, ent.packed.mode, pq.exp, pq.codebooks.cpu().numpy(),
-                                   pq.codes[:, :pq.M].cpu().numpy(), pq.beta.cpu().numpy(), store.ivf_digest(c, off, rows))
+            store.write_ivf(index_dir, self._nlist, self.metric, ent.packed.mode, *lists_host)
+            self._mode.write(index_dir, self._nlist, self.metric, ent, lists_host)
         except OSError:
             if not best_effort:
                 raise
@@ -687,14 +737,8 @@ class HipVS(VS):
         queries = be.pack(q, ent.packed.mode, normalize=self.normalize, exp=ent.packed.exp, check=True)
         if queries.n == 0:
             return np.zeros((0, nprobe), np.int32)
-        if ent.sq8 is not None and be.ivf_sq8_fits(ent.d, 1, ent.packed.mode):
-            _, probe = be.ivf_sq8_search(ent.packed, ent.ivf, ent.sq8, queries, 1, self.metric, nprobe, want_probe=True)
-            return probe.cpu().numpy()
-        if ent.pq is not None and be.ivf_pq_fits(ent.d, ent.pq.M, 1, ent.packed.mode):
-            _, probe = be.ivf_pq_search(ent.packed, ent.ivf, ent.pq, queries, 1, self.metric, nprobe, want_probe=True)
-            return probe.cpu().numpy()
-        if ent.sq8 is None and ent.pq is None and be.ivf_fits(ent.d, 1, ent.packed.mode):
-            _, probe = be.ivf_search(ent.packed, ent.ivf, queries, 1, self.metric, nprobe, want_probe=True)
+        if self._mode.fits(be, ent, 1):
+            _, probe = self._mode.search(be, ent, queries, 1, self.metric, nprobe, want_probe=True)
             return probe.cpu().numpy()
         # the coarse step on its own: lvs_flat_search_keys over the centroids, as inside lvs_ivf_search_keys
         keys = be.search_keys(ent.ivf.centroids, queries, nprobe, self.metric, one_pass=False).cpu().numpy().view(np.uint64)
@@ -706,17 +750,7 @@ class HipVS(VS):
         IVF-SQ8 store, in the caller's units: row i decodes to ``c_l + vmin + (codes[i] + 0.5) * vdiff / 255`` (``l``: its
         list in ``ivf_lists()``, ``c_l`` its centroid there), and ``norms[i]`` is ``|vmin + (codes[i] + 0.5) * vdiff / 255|^2``
         as the device computed it in fp32."""
-        ent = self._ivf_current()
-        if ent.sq8 is None:
-            raise ValueError("the loaded index has no SQ8 codes (factory_string is not 'IVF<nlist>,SQ8')")
-        sq = ent.sq8
-        scale = np.float32(2.0) ** -sq.exp  # exact: the stored scale is a power of two
-        rows = ent.ivf.rows.cpu().numpy().view(np.uint32).astype(np.int64)
-        codes = np.empty((ent.n, ent.d), np.uint8)
-        codes[rows] = sq.codes[:, :ent.d].cpu().numpy()
-        rnorm = np.empty(ent.n, np.float32)
-        rnorm[rows] = sq.rnorm.cpu().numpy() * (scale * scale)
-        return sq.vmin.cpu().numpy() * scale, sq.vdiff.cpu().numpy() * scale, codes, rnorm
+        return self._export_codes("SQ8", "SQ8")
 
     @_serialised
     def pq_codes(self):
@@ -724,22 +758,17 @@ class HipVS(VS):
         the caller's units: row i decodes to ``c_l + concat_m codebooks[m, codes[i, m]]`` (``l``: its list in
         ``ivf_lists()``, ``c_l`` its centroid there), and ``beta[i]`` is ``|rhat|^2 + 2 <c_l, rhat>`` of that decoded residual
         as the device computed it in fp32."""
-        ent = self._ivf_current()
-        if ent.pq is None:
-            raise ValueError("the loaded index has no PQ codes (factory_string is not 'IVF<nlist>,PQ<M>')")
-        pq = ent.pq
-        scale = np.float32(2.0) ** -pq.exp  # exact: the stored scale is a power of two
-        rows = ent.ivf.rows.cpu().numpy().view(np.uint32).astype(np.int64)
-        codes = np.empty((ent.n, pq.M), np.uint8)
-        codes[rows] = pq.codes[:, :pq.M].cpu().numpy()
-        beta = np.empty(ent.n, np.float32)
-        beta[rows] = pq.beta.cpu().numpy() * (scale * scale)
-        return pq.codebooks.cpu().numpy() * scale, codes, beta
+        return self._export_codes("PQ", "PQ<M>")
 
-    def _check_pq_width(self, d: int) -> None:
-        """faiss asserts d % M == 0 for a product quantizer: rows of another width cannot back an IVF-PQ store."""
-        if self._pq_m is not None and d % self._pq_m != 0:
-            raise ValueError(f"factory_string={self.factory_string!r} needs a dimension divisible by M={self._pq_m}, got d={d}")
+    def _export_codes(self, kind: str, spelled: str):
+        ent = self._ivf_current()
+        if self._mode.kind != kind:
+            raise ValueError(f"the loaded index has no {kind} codes (factory_string is not 'IVF<nlist>,{spelled}')")
+        return self._mode.export(ent)
+
+    def _check_width(self, d: int) -> None:
+        if self._mode is not None:
+            self._mode.check_width(d, self.factory_string)
 
     @staticmethod
     def _fp32_path(ent, q) -> bool:

@@ -51,8 +51,8 @@ def reference(vs, xq, k, nprobe=None):
 def test_factory_string_parsing():
     for fs, M in (("IVF16,PQ8", 8), ("IVF16,PQ8x8", 8), ("IVF4096,PQ64", 64), ("IVF1,PQ1", 1), ("IVF16,PQ96x8", 96)):
         vs = make_vs(factory_string=fs, nprobe=4)
-        assert vs._nlist == int(fs[3:fs.index(",")]) and vs._pq_m == M and not vs._sq8
-    assert make_vs(factory_string="IVF16,SQ8")._pq_m is None
+        assert vs._nlist == int(fs[3:fs.index(",")]) and vs._mode.M == M and vs._mode.kind != "SQ8"
+    assert make_vs(factory_string="IVF16,SQ8")._mode.M is None
     for bad in ("IVF16,PQ16x4", "IVF16,PQ16x4fs", "IVF16,PQ8x8fs", "IVF16,PQ0", "IVF16,PQ0x8", "IVF16,PQ", "IVF0,PQ8",
                 "IVF16,PQ8x", "IVF16,PQ8x16", "IVF16,pq8", "IVF16,PQ8 ", "IVF16,PQ8,RFlat", "OPQ8,IVF16,PQ8", "PQ8"):
         with pytest.raises(ValueError, match="PQ<M>"):

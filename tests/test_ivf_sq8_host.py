@@ -45,8 +45,8 @@ def reference(vs, xq, k, nprobe=None):
 # ---- factory strings ---------------------------------------------------------------------------------------------------
 def test_factory_string_parsing():
     vs = make_vs(factory_string="IVF16,SQ8", nprobe=4)
-    assert vs._nlist == 16 and vs._sq8 and vs.nprobe == 4
-    assert not make_vs(factory_string="IVF16,Flat")._sq8
+    assert vs._nlist == 16 and vs._mode.kind == "SQ8" and vs.nprobe == 4
+    assert make_vs(factory_string="IVF16,Flat")._mode.kind != "SQ8"
     for bad in ("SQ8", "IVF16,SQ4", "IVF16,SQ8 ", "IVF0,SQ8", "IVF,SQ8", "IVF16,sq8", "IVF16,SQ8,Flat", "IVF16,PQ8", "HNSW32"):
         with pytest.raises(ValueError, match="'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8'"):
             make_vs(factory_string=bad)

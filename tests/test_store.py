@@ -246,3 +246,55 @@ def test_same_shape_rewrite_of_a_few_middle_rows_voids_the_row_store(tmp_path):
     vs.load_index(d)
     assert np.array_equal(vs.get_vectors_from_index(d, rows), b[rows])
     assert vs(b[rows[2]:rows[2] + 1].astype(np.float32), 1).indices[0, 0] == rows[2]
+
+
+# ---- the IVF sidecars (ivf.npz, ivf_sq8.npz, ivf_pq.npz) ----------------------------------------------------------------
+def _sidecar_cases(index_dir, n=6, d=4, M=2):
+    """Per sidecar: (file name, the write call, the read call that accepts what it wrote), over an empty directory."""
+    rng = np.random.default_rng(5)
+    lists = (rng.standard_normal((2, d)).astype(np.float32), np.array([0, 4, n], np.int64), np.arange(n, dtype=np.uint32))
+    dig = store.ivf_digest(*lists)
+    vmin, vdiff = np.zeros(d, np.float32), np.ones(d, np.float32)
+    codes8, rnorm = rng.integers(0, 256, (n, d)).astype(np.uint8), np.ones(n, np.float32)
+    books, codes_pq = rng.standard_normal((M, 3, d // M)).astype(np.float32), rng.integers(0, 3, (n, M)).astype(np.uint8)
+    split = _capi.PACK_SPLIT
+    return [
+        (store.IVF_SIDECAR, lambda: store.write_ivf(index_dir, 2, 0, split, *lists),
+         lambda: store.read_ivf(index_dir, 2, 0, split, d, n)),
+        (store.IVF_SQ8_SIDECAR, lambda: store.write_ivf_sq8(index_dir, 2, 0, split, 3, vmin, vdiff, codes8, rnorm, dig),
+         lambda: store.read_ivf_sq8(index_dir, 2, 0, split, 3, d, n, dig)),
+        (store.IVF_PQ_SIDECAR, lambda: store.write_ivf_pq(index_dir, 2, 0, split, 3, books, codes_pq, rnorm, dig),
+         lambda: store.read_ivf_pq(index_dir, 2, 0, split, 3, d, M, n, dig)),
+    ]
+
+
+def _flat_dir(tmp_path):
+    d = str(tmp_path / "i")
+    HipVS(backend=OracleBackend()).index(None, synth.corpus(6, 4, seed=3), d)
+    return d
+
+
+def test_sidecar_header_that_is_not_an_object_is_not_valid(tmp_path):
+    d = _flat_dir(tmp_path)
+    for name, write, read in _sidecar_cases(d):
+        write()
+        assert read() is not None
+        with np.load(os.path.join(d, name), allow_pickle=False) as z:
+            arrays = {key: np.array(z[key]) for key in z.files}
+        for header in ("[]", "3", '"version"', "null"):  # valid JSON, no object
+            np.savez(os.path.join(d, name), **dict(arrays, header=np.array(header)))
+            assert read() is None, (name, header)
+
+
+def test_failed_sidecar_write_leaves_no_temporary_file(tmp_path, monkeypatch):
+    d = _flat_dir(tmp_path)
+    before = sorted(os.listdir(d))
+
+    def refuse(src, dst):
+        raise OSError("no rename today")
+
+    monkeypatch.setattr(os, "replace", refuse)
+    for name, write, _ in _sidecar_cases(d):
+        with pytest.raises(OSError, match="no rename today"):
+            write()
+        assert sorted(os.listdir(d)) == before, name  # neither the sidecar nor its *.npz.tmp

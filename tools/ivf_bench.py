@@ -1,15 +1,23 @@
-"""IVF-Flat against the exact path on one MI355X: 1 M x 768 fp16 rows, nlist 4 096, nprobe in {8, 32, 128}.
+"""The IVF modes (--modes flat sq8 pq) against the exact path on one MI355X: 1 M rows, nlist 4 096, nprobe in {8, 32, 128},
+k = 10, per --workloads d:storage pair (default: d = 768 and d = 3072, text-embedding-3-large's width, stored as hi|lo).
 
-Per nprobe and for 1 and 10 000 queries (k = 10):
-  * wall ms per call: host clock around a call that ends with the results on the host (so it includes the copies and the
-    launch gaps), median of the timed calls;
-  * kernel ms per call: lvs_timing_read_calls (HIP events around the dominant kernel: lvs_ivf_scan_kernel for IVF, the
-    flat path's search kernel for exact);
-  * the scan kernel's HBM share (1 query: bytes of the probed lists' rows over 8 TB/s, over kernel time) and MFMA share
-    (10 000 queries: 2 x sum over (query, probed row) x d over 2.5 PFLOP/s, over kernel time);
+Per workload, column (exact, then every chosen mode whose list scan takes the width) and nprobe, for 1 and 10 000 queries:
+  * wall ms per call: host clock around a call that ends with the results on the host, median of the timed calls;
+  * kernel ms per call: lvs_timing_read_calls (HIP events around the dominant kernel: for IVF-PQ the table kernel and
+    lvs_ivf_pq_scan_kernel together, for the others their list scan or the flat path's search kernel; the split between the
+    two PQ kernels comes from a rocprofv3 --kernel-trace --stats run of this tool);
+  * hbm_share: bytes of the probed rows as the scan reads them (PQ: M code bytes per row; SQ8: d; IVF-Flat: 2 or 4 bytes
+    per dimension) over 8 TB/s, over kernel time - 1 query: every probed row once; 10 000 queries: the union of the probed
+    lists once (a lower bound);
   * recall@10 against the exact search on benchdata's configs[2] rows (uniform: the worst case for IVF) and on a seeded
     clustered set (benchdata.blobs).
-Prints one JSON document (and writes it to --out)."""
+Prints one JSON document (and writes it to --out).
+
+The committed profiles are records of these runs (the first two of earlier generations of this tool, whose JSON named some
+keys differently):
+  profiles/ivf_bench.json      python tools/ivf_bench.py --modes flat --workloads 768:fp16 --reps1 50
+  profiles/ivf_sq8_bench.json  python tools/ivf_bench.py --modes flat sq8 --workloads 768:fp16 768:fp32 1536:fp32
+  profiles/ivf_pq_bench.json   python tools/ivf_bench.py"""
 from __future__ import annotations
 
 import argparse
@@ -24,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BPS = 8e12
-MFMA_FLOPS = 2.5e15
+MODES = ("flat", "sq8", "pq")
 
 
 def timed(vs, q, k, reps, warmup, **kw):
@@ -51,20 +59,96 @@ def probed_rows(vs, q, nprobe):
     return int(sizes[probe].sum()), int(sizes[np.unique(probe)].sum())
 
 
-def recall(ivf, exact, q, k, nprobe):
-    a = ivf(q, k, nprobe=nprobe).indices
-    b = exact(q, k).indices
-    return float(np.mean([len(set(x) & set(y)) / k for x, y in zip(a, b)]))
+def columns(a, be, d, k, mode):
+    """{the column's key in the JSON: the second half of its factory string} of the chosen modes whose list scan takes the shape."""
+    cols = {}
+    if "flat" in a.modes and be.ivf_fits(d, k, mode):
+        cols["ivf_flat"] = "Flat"
+    if "sq8" in a.modes and be.ivf_sq8_fits(d, k, mode):
+        cols["sq8"] = "SQ8"
+    if "pq" in a.modes and be.ivf_pq_fits(d, a.M, k, mode):
+        cols["pq"] = f"PQ{a.M}"
+    return cols
+
+
+def recall(a, b):
+    return float(np.mean([len(set(x) & set(y)) / len(x) for x, y in zip(a, b)]))
+
+
+def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
+    from lotus_amd import _capi
+
+    k = 10
+    mode = _capi.PACK_F16 if storage == "fp16" else _capi.PACK_SPLIT
+    dtype = np.float16 if storage == "fp16" else np.float32
+    res = {"n": a.n, "d": d, "storage": storage, "nlist": a.nlist, "k": k}
+    xb = benchdata.corpus(benchdata.CFG_SEARCH, a.n, d, dtype=dtype)
+    xq, _ = benchdata.queries(benchdata.CFG_SEARCH, xb, a.big, dtype=dtype)
+    exact = HipVS(storage=storage, device="cuda:0")
+    exact.index(None, xb, "bench-exact", persist=False)
+    kinds = columns(a, exact.backend, d, k, mode)
+    if "pq" in kinds:
+        res["M"] = a.M
+    stores = {}
+    for name, kind in kinds.items():
+        vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        vs.index(None, xb, f"bench-{name}", persist=False)
+        torch.cuda.synchronize()
+        res[f"{name}_build_s"] = time.perf_counter() - t0
+        stores[name] = vs
+    q1, qb = xq[:1], xq[:a.big]
+    res["exact"] = {"q1": timed(exact, q1, k, a.reps1, 5), f"q{a.big}": timed(exact, qb, k, a.repsbig, 1)}
+    ref = exact(xq[:a.recall_queries], k).indices
+    row_bytes = {"pq": a.M, "sq8": d, "ivf_flat": d * (2 if storage == "fp16" else 4)}
+    for name, vs in stores.items():
+        col = {}
+        for nprobe in a.nprobe:
+            r = {"q1": timed(vs, q1, k, a.reps1, 5, nprobe=nprobe), f"q{a.big}": timed(vs, qb, k, a.repsbig, 1, nprobe=nprobe)}
+            rows1, _ = probed_rows(vs, q1, nprobe)
+            pairs, union = probed_rows(vs, qb, nprobe)
+            r["q1"]["probed_rows"] = rows1
+            r["q1"]["hbm_share"] = rows1 * row_bytes[name] / HBM_BPS / (r["q1"]["kernel_ms"] * 1e-3)
+            r[f"q{a.big}"]["query_row_pairs"] = pairs
+            r[f"q{a.big}"]["union_rows"] = union
+            r[f"q{a.big}"]["hbm_share"] = union * row_bytes[name] / HBM_BPS / (r[f"q{a.big}"]["kernel_ms"] * 1e-3)
+            r["recall10_uniform"] = recall(vs(xq[:a.recall_queries], k, nprobe=nprobe).indices, ref)
+            r["speedup_q1_kernel_vs_exact"] = res["exact"]["q1"]["kernel_ms"] / r["q1"]["kernel_ms"]
+            r[f"speedup_q{a.big}_kernel_vs_exact"] = res["exact"][f"q{a.big}"]["kernel_ms"] / r[f"q{a.big}"]["kernel_ms"]
+            col[str(nprobe)] = r
+        res[name] = col
+    del exact, stores
+    torch.cuda.empty_cache()
+    if not a.skip_clustered:
+        xc, _ = benchdata.blobs(benchdata.CFG_KMEANS, a.n, d, a.nlist, dtype=dtype)
+        qc, _ = benchdata.queries(benchdata.CFG_KMEANS, xc, a.recall_queries, dtype=dtype)
+        exact = HipVS(storage=storage, device="cuda:0")
+        exact.index(None, xc, "bench-exact-c", persist=False)
+        ref = exact(qc, k).indices
+        del exact
+        for name, kind in kinds.items():
+            vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}")
+            vs.index(None, xc, f"bench-{name}-c", persist=False)
+            for nprobe in a.nprobe:
+                res[name][str(nprobe)]["recall10_clustered"] = recall(vs(qc, k, nprobe=nprobe).indices, ref)
+            del vs
+        torch.cuda.empty_cache()
+    return res
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
-    ap.add_argument("--d", type=int, default=768)
     ap.add_argument("--nlist", type=int, default=4096)
     ap.add_argument("--nprobe", type=int, nargs="+", default=[8, 32, 128])
+    ap.add_argument("--modes", nargs="+", choices=MODES, default=list(MODES),
+                    help="the columns beside the exact one; a mode whose list scan refuses a workload's width is skipped there")
+    ap.add_argument("--M", type=int, default=64, help="subspaces of the pq mode")
+    ap.add_argument("--workloads", nargs="+", default=["768:fp32", "3072:fp32"],
+                    help="d:storage pairs (storage fp16 or fp32 = hi|lo)")
     ap.add_argument("--big", type=int, default=10_000)
-    ap.add_argument("--reps1", type=int, default=50)
+    ap.add_argument("--reps1", type=int, default=30)
     ap.add_argument("--repsbig", type=int, default=5)
     ap.add_argument("--recall-queries", type=int, default=1000)
     ap.add_argument("--skip-clustered", action="store_true")
@@ -78,51 +162,11 @@ def main() -> None:
 
     if not torch.cuda.is_available():
         raise SystemExit("ivf_bench needs a GPU")
-    k = 10
-    res = {"n": a.n, "d": a.d, "nlist": a.nlist, "k": k, "storage": "fp16", "device": torch.cuda.get_device_name(0)}
-    xb = benchdata.corpus(benchdata.CFG_SEARCH, a.n, a.d)
-    xq, _ = benchdata.queries(benchdata.CFG_SEARCH, xb, a.big)
-    exact = HipVS(storage="fp16", device="cuda:0")
-    exact.index(None, xb, "bench-exact", persist=False)
-    ivf = HipVS(storage="fp16", device="cuda:0", factory_string=f"IVF{a.nlist},Flat")
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    ivf.index(None, xb, "bench-ivf", persist=False)
-    torch.cuda.synchronize()
-    res["build_s"] = time.perf_counter() - t0
-    _, off, _ = ivf.ivf_lists()
-    sizes = np.diff(off)
-    res["list_rows"] = {"min": int(sizes.min()), "median": float(np.median(sizes)), "max": int(sizes.max()),
-                        "empty": int((sizes == 0).sum())}
-    q1, qb = xq[:1], xq[:a.big]
-    res["exact"] = {"q1": timed(exact, q1, k, a.reps1, 5), f"q{a.big}": timed(exact, qb, k, a.repsbig, 1)}
-    row_bytes = a.d * 2
-    res["ivf"] = {}
-    for nprobe in a.nprobe:
-        r = {"q1": timed(ivf, q1, k, a.reps1, 5, nprobe=nprobe), f"q{a.big}": timed(ivf, qb, k, a.repsbig, 1, nprobe=nprobe)}
-        rows1, _ = probed_rows(ivf, q1, nprobe)
-        pairs, union = probed_rows(ivf, qb, nprobe)
-        r["q1"]["probed_rows"] = rows1
-        r["q1"]["hbm_share"] = rows1 * row_bytes / HBM_BPS / (r["q1"]["kernel_ms"] * 1e-3)
-        r[f"q{a.big}"]["query_row_pairs"] = pairs
-        r[f"q{a.big}"]["union_rows"] = union
-        r[f"q{a.big}"]["mfma_share"] = 2.0 * pairs * a.d / MFMA_FLOPS / (r[f"q{a.big}"]["kernel_ms"] * 1e-3)
-        r["recall10_uniform"] = recall(ivf, exact, xq[:a.recall_queries], k, nprobe)
-        r["speedup_q1_kernel"] = res["exact"]["q1"]["kernel_ms"] / r["q1"]["kernel_ms"]
-        r[f"speedup_q{a.big}_kernel"] = res["exact"][f"q{a.big}"]["kernel_ms"] / r[f"q{a.big}"]["kernel_ms"]
-        res["ivf"][str(nprobe)] = r
-    del exact, ivf
-    torch.cuda.empty_cache()
-    if not a.skip_clustered:
-        xc, _ = benchdata.blobs(benchdata.CFG_KMEANS, a.n, a.d, a.nlist)
-        qc, _ = benchdata.queries(benchdata.CFG_KMEANS, xc, a.recall_queries)
-        exact = HipVS(storage="fp16", device="cuda:0")
-        exact.index(None, xc, "bench-exact-c", persist=False)
-        ivf = HipVS(storage="fp16", device="cuda:0", factory_string=f"IVF{a.nlist},Flat")
-        ivf.index(None, xc, "bench-ivf-c", persist=False)
-        for nprobe in a.nprobe:
-            res["ivf"][str(nprobe)]["recall10_clustered"] = recall(ivf, exact, qc, k, nprobe)
-    text = json.dumps(res, indent=1)
+    out = {"device": torch.cuda.get_device_name(0), "workloads": []}
+    for wl in a.workloads:
+        d, storage = wl.split(":")
+        out["workloads"].append(run_workload(int(d), storage, a, HipVS, benchdata, torch))
+    text = json.dumps(out, indent=1)
     print(text)
     if a.out:
         with open(a.out, "w") as fp:
