@@ -24,6 +24,20 @@
 // library: keys bit-identical to the list kernel's.  Exactness of the deferred insertion: a score is dropped only when it is
 // below a threshold that is the k-th best key's score of a list holding real rows of the searched set (own list or another
 // workgroup's through gtau) - never above the final k-th best - and everything appended is inserted before the lists are written.
+//
+// The seam between two 32-row blocks, and who waits for what.  The fragment reads, the MFMAs and the staging loads are asm: the
+// compiler's waitcnt pass neither counts them nor reads the s_waitcnt strings that do - inside the unit loop that is the design
+// (lgkmcnt(AD - 1): three reads stay in flight, also across a block's end).  The visit and the drains are plain C++: THEIR LDS
+// reads and writes are counted by the compiler, and their temporaries share registers with acc[].  Closed with a wait in an asm
+// string, such a path left the pass believing that LDS results were still pending into those registers at the loop's back edge,
+// and it put a full `s_waitcnt lgkmcnt(0)` in front of every block's first MFMA - behind the fragment read just issued, on every
+// block, visit or not.  So every path that issues compiler-visible LDS operations (the end of `drain`, hence the overflow drain
+// in `append` and the final drain; the visit in the epilogue) ends in rj_wait_lds(), the builtin the pass understands, and the
+// prologue's vmcnt(0) is repeated as a builtin for the compiler's own loads of bv[] (without it the RANGE instantiations counted
+// them down INSIDE the loop: vmcnt(35) ... vmcnt(0) per block, emptying the staging queue).  On the path without a candidate
+// the block loop now holds no compiler-inserted wait at all (inner product; squared L2 keeps the two that its own reads of
+// the rows' |y|^2 need).  The filter is ONE compare-and-branch round trip for both query blocks; which block holds the candidate
+// is decided behind it.  Issuing the next unit's barrier and first read AHEAD of the filter was measured and lost 0.2 %.
 #include "lvs_common.h"
 #include "lvs_kstep.h"
 #include "lvs_tile.h"
@@ -98,6 +112,14 @@ __device__ inline float rj_max16(const f32x16& v) {
     const float a = rj_max3(v[0], v[1], v[2]), b = rj_max3(v[3], v[4], v[5]), c = rj_max3(v[6], v[7], v[8]);
     const float d = rj_max3(v[9], v[10], v[11]), e = rj_max3(v[12], v[13], v[14]);
     return rj_max3(rj_max3(a, b, c), rj_max3(d, e, v[15]), v[15]);
+}
+// lgkmcnt(0) as an instruction the compiler's waitcnt pass sees (gfx9 encoding: vmcnt 63, expcnt 7 = not waited for; lgkmcnt =
+// bits 11:8 = 0).  It closes every path that issued compiler-visible LDS operations: a wait inside an asm string is opaque to
+// that pass, which then believes results may still be pending into registers the next block overwrites (see the header).
+__device__ inline void rj_wait_lds() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    asm volatile("" ::: "memory");
 }
 constexpr int rj_piece_at(int jj, int uk, int lpw) {  // staging piece p (0 .. lpw) goes out at MFMA step p * uk / (lpw + 1) + 1
     for (int p = 0; p <= lpw; ++p)
@@ -188,6 +210,10 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
         qnv[qb] = L2 ? a.qn[qrow] : 0.f;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory", RJ_CLOBBER_AGPRS);  // (the loads into named registers are asm: nobody else waits for them)
+    // ... and once more as an instruction the waitcnt pass sees (vmcnt 0; expcnt 7, lgkmcnt 15 = not waited for): the fragments in
+    // bv[] are the compiler's own loads, and without it it counts them down in front of their first uses INSIDE the block loop -
+    // vmcnt(35) ... vmcnt(0) per block in the RANGE instantiations, the last of which empties the staging queue
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     if constexpr (!RANGE)
         for (int i = lane; i < 64 * KCAP; i += 64) mylists[i] = 0;
 
@@ -348,7 +374,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
                 if (lane < 32 && !(DBG & 512)) atomicMax(&a.gtau[qidx_of(qb)], best[qb]);
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the unit loop counts its fragment reads from zero
+        rj_wait_lds();  // the unit loop counts its fragment reads from zero
         if (DBG & 32) d_drain += __builtin_amdgcn_s_memtime() - t_d0;
     };
     // what the other workgroups have found meanwhile (a lower bound of the k-th best over ALL rows), as it rode in with the block
@@ -424,9 +450,11 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
         }
         if constexpr (RANGE) {
             // strict ">" as the reference compares (sem_dedup.py:46); a self-join keeps the pairs with row id > query row
+            const float mx[2] = {rj_max16(acc[0]), rj_max16(acc[1])};
+            if (__any(mx[0] > tauf[0] || mx[1] > tauf[1]))  // ONE round trip on the common path; per query block only behind it
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb) {
-                if (!__any(rj_max16(acc[qb]) > tauf[qb])) continue;
+                if (!__any(mx[qb] > tauf[qb])) continue;
                 const long long qg = qidx_of(qb);
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
@@ -450,23 +478,23 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
                 }
             }
         } else if constexpr (!(DBG & 4)) {
-            bool wrote = false;
             const unsigned long long t_v0 = (DBG & 32) ? __builtin_amdgcn_s_memtime() : 0;
+            // ONE "does any lane of either query block hold a candidate?" round trip on the common path; which block - the
+            // same compares against the same thresholds, block 1's after block 0's visit as before - only behind it
+            const float mx[2] = {rj_max16(acc[0]), rj_max16(acc[1])};
+            if (__any(mx[0] >= tauf[0] || mx[1] >= tauf[1])) {
 #pragma unroll
-            for (int qb = 0; qb < 2; ++qb)
-                if (__any(rj_max16(acc[qb]) >= tauf[qb])) {
-                    if constexpr (!(DBG & 64)) {
-                        append(acc[qb], qb, row0);
-                        wrote = true;
-                    } else {
-                        count += 1;
+                for (int qb = 0; qb < 2; ++qb)
+                    if (__any(mx[qb] >= tauf[qb])) {
+                        if constexpr (!(DBG & 64)) append(acc[qb], qb, row0);
+                        else count += 1;
                     }
+                // (LDS writes of its own only behind a visit: the unit loop counts its fragment reads from zero)
+                if constexpr (!(DBG & 64)) rj_wait_lds();
+                if (DBG & 32) {
+                    d_visit += __builtin_amdgcn_s_memtime() - t_v0;
+                    d_nvisit += 1;
                 }
-            // (LDS writes of its own only behind a visit: the unit loop counts its fragment reads from zero)
-            if (wrote) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if ((DBG & 32) && wrote) {
-                d_visit += __builtin_amdgcn_s_memtime() - t_v0;
-                d_nvisit += 1;
             }
         } else {
             if (__any(rj_max16(acc[0]) >= 3.0e38f) || __any(rj_max16(acc[1]) >= 3.0e38f)) count = 1;
