@@ -368,11 +368,6 @@ __global__ __launch_bounds__(256) void nearest3_select_kernel(const u64* __restr
 }
 
 typedef _Float16 as_half8 __attribute__((ext_vector_type(8)));
-__device__ inline float as_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 // one wave per listed query: exact (hi + lo of both operands, float32) scores of the query against the rows named by
 // keys1[q] and keys2[q]; the better key (score, then lower id) replaces keys1[q].  Same arithmetic as rescore_keys_kernel.
 template <int QSPLIT, int BSPLIT>
@@ -410,8 +405,8 @@ __global__ __launch_bounds__(256) void resolve_pairs_kernel(const _Float16* __re
             sb += x * ((float)bh[t] + (BSPLIT ? (float)bl[t] : 0.f));
         }
     }
-    sa = as_wave_sum(sa);
-    sb = as_wave_sum(sb);
+    sa = lvs_wave_sum(sa);
+    sb = lvs_wave_sum(sb);
     if (lane == 0) {
         float fa = sa, fb = sb;
         if (metric == LVS_METRIC_L2) {
@@ -510,14 +505,8 @@ extern "C" int32_t lvs_nearest3(const void* xb, int32_t xb_pack, int64_t nb, con
     a.tiles_per_slab = p.tps;
     a.nslab = p.nslab;
     a.gq = p.gq;
-    static LvsPerDeviceOnce attr;
-    int dev = 0;
-    LVS_HIP_CHECK(hipGetDevice(&dev));
-    if (!attr.done(dev, (size_t)A_LDS)) {
-        LVS_HIP_CHECK(hipFuncSetAttribute((const void*)lvs_assign_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-        LVS_HIP_CHECK(hipFuncSetAttribute((const void*)lvs_assign_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-        attr.set(dev, (size_t)A_LDS);
-    }
+    LVS_HIP_CHECK(lvs_arm_lds<lvs_assign_kernel<false>>(A_LDS));
+    LVS_HIP_CHECK(lvs_arm_lds<lvs_assign_kernel<true>>(A_LDS));
     {
         LvsKernelTimer timer(st);
         const dim3 grid((unsigned)lvs_tile_grid_blocks(p.nct, p.nslab, p.gq, 0));

@@ -154,12 +154,6 @@ extern "C" int32_t lvs_packed_ld(int32_t d, int32_t pack_mode) {
 
 namespace {
 
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // one wave per row, one element per lane and step: the fallback for d % 8 != 0 (rows not 16-byte aligned)
 // flags (nullable device word): LVS_PACK_FLAG_NONFINITE when an input value is inf / NaN, LVS_PACK_FLAG_RANGE when a finite
 // value (after the optional normalisation) lies outside fp16's range (|x| > 65504 would be stored as inf)
@@ -190,7 +184,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const SrcT* __restrict__
             float x = (float)s[j];
             ss += x * x;
         }
-        ss = wave_sum(ss);
+        ss = lvs_wave_sum(ss);
         scale = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
     }
     float nn = 0.f;
@@ -209,7 +203,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const SrcT* __restrict__
         nn += stored * stored;
     }
     if (norms) {
-        nn = wave_sum(nn);
+        nn = lvs_wave_sum(nn);
         if (lane == 0) norms[row] = nn;
     }
     pack_report(bad, flags);
@@ -251,7 +245,7 @@ __global__ __launch_bounds__(256) void pack_rows_vec_kernel(const SrcT* __restri
 #pragma unroll
             for (int t = 0; t < 8; ++t) ss += v[t] * v[t];
         }
-        ss = wave_sum(ss);
+        ss = lvs_wave_sum(ss);
         scale = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
     }
     float nn = 0.f;
@@ -281,7 +275,7 @@ __global__ __launch_bounds__(256) void pack_rows_vec_kernel(const SrcT* __restri
         if (SPLIT) *(pk_half8*)(o + dpad + j) = lo;
     }
     if (norms) {
-        nn = wave_sum(nn);
+        nn = lvs_wave_sum(nn);
         if (lane == 0) norms[row] = nn;
     }
     pack_report(bad, flags);
@@ -471,7 +465,7 @@ __global__ __launch_bounds__(256) void rescore_keys_kernel(const _Float16* __res
             acc += a * b;
         }
     }
-    acc = wave_sum(acc);
+    acc = lvs_wave_sum(acc);
     if (lane == 0) {
         float better = acc;
         if (metric == LVS_METRIC_L2) better = -fmaxf((qn[q] + bn[row]) - 2.0f * acc, 0.f);

@@ -12,7 +12,7 @@
 //   * each wave takes every fourth 32-row block of the list: v_mfma_f32_32x32x16_f16 on 32 rows x 32 queries per K step,
 //     hi|lo operands as the K segments hi.hi + hi.lo + lo.hi (fp32-accurate, like the flat path); the fragments of the next
 //     K step are loaded while the current ones are multiplied;
-//   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_tile.h) into per-query lists in LDS (one
+//   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_common.h) into per-query lists in LDS (one
 //     lock per query: the four waves share the tile).  Keys carry the GLOBAL row number, so ties between rows of different
 //     lists keep the oracle's total order when the per-probe lists are merged (lvs_merge_keys);
 //   * the work item writes its k keys per pair to the part of the pair's probe rank: parts [nprobe][nq][k].
@@ -46,14 +46,7 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
     const uint32_t p0 = a.pair_offs[l] + (wi - a.tile_offs[l]) * TQ;
     const uint32_t pend = a.pair_offs[l + 1];
     const int npair = (int)(pend - p0 < (uint32_t)TQ ? pend - p0 : (uint32_t)TQ);  // >= 1
-    if (tid < TQ) {
-        const uint32_t pr = a.pairs[p0 + (tid < npair ? tid : 0)];  // empty slots repeat the first pair (never written)
-        slot_q[tid] = (int)(pr / (uint32_t)a.nprobe);
-        slot_p[tid] = (int)(pr % (uint32_t)a.nprobe);
-    }
-    for (int i = tid; i < TQ * KCAP; i += LVS_IVF_WAVES * 64) lists[i] = 0;
-    for (int i = tid; i < TQ; i += LVS_IVF_WAVES * 64) locks[i] = 0;
-    __syncthreads();
+    lvs_ivf_tile_begin<TQ, LVS_IVF_WAVES * 64>(a.pairs, p0, npair, a.nprobe, tid, lists, KCAP, locks, slot_q, slot_p);
     // ---- queries -> LDS as B fragments: fragment f, lane v = pair slot (v & 31), halfs (v >> 5) * 8 .. + 8
     const _Float16* xq = (const _Float16*)a.xq;
     for (int idx = tid; idx < a.nbfrag * 64; idx += LVS_IVF_WAVES * 64) {
@@ -135,11 +128,7 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
             lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
     }
-    __syncthreads();
-    for (int i = tid; i < npair * k; i += LVS_IVF_WAVES * 64) {
-        const int s = i / k, j = i - s * k;
-        a.out[((long long)slot_p[s] * a.nq + slot_q[s]) * k + j] = lists[s * KCAP + j];
-    }
+    lvs_ivf_write_parts<LVS_IVF_WAVES * 64>(lists, KCAP, slot_q, slot_p, npair, k, a.nq, tid, a.out);
 }
 
 // tile_offs[l] = first work item of list l (exclusive scan of ceil(pairs / 32)), tile_offs[nlist] = work items;
@@ -199,18 +188,8 @@ __global__ __launch_bounds__(256) void lvs_ivf_offsets_kernel(const uint32_t* __
 
 template <int U>
 hipError_t ivf_scan_launch_u(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream) {
-    static LvsPerDeviceOnce attr;
-    const size_t lds = lvs_ivf_lds_bytes(a.nbfrag, a.kcap);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_ivf_scan_kernel<U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, lds);
-    }
-    hipLaunchKernelGGL(lvs_ivf_scan_kernel<U>, dim3((unsigned)max_items), dim3(LVS_IVF_WAVES * 64), lds, stream, a);
-    return hipGetLastError();
+    return lvs_launch_lds<lvs_ivf_scan_kernel<U>>(dim3((unsigned)max_items), dim3(LVS_IVF_WAVES * 64),
+                                                  lvs_ivf_lds_bytes(a.nbfrag, a.kcap), stream, a);
 }
 
 }  // namespace

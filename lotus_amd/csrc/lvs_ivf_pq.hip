@@ -16,7 +16,7 @@
 // lvs_ivf_pq_scan_kernel is query-major: a workgroup takes one query and a range of its probed lists, stages the query's
 // fp32 table (M KB) in LDS, and every lane scores one row of the concatenated lists from its M code bytes (16-byte loads,
 // then M ds_read_b32 lookups summed in the order m = 0 .. M-1).  Hits go through the wave-cooperative sorted insertion
-// (the text of lvs_list_insert, lvs_tile.h) into the workgroup's one list in LDS; keys carry the GLOBAL row number; parts [nranges][nq][k] are
+// (the text of lvs_list_insert, lvs_common.h) into the workgroup's one list in LDS; keys carry the GLOBAL row number; parts [nranges][nq][k] are
 // merged by lvs_merge_keys.  LDS: M KB of table + the list: M <= 159 (lvs_ivf_pq_lds_bytes), whatever d.
 #include "lvs_common.h"
 #include "lvs_tile.h"
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
             pending = pending && ord >= kth;
             pm = __ballot(pending);
         }
-        // the text of lvs_list_insert (lvs_tile.h) for one list and one lock: calling it here changes this kernel's instructions
+        // the text of lvs_list_insert (lvs_common.h) for one list and one lock: calling it here changes this kernel's instructions
         while (pm) {
             const int srcl = __ffsll((long long)pm) - 1;
             pm &= pm - 1;
@@ -315,17 +315,7 @@ hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream) {
         a.prange > LVS_PQ_MAXRANGE || a.nprobe < 1 || a.nq > 65535 || lvs_ivf_pq_lds_bytes(a.M, a.kcap) > 160 * 1024)
         return hipErrorInvalidValue;
     if (a.nq <= 0) return hipSuccess;
-    static LvsPerDeviceOnce attr;
-    const size_t lds = lvs_ivf_pq_lds_bytes(a.M, a.kcap);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_ivf_pq_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, lds);
-    }
     const int nranges = (a.nprobe + a.prange - 1) / a.prange;
-    hipLaunchKernelGGL(lvs_ivf_pq_scan_kernel, dim3((unsigned)nranges, (unsigned)a.nq), dim3(PQ_THREADS), lds, stream, a);
-    return hipGetLastError();
+    return lvs_launch_lds<lvs_ivf_pq_scan_kernel>(dim3((unsigned)nranges, (unsigned)a.nq), dim3(PQ_THREADS),
+                                                  lvs_ivf_pq_lds_bytes(a.M, a.kcap), stream, a);
 }

@@ -22,7 +22,7 @@
 //     64 kb + 16 g + 8 s + t, and the B fragments are staged with the same permutation.  A code byte becomes an exact fp16
 //     by v_perm_b32 (0x64XX = 1024 + code) and v_pk_add_f16 (-1024);
 //   * acc = codes x w_hi + codes x w_lo (fp32 accumulation of exact products: fp32-accurate);
-//   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_tile.h) into per-pair lists in LDS, keys carry
+//   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_common.h) into per-pair lists in LDS, keys carry
 //     the GLOBAL row number, parts [nprobe][nq][k] are merged by lvs_merge_keys.
 // LDS: 2 x (ldc / 32) fragments of 1 KB + 16 lists of kcap keys: ldc <= 2368 (d = 1536: 96 KB + 8 KB); wider rows are not
 // served (lvs_ivf_sq8_fits).
@@ -123,14 +123,7 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
     const uint32_t pend = a.pair_offs[l + 1];
     if (p0 >= pend) return;
     const int npair = (int)(pend - p0 < (uint32_t)SQ8_TQ ? pend - p0 : (uint32_t)SQ8_TQ);  // >= 1
-    if (tid < SQ8_TQ) {
-        const uint32_t pr = a.pairs[p0 + (tid < npair ? tid : 0)];  // empty slots repeat the first pair (never written)
-        slot_q[tid] = (int)(pr / (uint32_t)a.nprobe);
-        slot_p[tid] = (int)(pr % (uint32_t)a.nprobe);
-    }
-    for (int i = tid; i < SQ8_TQ * KCAP; i += SQ8_THREADS) lists[i] = 0;
-    for (int i = tid; i < SQ8_TQ; i += SQ8_THREADS) locks[i] = 0;
-    __syncthreads();
+    lvs_ivf_tile_begin<SQ8_TQ, SQ8_THREADS>(a.pairs, p0, npair, a.nprobe, tid, lists, KCAP, locks, slot_q, slot_p);
 
     const bool l2 = a.metric == LVS_METRIC_L2;
     const int d = a.d, ldc = a.ldc;
@@ -265,11 +258,7 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
             lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
     }
-    __syncthreads();
-    for (int i = tid; i < npair * k; i += SQ8_THREADS) {
-        const int s = i / k, j = i - s * k;
-        a.out[((long long)slot_p[s] * a.nq + slot_q[s]) * k + j] = lists[s * KCAP + j];
-    }
+    lvs_ivf_write_parts<SQ8_THREADS>(lists, KCAP, slot_q, slot_p, npair, k, a.nq, tid, a.out);
 }
 
 // one wave per list position: residual against the list's centroid, codes, |rhat|^2
@@ -315,18 +304,8 @@ __global__ __launch_bounds__(256) void lvs_ivf_sq8_encode_kernel(const _Float16*
 
 template <int U>
 hipError_t sq8_scan_launch_u(const LvsIvfSq8Args& a, int64_t max_items, hipStream_t stream) {
-    static LvsPerDeviceOnce attr;
-    const size_t lds = lvs_ivf_sq8_lds_bytes(a.ldc, a.kcap);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_ivf_sq8_scan_kernel<U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, lds);
-    }
-    hipLaunchKernelGGL(lvs_ivf_sq8_scan_kernel<U>, dim3((unsigned)(2 * max_items)), dim3(SQ8_THREADS), lds, stream, a);
-    return hipGetLastError();
+    return lvs_launch_lds<lvs_ivf_sq8_scan_kernel<U>>(dim3((unsigned)(2 * max_items)), dim3(SQ8_THREADS),
+                                                      lvs_ivf_sq8_lds_bytes(a.ldc, a.kcap), stream, a);
 }
 
 }  // namespace

@@ -854,6 +854,9 @@ int32_t km_bucket_rows(const KeyT* assign, int64_t n, int32_t k, int64_t id_offs
     uint32_t* rows[2] = {(uint32_t*)(w + p.off_rows_a), (uint32_t*)(w + p.off_rows_b)};
     uint32_t* offs = (uint32_t*)(w + p.off_offs);
     const uint32_t* order = nullptr;
+    // a pass may use KM_MAX_BINS counters: > 64 KB of dynamic LDS needs the attribute
+    LVS_HIP_CHECK(lvs_arm_lds<km_count_kernel<KeyT>>((size_t)KM_MAX_BINS * 4));
+    LVS_HIP_CHECK(lvs_arm_lds<km_scatter_kernel<KeyT>>((size_t)KM_MAX_BINS * 4));
     for (int ps = 0; ps < p.passes; ++ps) {
         const int nbins = p.nbins[ps];
         const size_t lds = (size_t)nbins * 4;
@@ -896,20 +899,6 @@ int32_t km_accumulate(const void* x, int64_t n, int32_t d, int32_t pack_mode, co
     }
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
-    static LvsPerDeviceOnce attr_count, attr_scatter;  // > 64 KB of dynamic LDS needs the attribute (per device)
-    {
-        int dev = 0;
-        LVS_HIP_CHECK(hipGetDevice(&dev));
-        const size_t lds = (size_t)KM_MAX_BINS * 4;
-        if (!attr_count.done(dev, lds)) {
-            LVS_HIP_CHECK(hipFuncSetAttribute((const void*)km_count_kernel<KeyT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_count.set(dev, lds);
-        }
-        if (!attr_scatter.done(dev, lds)) {
-            LVS_HIP_CHECK(hipFuncSetAttribute((const void*)km_scatter_kernel<KeyT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_scatter.set(dev, lds);
-        }
-    }
     const uint32_t *rows = nullptr, *offs = nullptr;
     const int32_t rc = km_bucket_rows<KeyT>(assign, n, k, id_offset, p, (char*)workspace, st, &rows, &offs);
     if (rc != LVS_OK) return rc;
@@ -952,18 +941,6 @@ int32_t km_bucket_positions(const KeyT* assign, int64_t n, int32_t k, void* ws, 
     if (ws_bytes < p.total) {
         lvs_set_error("workspace too small: need %lld bytes", (long long)p.total);
         return LVS_ENOMEM;
-    }
-    static LvsPerDeviceOnce attr_count, attr_scatter;
-    int dev = 0;
-    LVS_HIP_CHECK(hipGetDevice(&dev));
-    const size_t lds = (size_t)KM_MAX_BINS * 4;
-    if (!attr_count.done(dev, lds)) {
-        LVS_HIP_CHECK(hipFuncSetAttribute((const void*)km_count_kernel<KeyT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_count.set(dev, lds);
-    }
-    if (!attr_scatter.done(dev, lds)) {
-        LVS_HIP_CHECK(hipFuncSetAttribute((const void*)km_scatter_kernel<KeyT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_scatter.set(dev, lds);
     }
     return km_bucket_rows<KeyT>(assign, n, k, 0, p, (char*)ws, st, rows_out, offs_out);
 }

@@ -102,17 +102,6 @@ __device__ inline void rj_glds16(const char* base, unsigned off, unsigned lds) {
 __device__ inline void rj_glds4(const void* gsrc, void* ldst) {
     __builtin_amdgcn_global_load_lds((lvs_kstep::gbl_void_t*)gsrc, (lvs_kstep::lds_void_t*)ldst, 4, 0, 0);
 }
-__device__ inline float rj_tau_float(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
-__device__ inline float rj_max3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ inline float rj_max16(const f32x16& v) {
-    const float a = rj_max3(v[0], v[1], v[2]), b = rj_max3(v[3], v[4], v[5]), c = rj_max3(v[6], v[7], v[8]);
-    const float d = rj_max3(v[9], v[10], v[11]), e = rj_max3(v[12], v[13], v[14]);
-    return rj_max3(rj_max3(a, b, c), rj_max3(d, e, v[15]), v[15]);
-}
 // lgkmcnt(0) as an instruction the compiler's waitcnt pass sees (gfx9 encoding: vmcnt 63, expcnt 7 = not waited for; lgkmcnt =
 // bits 11:8 = 0).  It closes every path that issued compiler-visible LDS operations: a wait inside an asm string is opaque to
 // that pass, which then believes results may still be pending into registers the next block overwrites (see the header).
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
             }
         });
         pub[qb] = (valid && !RANGE) ? a.gtau[qi] : 0u;
-        tauf[qb] = valid ? (RANGE ? a.threshold : rj_tau_float(pub[qb])) : INFINITY;  // lanes without a query never hold a candidate
+        tauf[qb] = valid ? (RANGE ? a.threshold : lvs_tau(pub[qb])) : INFINITY;  // lanes without a query never hold a candidate
         qnv[qb] = L2 ? a.qn[qrow] : 0.f;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory", RJ_CLOBBER_AGPRS);  // (the loads into named registers are asm: nobody else waits for them)
@@ -369,7 +358,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             if (best[qb] > pub[qb]) {  // a full list's k-th key is published to the other workgroups (fire and forget)
-                tauf[qb] = fmaxf(tauf[qb], rj_tau_float(best[qb]));
+                tauf[qb] = fmaxf(tauf[qb], lvs_tau(best[qb]));
                 pub[qb] = best[qb];
                 if (lane < 32 && !(DBG & 512)) atomicMax(&a.gtau[qidx_of(qb)], best[qb]);
             }
@@ -381,7 +370,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
     auto take_shared = [&](int qb, uint32_t g) {
         if (g > pub[qb]) {
             pub[qb] = g;
-            tauf[qb] = fmaxf(tauf[qb], rj_tau_float(g));
+            tauf[qb] = fmaxf(tauf[qb], lvs_tau(g));
         }
     };
     // The lanes whose scores of query block qb reach their thresholds append them to the wave's buffer; lane holds query
@@ -450,7 +439,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
         }
         if constexpr (RANGE) {
             // strict ">" as the reference compares (sem_dedup.py:46); a self-join keeps the pairs with row id > query row
-            const float mx[2] = {rj_max16(acc[0]), rj_max16(acc[1])};
+            const float mx[2] = {lvs_max16(acc[0]), lvs_max16(acc[1])};
             if (__any(mx[0] > tauf[0] || mx[1] > tauf[1]))  // ONE round trip on the common path; per query block only behind it
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb) {
@@ -481,7 +470,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
             const unsigned long long t_v0 = (DBG & 32) ? __builtin_amdgcn_s_memtime() : 0;
             // ONE "does any lane of either query block hold a candidate?" round trip on the common path; which block - the
             // same compares against the same thresholds, block 1's after block 0's visit as before - only behind it
-            const float mx[2] = {rj_max16(acc[0]), rj_max16(acc[1])};
+            const float mx[2] = {lvs_max16(acc[0]), lvs_max16(acc[1])};
             if (__any(mx[0] >= tauf[0] || mx[1] >= tauf[1])) {
 #pragma unroll
                 for (int qb = 0; qb < 2; ++qb)
@@ -497,7 +486,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
                 }
             }
         } else {
-            if (__any(rj_max16(acc[0]) >= 3.0e38f) || __any(rj_max16(acc[1]) >= 3.0e38f)) count = 1;
+            if (__any(lvs_max16(acc[0]) >= 3.0e38f) || __any(lvs_max16(acc[1]) >= 3.0e38f)) count = 1;
         }
         if constexpr (!RANGE) block_end(blk);
         if (DBG & 32) d_epi += __builtin_amdgcn_s_memtime() - t_e0;
@@ -599,17 +588,7 @@ template <int NJ, int KCAP, bool L2, int DBG = 0, bool RANGE = false>
 hipError_t rj_launch_k(const LvsRqArgs& a, int grid, hipStream_t stream) {
     using G = RjGeom<NJ>;
     const size_t lds = (size_t)G::lds_bytes(G::ring(KCAP), KCAP);
-    static LvsPerDeviceOnce attr;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_rj_kernel<NJ, KCAP, L2, DBG, RANGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, lds);
-    }
-    hipLaunchKernelGGL((lvs_rj_kernel<NJ, KCAP, L2, DBG, RANGE>), dim3(grid), dim3(256), lds, stream, a);
-    return hipGetLastError();
+    return lvs_launch_lds<lvs_rj_kernel<NJ, KCAP, L2, DBG, RANGE>>(dim3(grid), dim3(256), lds, stream, a);
 }
 template <int NJ>
 hipError_t rj_launch_nj(const LvsRqArgs& a, int grid, hipStream_t stream) {

@@ -39,17 +39,6 @@ using lvs_kstep::static_for;
 
 constexpr int RQ_KMAX = LVS_RQ_KMAX;  // most list slots per query (k <= 16); calls with k <= 12 use 12 and spend the LDS on the ring
 
-__device__ inline float rq_tau_float(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
-__device__ inline float rq_max3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ inline float rq_max16(const f32x16& v) {
-    const float a = rq_max3(v[0], v[1], v[2]), b = rq_max3(v[3], v[4], v[5]), c = rq_max3(v[6], v[7], v[8]);
-    const float d = rq_max3(v[9], v[10], v[11]), e = rq_max3(v[12], v[13], v[14]);
-    return rq_max3(rq_max3(a, b, c), rq_max3(d, e, v[15]), v[15]);
-}
 // which staging piece (0 .. lpw) goes out at MFMA step jj of a unit of uk steps: piece p at step p * uk / (lpw + 1) + 1
 constexpr int rq_piece_at(int jj, int uk, int lpw) {
     for (int p = 0; p <= lpw; ++p)
@@ -135,7 +124,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void lvs_rq_kernel(const Lvs
 #pragma unroll
         for (int j = 0; j < NJ; ++j) breg[qb][j] = *(const half8*)(qp + j * 16);
         gord[qb] = (!SEED && qvalid[qb]) ? a.gtau[qidx[qb]] : 0u;
-        tauf[qb] = rq_tau_float(gord[qb]);
+        tauf[qb] = lvs_tau(gord[qb]);
         qnv[qb] = l2 ? a.qn[qrow] : 0.f;
     }
     u64* mylists = lists + (long long)(wave * NQW * 32) * RQ_KCAP;  // wave-private: queries are never shared between waves
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void lvs_rq_kernel(const Lvs
 #pragma unroll
         for (int qb = 0; qb < NQW; ++qb) {
             if constexpr (SEED) {
-                seedbest[qb] = fmaxf(seedbest[qb], rq_max16(acc[qb]));  // the sample holds whole 32-row blocks only
+                seedbest[qb] = fmaxf(seedbest[qb], lvs_max16(acc[qb]));  // the sample holds whole 32-row blocks only
                 continue;
             }
             {   // the shared threshold as it was when this block's rows were requested (a lower bound of the k-th best score
@@ -302,10 +291,10 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void lvs_rq_kernel(const Lvs
                 // (reading it only every 8th block measured 7 % slower)
                 const uint32_t g = __float_as_uint(sideb[qb * 64 + 32 + (lane & 31)]);
                 gord[qb] = g > gord[qb] ? g : gord[qb];
-                tauf[qb] = fmaxf(tauf[qb], rq_tau_float(gord[qb]));
+                tauf[qb] = fmaxf(tauf[qb], lvs_tau(gord[qb]));
             }
             const int ql = qb * 32 + (lane & 31);  // list index inside this wave
-            const bool th = qvalid[qb] && (rq_max16(acc[qb]) >= tauf[qb]);
+            const bool th = qvalid[qb] && (lvs_max16(acc[qb]) >= tauf[qb]);
             if (__any(th)) {
                 uint32_t best_tau = 0;  // the tightest k-th key this lane's query reached in this block
                 // one candidate of one lane is the usual case: every lane finds its FIRST candidate (value and register index) in
@@ -351,7 +340,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void lvs_rq_kernel(const Lvs
                         if (lane < k) UL[lane] = newv;
                         const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
                         if (ql == uq) {
-                            tauf[qb] = fmaxf(tauf[qb], rq_tau_float(ntau));
+                            tauf[qb] = fmaxf(tauf[qb], lvs_tau(ntau));
                             best_tau = ntau > best_tau ? ntau : best_tau;
                         }
                     }
@@ -446,19 +435,8 @@ template <int NJ, int UK, int WAVES, int NQW, int AD, int KCAP, bool SEED>
 hipError_t rq_launch_k(const LvsRqArgs& a, int grid, hipStream_t stream) {
     using G = RqGeom<NJ, UK, WAVES, NQW, KCAP>;
     const size_t lds = (size_t)G::lds_bytes(G::RING);
-    static LvsPerDeviceOnce attr;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_rq_kernel<NJ, UK, WAVES, NQW, AD, KCAP, SEED>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, lds);
-    }
     if (a.groups > 1 && WAVES * NQW * 32 != LVS_RQ_GROUPQ) return hipErrorInvalidValue;  // groups are the eight-wave variant's
-    hipLaunchKernelGGL((lvs_rq_kernel<NJ, UK, WAVES, NQW, AD, KCAP, SEED>), dim3(grid), dim3(WAVES * 64), lds, stream, a);
-    return hipGetLastError();
+    return lvs_launch_lds<lvs_rq_kernel<NJ, UK, WAVES, NQW, AD, KCAP, SEED>>(dim3(grid), dim3(WAVES * 64), lds, stream, a);
 }
 template <int NJ, int UK, int WAVES, int NQW, int AD, bool SEED>
 hipError_t rq_launch_one(const LvsRqArgs& a, int grid, hipStream_t stream) {

@@ -37,19 +37,6 @@ constexpr int SQ = 32;          // queries per query block (MFMA N)
 // UNROLL = A-fragment loads in flight per wave (1 KB each) = fragments per inner-loop iteration: a template parameter so
 // that the branch-free fast path exists for every row length whose fragment count per K segment is a multiple of 8:
 //   16 (d = 256, 512, 768, 1024, ...), 24 (d = 384 - BASELINE configs[0]'s dimension -, 1152), 8 (d = 128, 640, ...)
-
-// scores are finite or -inf, never NaN: v_max3_f32 without fmaxf's canonicalisation (8 instructions for 16 values)
-__device__ inline float max3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ inline float max16(const f32x16& v) {
-    const float a = max3(v[0], v[1], v[2]), b = max3(v[3], v[4], v[5]), c = max3(v[6], v[7], v[8]);
-    const float d = max3(v[9], v[10], v[11]), e = max3(v[12], v[13], v[14]);
-    return max3(max3(a, b, c), max3(d, e, v[15]), v[15]);
-}
-
 }  // namespace
 
 // SEED = true: the same scan over a SAMPLE of the rows with a trivial epilogue - every lane keeps the best score it saw, the
@@ -252,14 +239,14 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
                 }
             }
             if constexpr (SEED) {
-                seedbest[qb] = fmaxf(seedbest[qb], max16(acc[qb]));  // the sample holds whole 32-row blocks only: every row is real
+                seedbest[qb] = fmaxf(seedbest[qb], lvs_max16(acc[qb]));  // the sample holds whole 32-row blocks only: every row is real
                 continue;
             }
             {
                 const uint32_t lo = (uint32_t)(lists[q * KCAP + k - 1] >> 32);
                 tauf[qb] = fmaxf(tauf[qb], lvs_tau(lo));
             }
-            const bool th = qvalid[qb] && (max16(acc[qb]) >= tauf[qb]);
+            const bool th = qvalid[qb] && (lvs_max16(acc[qb]) >= tauf[qb]);
             if (__any(th)) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -275,7 +262,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
                         }
                     }
                     unsigned long long pm = __ballot(pending);
-                    // the text of lvs_list_insert (lvs_tile.h): calling it here renames registers of the fragment loop
+                    // the text of lvs_list_insert (lvs_common.h): calling it here renames registers of the fragment loop
                     while (pm) {
                         const int src = __ffsll((long long)pm) - 1;
                         pm &= pm - 1;
@@ -398,18 +385,7 @@ int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, 
 
 template <int U, int NQB, int WAVES, bool SEED>
 static hipError_t stream_launch_one(const LvsStreamArgs& a, int grid, size_t lds, hipStream_t stream) {
-    static LvsPerDeviceOnce attr;  // the attribute is a per-device property (one per instantiation)
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_stream_kernel<U, NQB, WAVES, SEED>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, lds);
-    }
-    hipLaunchKernelGGL((lvs_stream_kernel<U, NQB, WAVES, SEED>), dim3(grid), dim3(WAVES * 64), lds, stream, a);
-    return hipGetLastError();
+    return lvs_launch_lds<lvs_stream_kernel<U, NQB, WAVES, SEED>>(dim3(grid), dim3(WAVES * 64), lds, stream, a);
 }
 
 template <int NQB, int WAVES, bool SEED>

@@ -288,6 +288,14 @@ bool lvs_rj_fits(int64_t nq, int64_t nb, int dpad, int k, bool has_row_ids);
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // whole 32-row blocks only: the caller adds the tail
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // the same geometry, RANGE epilogue (inner product)
 
+// ---- lvs_kmeans.hip: the stable counting sort of the k-means update, for other callers (the IVF lists and the inversion of
+// an IVF search's probes).  Positions 0 .. n-1 grouped by the id in their result key (keys[i], id_offset 0) or by assign[i]
+// (exactly one of the two non-NULL), ascending inside a bucket; ids outside [0, k) are left out.  *rows_out [n] and
+// *offs_out [k + 1] point into the workspace. ----
+int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k);
+int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
+                             hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out);
+
 // ---- lvs_ivf.hip: the list scan of an IVF-Flat search.  A work item is one inverted list and a tile of up to 32 of the
 // (query, probe rank) pairs that probe it; the list's rows are gathered by number from the flat image. ----
 #define LVS_IVF_TILEQ 32     // pairs per work item (MFMA N)
@@ -318,12 +326,6 @@ hipError_t lvs_ivf_tiles_launch(const uint32_t* pair_offs, int nlist, uint32_t* 
 hipError_t lvs_ivf_scan_launch(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream);
 hipError_t lvs_ivf_probe_ids_launch(const u64* keys, int64_t n, int32_t* out, hipStream_t stream);
 hipError_t lvs_ivf_offsets_launch(const uint32_t* offs, int nlist, int64_t* out, hipStream_t stream);
-// stable bucketing (lvs_kmeans.hip): positions 0 .. n-1 grouped by the id in their result key (keys[i], id_offset 0) or
-// by assign[i] (exactly one of the two non-NULL), ascending inside a bucket; ids outside [0, k) are left out.
-// *rows_out [n] and *offs_out [k + 1] point into the workspace.
-int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k);
-int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
-                             hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out);
 
 // ---- lvs_ivf_sq8.hip: the 8-bit residual codec of IVF-SQ8 and its list scan.  A work item is one list and up to 16 of the
 // (query, probe rank) pairs that probe it (half of a work item of lvs_ivf_tiles_launch); the codes are in list order. ----
@@ -381,58 +383,6 @@ hipError_t lvs_ivf_pq_lut_launch(const void* xq, int64_t ldq, int split, int qdp
                                  const float* codebooks, float* lut, hipStream_t stream);
 // launches ceil(nprobe / prange) x nq workgroups
 hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream);
-
-// ---- device helpers shared by lvs_stream.hip and the three IVF files ----
-// the score a list's last slot stands for: an empty slot (ord 0) admits everything
-__device__ __forceinline__ float lvs_tau(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
-__device__ __forceinline__ float lvs_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float lvs_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-// Wave-cooperative sorted insertion into descending lists of k keys in LDS (lists [slots][KCAP], one lock per slot: the
-// waves of a workgroup share the lists).  pm is the ballot of the lanes that hold a key; every such key goes, one at a time,
-// into the list of its lane's slot: the key and slot are broadcast, lane 0 takes the list's lock, lane j < k reads slots j
-// and j - 1 and writes the shifted slot j, lane 0 unlocks; lanes of the same slot raise their threshold tauf to the list's
-// new last slot.  lvs_stream_kernel and lvs_ivf_pq_scan_kernel carry the same text in place (the call changes their code).
-__device__ __forceinline__ void lvs_list_insert(unsigned long long pm, u64 key, int slot, u64* lists, int KCAP, uint32_t* locks,
-                                                int k, int lane, float& tauf) {
-    while (pm) {
-        const int src = __ffsll((long long)pm) - 1;
-        pm &= pm - 1;
-        const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src);
-        const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), src);
-        const u64 ukey = ((u64)khi << 32) | klo;
-        const int uq = __builtin_amdgcn_readlane(slot, src);
-        u64* UL = lists + uq * KCAP;
-        u64 mine = 0, prev = ~0ull;
-        for (;;) {
-            uint32_t seen = 0;
-            if (lane == 0)
-                __hip_atomic_compare_exchange_strong(&locks[uq], &seen, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
-            asm volatile("" ::: "memory");
-            if (lane < k) {
-                mine = UL[lane];
-                if (lane > 0) prev = UL[lane - 1];
-            }
-            if (__builtin_amdgcn_readfirstlane(seen) == 0) break;
-        }
-        u64 newv = 0;
-        if (lane < k) newv = mine > ukey ? mine : (prev > ukey ? ukey : prev);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < k) UL[lane] = newv;
-        const uint32_t ntau = __builtin_amdgcn_readlane((uint32_t)(newv >> 32), k - 1);
-        asm volatile("" ::: "memory");  // slot writes stay ahead of the unlock (LDS is in-order per wave)
-        if (lane == 0) __hip_atomic_store(&locks[uq], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (slot == uq) tauf = fmaxf(tauf, lvs_tau(ntau));
-    }
-}
 
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);

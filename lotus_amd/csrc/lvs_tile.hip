@@ -52,23 +52,9 @@ struct Geo {
     static_assert(KCAP <= 64, "one lane per list slot");
 };
 
-// Scores are finite or -inf, never NaN, so the maxima need none of fmaxf's canonicalisation (hipcc emits one extra
-// `v_max_f32 x, x` per MFMA output to quiet signalling NaNs): v_max3_f32 directly - 8 instructions for 16 values.
-__device__ inline float max3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ inline float max4(float a, float b, float c, float d) { return max3(max3(a, b, c), d, d); }
-__device__ inline float max16(const f32x16& v) {
-    const float a = max3(v[0], v[1], v[2]), b = max3(v[3], v[4], v[5]), c = max3(v[6], v[7], v[8]);
-    const float d = max3(v[9], v[10], v[11]), e = max3(v[12], v[13], v[14]);
-    return max3(max3(a, b, c), max3(d, e, v[15]), v[15]);
-}
+__device__ inline float max4(float a, float b, float c, float d) { return lvs_max3(lvs_max3(a, b, c), d, d); }
 // wave-uniform "any lane" without materialising a per-lane bool
 __device__ inline bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
-
-__device__ inline float tau_float(uint32_t ord) { return ord == 0 ? -INFINITY : lvs_unord32(ord); }
 
 // Every lane's first candidate (lowest accumulator register r with v[r] >= tf) of one 32 x 32 block, in straight-line
 // code: per register one compare, two selects and two scalar mask operations - no per-row branch.  any_m = lanes with at
@@ -213,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
             if (a.metric == LVS_METRIC_L2) qnv[ni] = a.qn[q0 + qloc[ni]];
             if (MODE == LVS_MODE_COLLECT) {  // ubk = LOWER bound key here, tauf = its score
                 ubk[ni] = a.thr_key[q0 + qloc[ni]];
-                tauf[ni] = tau_float((uint32_t)(ubk[ni] >> 32));
+                tauf[ni] = lvs_tau((uint32_t)(ubk[ni] >> 32));
             }
         }
     }
@@ -339,7 +325,7 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
                     const long long qg = q0 + qloc[ni];
                     if constexpr (MODE == LVS_MODE_COLLECT) {
                         // tauf / ubk were loaded from a.thr_key: score part (fast filter) and full key (exact test)
-                        const bool th = qvalid[ni] && (max16(acc[mi][ni]) >= tauf[ni]);
+                        const bool th = qvalid[ni] && (lvs_max16(acc[mi][ni]) >= tauf[ni]);
                         if (!wave_any(th)) continue;
                         if (!th) continue;
 #pragma unroll
@@ -363,7 +349,7 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
                             if (row < a.nb) orow[row] = acc[mi][ni][r] * a.out_scale;
                         }
                     } else {
-                        const bool th = qvalid[ni] && (max16(acc[mi][ni]) > a.threshold);
+                        const bool th = qvalid[ni] && (lvs_max16(acc[mi][ni]) > a.threshold);
                         if (!__any(th)) continue;
                         if (!th) continue;
 #pragma unroll
@@ -472,18 +458,18 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < 2; ++ni) bestv[ni] = fmaxf(bestv[ni], max16(acc[mi][ni]));
+                for (int ni = 0; ni < 2; ++ni) bestv[ni] = fmaxf(bestv[ni], lvs_max16(acc[mi][ni]));
         } else {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
             if (qvalid[ni]) {
                 const uint32_t g = gpre[ni];
                 gord[ni] = g > gord[ni] ? g : gord[ni];
-                tauf[ni] = fmaxf(tauf[ni], tau_float(gord[ni]));
+                tauf[ni] = fmaxf(tauf[ni], lvs_tau(gord[ni]));
             }
         // own lists' thresholds (they may have risen since this lane last looked: the wave sharing these queries inserts too)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) tauf[ni] = fmaxf(tauf[ni], tau_float(lpre[ni]));
+        for (int ni = 0; ni < 2; ++ni) tauf[ni] = fmaxf(tauf[ni], lvs_tau(lpre[ni]));
         // fast filter: which of the wave's 2*MI 32x32 blocks hold a score that may enter some query's list?
         uint32_t hitmask = 0;  // wave-uniform, bit tsel = mi * 2 + ni
 #ifdef LVS_COUNT_EVENTS
@@ -496,7 +482,7 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
-                if (wave_any(max16(acc[mi][ni]) >= tfe[ni])) hitmask |= 1u << (mi * 2 + ni);
+                if (wave_any(lvs_max16(acc[mi][ni]) >= tfe[ni])) hitmask |= 1u << (mi * 2 + ni);
 #ifdef LVS_TUNING
         if (a.debug_hot == 2) hitmask = 0;  // tuning aid: skip the slow path (results are wrong, timing only)
 #endif
@@ -568,7 +554,7 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
                     asm volatile("" ::: "memory");
                     if (lane == 0)
                         __hip_atomic_store(&locks[uq], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (q == uq) tf = fmaxf(tf, tau_float(ntau));
+                    if (q == uq) tf = fmaxf(tf, lvs_tau(ntau));
 #ifdef LVS_COUNT_EVENTS
                     c_ins += __builtin_amdgcn_s_memtime() - ti0;
 #endif
@@ -754,19 +740,8 @@ __global__ __launch_bounds__(512, 2) void lvs_tile_kernel(const LvsTileArgs a) {
 
 template <int MODE, int MI>
 static hipError_t launch_one(const LvsTileArgs& a, hipStream_t stream) {
-    static LvsPerDeviceOnce attr;  // one per instantiation; the attribute is a per-device property
-    constexpr int lds = Geo<MI>::LDS_TOTAL;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!attr.done(dev, (size_t)lds)) {
-        e = hipFuncSetAttribute((const void*)lvs_tile_kernel<MODE, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr.set(dev, (size_t)lds);
-    }
-    dim3 grid(lvs_tile_grid_blocks(a.nqt, a.nslab, a.gq, a.lead_slabs)), block(512);
-    hipLaunchKernelGGL((lvs_tile_kernel<MODE, MI>), grid, block, lds, stream, a);
-    return hipGetLastError();
+    const dim3 grid(lvs_tile_grid_blocks(a.nqt, a.nslab, a.gq, a.lead_slabs));
+    return lvs_launch_lds<lvs_tile_kernel<MODE, MI>>(grid, dim3(512), Geo<MI>::LDS_TOTAL, stream, a);
 }
 
 // a.bq names the geometry a.nqt was computed for: LVS2_BQ (k <= LVS2_KCAP and the TOP1 / RANGE / SCORES modes) or
