@@ -44,7 +44,8 @@ extern "C" {
                                 lvs_ivf_search_workspace_bytes, lvs_ivf_search_keys, LVS_KERNEL_IVF) - no existing entry changed;
                                 IVF-SQ8 codes and search (lvs_ivf_sq8_encode, lvs_ivf_sq8_search_workspace_bytes,
                                 lvs_ivf_sq8_search_keys, LVS_KERNEL_IVF_SQ8); IVF-PQ codes and search (lvs_ivf_pq_encode,
-                                lvs_ivf_pq_search_workspace_bytes, lvs_ivf_pq_search_keys, LVS_KERNEL_IVF_PQ) */
+                                lvs_ivf_pq_search_workspace_bytes, lvs_ivf_pq_search_keys, LVS_KERNEL_IVF_PQ); exact re-ranking
+                                of a first stage's candidates (lvs_refine_keys, LVS_KERNEL_REFINE) */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -517,6 +518,20 @@ int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const fl
                                int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                void* stream);
 
+/* ---- exact re-ranking of a search's candidates (faiss `IndexRefineFlat`, "IVF<nlist>,PQ<M>,Refine(Flat)"): the second
+ * stage behind lvs_ivf_sq8_search_keys / lvs_ivf_pq_search_keys run at kc >= k.  cand_keys [nq][kc]: the first stage's keys;
+ * only the ROW NUMBER of a key is read (the score bits are ignored), and a slot whose key is 0 or whose row is >= nb is empty:
+ * never loaded from, wherever it stands in the list.  Every other slot's row is scored against xb [nb][ld(xb_pack)] - the
+ * flat packed image, fp16 or fp32-accurate hi|lo - exactly as lvs_flat_search_keys scores it (fp32 accumulation; squared L2
+ * from xb_norms_sq / xq_norms_sq, required for LVS_METRIC_L2, ignored for IP), and out_keys [nq][k] receives the best k by
+ * that score, best first, keys as lvs_flat_search_keys (equal scores in ascending row order; key 0 past the non-empty
+ * slots).  1 <= k <= kc <= 64, any d.  No workspace, no synchronisation; every argument check precedes the first device
+ * call and nq == 0 returns LVS_OK without a launch.  lvs_refine_kernel: one wave per query, whole rows gathered into
+ * registers, four rows in flight per wave. ---- */
+int32_t lvs_refine_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq, const void* xq, int32_t xq_pack,
+                        int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric, const uint64_t* cand_keys, int32_t kc,
+                        int32_t k, uint64_t* out_keys, void* stream);
+
 /* ---- measurement hook: average duration in ms of the dominant search kernel's launches since the last reset,
  * measured with HIP events on the launch stream (enabled with lvs_timing_enable(1)). ---- */
 int32_t lvs_timing_enable(int32_t on);
@@ -532,6 +547,7 @@ int32_t lvs_timing_read(double* out_total_ms, int64_t* out_launches);
 #define LVS_KERNEL_IVF_SQ8 5 /* lvs_ivf_sq8_scan_kernel: one list's 8-bit codes x up to 16 probing queries (lvs_ivf_sq8_search_keys) */
 #define LVS_KERNEL_IVF_PQ 6 /* lvs_ivf_pq_lut_kernel + lvs_ivf_pq_scan_kernel: one query's table x its probed lists' PQ codes
                                (lvs_ivf_pq_search_keys) */
+#define LVS_KERNEL_REFINE 7 /* lvs_refine_kernel: one wave re-scores a query's candidate rows exactly (lvs_refine_keys) */
 int32_t lvs_timing_read_calls(double* out_total_ms, int64_t* out_launches, int64_t* out_calls, int32_t* out_kernel);
 
 #ifdef __cplusplus

@@ -1147,6 +1147,26 @@ class HipBackend:
                 lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(pq.centroids))
         return self._ivf_search("lvs_ivf_pq_search", (pq.M,), head, corpus, lists, queries, k, metric, nprobe, want_probe)
 
+    # ---- exact re-ranking ("...,Refine(Flat)") ----
+    REFINE_MAX_CANDIDATES = 64  # candidate slots per query of lvs_refine_keys: one per lane of the query's wave
+
+    def refine_keys(self, corpus: PackedRows, queries: PackedRows, cand_keys, k: int, metric: int):
+        """cand_keys int64 [nq, kc] (a first stage's result keys, kc <= 64) -> int64 keys [nq, k], k <= kc: the best ``k`` of
+        every query's candidate rows by their EXACT score against the stored rows of ``corpus`` (``lvs_refine_keys``), best
+        first, equal scores in ascending row order.  Only the row number of a candidate key is read; key 0 (and a row
+        number past the corpus) is an empty slot, and the result is padded with key 0 when fewer than ``k`` slots hold a row."""
+        torch = self.torch
+        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
+            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
+        nq, kc = int(cand_keys.shape[0]), int(cand_keys.shape[1])
+        if nq != queries.n:
+            raise ValueError(f"cand_keys has {nq} rows for {queries.n} queries")
+        cand = cand_keys.contiguous()
+        out = torch.empty((nq, int(k)), dtype=torch.int64, device=self.device)
+        self._c("lvs_refine_keys", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(queries.rows), queries.mode,
+                nq, _ptr(queries.norms), corpus.d, metric, _ptr(cand), kc, int(k), _ptr(out), self._stream())
+        return out
+
     def merge_keys(self, parts):
         """parts int64 [P, nq, k] -> [nq, k]."""
         torch = self.torch
@@ -1410,7 +1430,7 @@ class HipBackend:
         _capi.check(self.lib.lvs_timing_enable(int(on)))
 
     KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel", 4: "lvs_ivf_scan_kernel",
-                    5: "lvs_ivf_sq8_scan_kernel", 6: "lvs_ivf_pq_scan_kernel"}
+                    5: "lvs_ivf_sq8_scan_kernel", 6: "lvs_ivf_pq_scan_kernel", 7: "lvs_refine_kernel"}
 
     def timing_read(self):
         """-> (total ms of the dominant kernel's launches, searches that timed at least one): total / searches = kernel time per

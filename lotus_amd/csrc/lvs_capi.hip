@@ -2468,3 +2468,42 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
         return LVS_OK;
     });
 }
+
+// ---- exact re-ranking of a first stage's candidates ("...,Refine(Flat)"): every check ahead of the first device call
+extern "C" int32_t lvs_refine_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq, const void* xq,
+                                   int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric,
+                                   const uint64_t* cand_keys, int32_t kc, int32_t k, uint64_t* out_keys, void* stream) {
+    LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
+    LVS_REQUIRE(nb >= 0 && nb < 0xFFFFFFFFll && nq >= 0 && nq < (1ll << 32) && d > 0 && d <= (1 << 24),
+                "bad shape nb=%lld nq=%lld d=%d", (long long)nb, (long long)nq, d);
+    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
+    LVS_REQUIRE(xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT, "bad xq_pack");
+    LVS_REQUIRE(kc >= 1 && kc <= LVS_REFINE_MAXKC, "kc=%d must be in [1, %d] (one candidate per lane)", kc, LVS_REFINE_MAXKC);
+    LVS_REQUIRE(k >= 1 && k <= kc, "k=%d must be in [1, kc=%d]", k, kc);
+    if (nq == 0) return LVS_OK;
+    LVS_REQUIRE(xq && cand_keys && out_keys && (xb || nb == 0), "NULL buffer");
+    LVS_REQUIRE(metric != LVS_METRIC_L2 || (xq_norms_sq && (xb_norms_sq || nb == 0)), "squared L2 needs the norms");
+    LvsRefineArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xb = xb;
+    a.bn = xb_norms_sq;
+    a.xq = xq;
+    a.qn = xq_norms_sq;
+    a.cand = (const u64*)cand_keys;
+    a.out = (u64*)out_keys;
+    a.nb = nb;
+    a.nq = nq;
+    a.dpad = (int)lvs_round_up(d, LVS_BK);
+    a.bsplit = xb_pack == LVS_PACK_SPLIT;
+    a.qsplit = xq_pack == LVS_PACK_SPLIT;
+    a.ldb = a.bsplit ? 2 * a.dpad : a.dpad;
+    a.ldq = a.qsplit ? 2 * a.dpad : a.dpad;
+    a.kc = kc;
+    a.k = k;
+    a.metric = metric;
+    LVS_DEVICE_GUARD(stream);
+    hipStream_t st = (hipStream_t)stream;
+    ScopedKernelTimer timer(st, LVS_KERNEL_REFINE);
+    LVS_HIP_CHECK(lvs_refine_launch(a, st));
+    return LVS_OK;
+}

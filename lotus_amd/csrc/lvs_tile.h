@@ -384,6 +384,22 @@ hipError_t lvs_ivf_pq_lut_launch(const void* xq, int64_t ldq, int split, int qdp
 // launches ceil(nprobe / prange) x nq workgroups
 hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream);
 
+// ---- lvs_refine.hip: exact re-ranking of up to 64 candidate rows per query (the second stage of "...,Refine(Flat)").  One
+// wave per query; the rows are gathered by number from the flat image, whole rows into registers. ----
+#define LVS_REFINE_WAVES 4   // queries (waves) per workgroup
+#define LVS_REFINE_MAXKC 64  // candidate slots per query: one per lane
+struct LvsRefineArgs {
+    const void* xb;              // the flat packed image [nb][ldb]
+    const float* bn;             // [nb] |row|^2 (L2 only)
+    const void* xq;              // packed queries [nq][ldq]
+    const float* qn;             // [nq] |q|^2 (L2 only)
+    const u64* cand;             // [nq][kc] candidate keys: only the row number is read; key 0 or row >= nb: empty slot
+    u64* out;                    // [nq][k]
+    long long nb, nq, ldb, ldq;
+    int dpad, kc, k, metric, qsplit, bsplit;
+};
+hipError_t lvs_refine_launch(const LvsRefineArgs& a, hipStream_t stream);
+
 int lvs_stream_ranges(int64_t nb, int groups);
 size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap);
 int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, int* out_groups);

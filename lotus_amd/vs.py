@@ -18,7 +18,8 @@ Differences that are deliberate supersets (SURVEY.md section 8(a) edge-case tabl
   * ``factory_string="IVF<nlist>,Flat"`` builds the inverted-file index ``FaissVS`` advertises but cannot train
     (``faiss_vs.py:23-24`` calls ``add()`` without ``train()``): plain searches probe ``nprobe`` lists, everything else
     stays exact (see ``HipVS``); ``"IVF<nlist>,SQ8"`` adds faiss's 8-bit residual scalar quantizer on top of the same lists,
-    ``"IVF<nlist>,PQ<M>"`` faiss's residual product quantizer (8-bit codes, M bytes per row).
+    ``"IVF<nlist>,PQ<M>"`` faiss's residual product quantizer (8-bit codes, M bytes per row); either followed by
+    ``",Refine(Flat)"`` re-ranks the codes' best candidates exactly against the full-precision rows (``IndexRefineFlat``).
 """
 from __future__ import annotations
 
@@ -64,10 +65,11 @@ class _IvfMode:
 
     kind: str  # "Flat" | "SQ8" | "PQ"
     M: int | None = None  # subspaces of a PQ store
+    refine: bool = False  # "...,Refine(Flat)": the codes' candidates are re-ranked by their exact scores (SQ8 and PQ only)
 
     @property
-    def requires(self):  # the method an injected backend must have to build such a store: asked of the newest mode only
-        return "ivf_pq_search" if self.kind == "PQ" else None
+    def requires(self):  # the methods an injected backend must have to build such a store: asked of the newest modes only
+        return (("ivf_pq_search",) if self.kind == "PQ" else ()) + (("refine_keys",) if self.refine else ())
 
     def check_width(self, d: int, factory_string: str) -> None:
         """faiss asserts d % M == 0 for a product quantizer: rows of another width cannot back an IVF-PQ store."""
@@ -206,28 +208,48 @@ class HipVS(VS):
             full-precision rows, which stay resident.  The directory is written as for ``"IVF<nlist>,Flat"`` plus
             ``ivf_pq.npz`` with the codebooks and the codes; ``pq_codes()`` returns them.  Other code sizes (``PQ<M>x4``,
             ``x4fs``) are refused.
+            ``"IVF<nlist>,SQ8,Refine(Flat)"`` / ``"IVF<nlist>,PQ<M>[x8],Refine(Flat)"`` - faiss's ``IndexRefineFlat`` around
+            the same store: a plain search runs the codes' scan at ``refine_candidates(K)`` candidates per query and then
+            re-scores those rows exactly against the full-precision image, which is resident anyway
+            (``HipBackend.refine_keys``); the best ``K`` by the exact score are returned, with exact distances.  Everything
+            else - the lists, the codec, the sidecars (a refined and a plain store of the same nlist and M read and write the
+            same files), the exact fallbacks, ``ivf_probe`` / ``sq8_codes`` / ``pq_codes`` - is the plain store's.  No other
+            refiner is taken (``RFlat``, ``Refine(SQ8)``), and ``"IVF<nlist>,Flat"`` has nothing to refine.
         nprobe: lists probed per query (faiss's default 1).
+        k_factor: candidates per returned row of a ``Refine(Flat)`` store (faiss's ``IndexRefine.k_factor``, default 1: the
+            codes' own top K, re-ordered by exact score); ``__call__(..., k_factor=...)`` overrides it per call.  A finite
+            number >= 1.  The candidate count is ``min(max(K, ceil(K * k_factor)), 56, n)``: unlike faiss it stops at 56, the
+            list scans' one-pass bound.  Stores without ``Refine(Flat)`` ignore it.
     """
 
     def __init__(self, metric: int = METRIC_INNER_PRODUCT, storage: str = "auto", device: str | None = None,
                  shard: bool | str = False, max_resident: int = 4, backend=None, process_group=None,
                  normalize: bool = False, abi_exchange: bool = False, factory_string: str = "Flat", nprobe: int = 1,
-                 ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256) -> None:
+                 ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256, k_factor: float = 1.0) -> None:
         super().__init__()
-        m = (re.fullmatch(r"IVF([0-9]+),(Flat|SQ8|PQ([0-9]+)(?:x8)?)", factory_string) if isinstance(factory_string, str)
-             else None)
+        m = (re.fullmatch(r"IVF([0-9]+),(Flat|(?:SQ8|PQ([0-9]+)(?:x8)?)(,Refine\(Flat\))?)", factory_string)
+             if isinstance(factory_string, str) else None)
         if factory_string != "Flat" and (m is None or int(m.group(1)) < 1 or (m.group(3) is not None and int(m.group(3)) < 1)):
             raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' or 'IVF<nlist>,PQ<M>[x8]' "
-                             f"(nlist >= 1, M >= 1, 8-bit codes), got {factory_string!r}")
+                             "(nlist >= 1, M >= 1, 8-bit codes; SQ8 and PQ<M> may be followed by ',Refine(Flat)', the only "
+                             f"refiner), got {factory_string!r}")
         self._nlist = int(m.group(1)) if m is not None else None
         # None for "Flat"; an IVF store's mode makes every call that differs between IVF-Flat, IVF-SQ8 and IVF-PQ
-        self._mode = None if m is None else _IvfMode("PQ", int(m.group(3))) if m.group(3) is not None else _IvfMode(m.group(2))
-        # an injected backend without the IVF-PQ codec (a test double of an earlier mode) cannot build such a store
-        needs = self._mode.requires if self._mode is not None and backend is not None else None
-        if needs is not None and not hasattr(backend, needs):
+        refine = m is not None and m.group(4) is not None
+        self._mode = (None if m is None else _IvfMode("PQ", int(m.group(3)), refine) if m.group(3) is not None
+                      else _IvfMode("SQ8" if refine else m.group(2), None, refine))
+        # an injected backend without the IVF-PQ codec or the re-ranking (a test double of an earlier mode) cannot build such a store
+        needs = self._mode.requires if self._mode is not None and backend is not None else ()
+        missing = [a for a in needs if not hasattr(backend, a)]
+        if missing and missing[0] == "ivf_pq_search":
             raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' with a backend that has "
                              f"no IVF-PQ codec ({type(backend).__name__}), got {factory_string!r}")
+        if missing:
+            raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' or 'IVF<nlist>,PQ<M>[x8]' "
+                             f"with a backend that has no exact re-ranking ({type(backend).__name__} lacks refine_keys), got "
+                             f"{factory_string!r}")
         self.factory_string = factory_string
+        self.k_factor = self._check_k_factor(k_factor)
         if self._nlist is not None and shard is not False:
             raise ValueError(f"an IVF index is single-GPU: shard must be False with factory_string={factory_string!r}")
         self.nprobe = self._check_nprobe(nprobe)
@@ -552,8 +574,13 @@ class HipVS(VS):
         # wide for its LDS image and more than 2 048 probes take the exact path below - which also ends the reference
         # sem_search's K-doubling loop (sem_search.py:120-138) once the probed lists hold fewer than K rows
         nprobe = min(self._check_nprobe(kwargs.get("nprobe", self.nprobe)), ent.ivf.nlist) if ent.ivf is not None else 0
+        # a Refine(Flat) store runs its codes' scan at kc >= K candidates per query and re-ranks them exactly; a scan that
+        # does not take kc leaves the call exact, like any shape the scan does not fit
+        k_factor = self._check_k_factor(kwargs.get("k_factor", self.k_factor))
+        refine = self._mode is not None and self._mode.refine
+        kc = self._refine_kc(K, k_factor, ent.n) if refine else K
         use_ivf = (ent.ivf is not None and sub is None and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
-                   and qworld == 1 and nprobe <= _capi.MAX_K and self._mode.fits(be, ent, K))
+                   and qworld == 1 and nprobe <= _capi.MAX_K and self._mode.fits(be, ent, kc))
         q_all = nq
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
             per = -(-nq // qworld)
@@ -613,7 +640,9 @@ class HipVS(VS):
                 id_map = be.to_device(order)
             world = 1  # already complete on every rank: nothing left to merge
         elif use_ivf:
-            keys = self._mode.search(be, ent, queries, k_eff, self.metric, nprobe)
+            keys = self._mode.search(be, ent, queries, kc, self.metric, nprobe)
+            if refine:  # the kc best by code score -> the k_eff best of them by exact score, exact scores in the keys
+                keys = be.refine_keys(ent.packed, queries, keys, k_eff, self.metric)
         elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
             # the same row-sharded search with its two exchanges issued from INSIDE the C ABI (lvs_search_sharded): the transport
             # is this process group's all-gather, handed over as a callback
@@ -675,6 +704,29 @@ class HipVS(VS):
         if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or int(nprobe) < 1:
             raise ValueError(f"nprobe must be an int >= 1, got {nprobe!r}")
         return int(nprobe)
+
+    @staticmethod
+    def _check_k_factor(k_factor) -> float:
+        ok = (not isinstance(k_factor, bool) and isinstance(k_factor, (int, float, np.integer, np.floating))
+              and np.isfinite(k_factor) and k_factor >= 1)
+        if not ok:
+            raise ValueError(f"k_factor must be a finite number >= 1, got {k_factor!r}")
+        return float(k_factor)
+
+    @staticmethod
+    def _refine_kc(K: int, k_factor: float, n: int) -> int:
+        """Candidates per query of a re-ranked search: faiss's ``ceil(K * k_factor)``, at least K, at most the list scans'
+        one-pass bound (56 - where faiss has no bound) and the number of rows."""
+        return int(min(max(K, int(np.ceil(K * k_factor))), _capi.IVF_MAX_K, n))
+
+    def refine_candidates(self, K: int, k_factor: float | None = None) -> int:
+        """How many candidates per query the codes' scan of a ``Refine(Flat)`` store hands to the exact re-ranking for a plain
+        search of ``K`` rows: ``min(max(K, ceil(K * k_factor)), 56, n)`` with the loaded index's ``n`` rows (``k_factor``
+        None: the store's).  The clamp at 56 is a deviation from faiss, whose ``IndexRefine`` takes any ``K * k_factor``."""
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or int(K) < 1:
+            raise ValueError(f"K must be an int >= 1, got {K!r}")
+        f = self.k_factor if k_factor is None else self._check_k_factor(k_factor)
+        return self._refine_kc(int(K), f, self._current().n)
 
     def _ivf_train(self, ent: _Resident):
         """Centroids (device k-means on the packed image, squared L2, fixed seed) and lists of an IVF store, and for an SQ8 or

@@ -1,4 +1,4 @@
-"""The IVF modes (--modes flat sq8 pq) against the exact path on one MI355X: 1 M rows, nlist 4 096, nprobe in {8, 32, 128},
+"""The IVF modes (--modes flat sq8 pq sq8r pqr) against the exact path on one MI355X: 1 M rows, nlist 4 096, nprobe in {8, 32, 128},
 k = 10, per --workloads d:storage pair (default: d = 768 and d = 3072, text-embedding-3-large's width, stored as hi|lo).
 
 Per workload, column (exact, then every chosen mode whose list scan takes the width) and nprobe, for 1 and 10 000 queries:
@@ -11,13 +11,18 @@ Per workload, column (exact, then every chosen mode whose list scan takes the wi
     lists once (a lower bound);
   * recall@10 against the exact search on benchdata's configs[2] rows (uniform: the worst case for IVF) and on a seeded
     clustered set (benchdata.blobs).
+The refined modes (sq8r, pqr: "...,Refine(Flat)" at --k-factor) run two timed kernels per call, the codes' scan at kc =
+refine_candidates(k) and lvs_refine_kernel; their kernel ms per call is the sum of both.  Beside it stands the plain store's
+search at K = kc (first_stage_kernel_ms: the same code and shape as the refined store's first stage), the difference
+(refine_kernel_ms) and the re-ranking's rate: queries x kc x bytes of a stored row over that difference (refine_tbps).
 Prints one JSON document (and writes it to --out).
 
 The committed profiles are records of these runs (the first two of earlier generations of this tool, whose JSON named some
 keys differently):
   profiles/ivf_bench.json      python tools/ivf_bench.py --modes flat --workloads 768:fp16 --reps1 50
   profiles/ivf_sq8_bench.json  python tools/ivf_bench.py --modes flat sq8 --workloads 768:fp16 768:fp32 1536:fp32
-  profiles/ivf_pq_bench.json   python tools/ivf_bench.py"""
+  profiles/ivf_pq_bench.json   python tools/ivf_bench.py
+  profiles/ivf_refine_bench.json  python tools/ivf_bench.py --modes sq8 pq sq8r pqr --k-factor 5"""
 from __future__ import annotations
 
 import argparse
@@ -32,10 +37,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BPS = 8e12
-MODES = ("flat", "sq8", "pq")
+MODES = ("flat", "sq8", "pq", "sq8r", "pqr")
+REFINED = {"sq8r": "sq8", "pqr": "pq"}  # a refined column -> the plain column whose scan is its first stage
 
 
-def timed(vs, q, k, reps, warmup, **kw):
+def timed(vs, q, k, reps, warmup, per_call=1, **kw):
+    """per_call: timed entry points per search (2 for a refined store: the scan and the re-ranking are added up)."""
     be = vs.backend
     for _ in range(warmup):
         vs(q, k, **kw)
@@ -48,7 +55,7 @@ def timed(vs, q, k, reps, warmup, **kw):
         walls.append((time.perf_counter() - t0) * 1e3)
     t = be.timing_read_full()
     be.timing_enable(False)
-    return {"wall_ms": float(np.median(walls)), "kernel_ms": t["total_ms"] / max(1, t["calls"]), "kernel": t["kernel"]}
+    return {"wall_ms": float(np.median(walls)), "kernel_ms": t["total_ms"] / max(1, t["calls"] // per_call), "kernel": t["kernel"]}
 
 
 def probed_rows(vs, q, nprobe):
@@ -68,6 +75,11 @@ def columns(a, be, d, k, mode):
         cols["sq8"] = "SQ8"
     if "pq" in a.modes and be.ivf_pq_fits(d, a.M, k, mode):
         cols["pq"] = f"PQ{a.M}"
+    kc = min(56, max(k, int(np.ceil(k * a.k_factor))))  # the refined stores' first stage runs at kc
+    if "sq8r" in a.modes and be.ivf_sq8_fits(d, kc, mode):
+        cols["sq8r"] = "SQ8,Refine(Flat)"
+    if "pqr" in a.modes and be.ivf_pq_fits(d, a.M, kc, mode):
+        cols["pqr"] = f"PQ{a.M},Refine(Flat)"
     return cols
 
 
@@ -87,11 +99,13 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
     exact = HipVS(storage=storage, device="cuda:0")
     exact.index(None, xb, "bench-exact", persist=False)
     kinds = columns(a, exact.backend, d, k, mode)
-    if "pq" in kinds:
+    if "pq" in kinds or "pqr" in kinds:
         res["M"] = a.M
+    if set(kinds) & set(REFINED):
+        res["k_factor"] = a.k_factor
     stores = {}
     for name, kind in kinds.items():
-        vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}")
+        vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}", k_factor=a.k_factor)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         vs.index(None, xb, f"bench-{name}", persist=False)
@@ -101,11 +115,27 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
     q1, qb = xq[:1], xq[:a.big]
     res["exact"] = {"q1": timed(exact, q1, k, a.reps1, 5), f"q{a.big}": timed(exact, qb, k, a.repsbig, 1)}
     ref = exact(xq[:a.recall_queries], k).indices
-    row_bytes = {"pq": a.M, "sq8": d, "ivf_flat": d * (2 if storage == "fp16" else 4)}
+    stored_row_bytes = d * (2 if storage == "fp16" else 4)
+    row_bytes = {"pq": a.M, "sq8": d, "ivf_flat": stored_row_bytes, "pqr": a.M, "sq8r": d}
     for name, vs in stores.items():
         col = {}
+        per_call = 2 if name in REFINED else 1
         for nprobe in a.nprobe:
-            r = {"q1": timed(vs, q1, k, a.reps1, 5, nprobe=nprobe), f"q{a.big}": timed(vs, qb, k, a.repsbig, 1, nprobe=nprobe)}
+            r = {"q1": timed(vs, q1, k, a.reps1, 5, per_call, nprobe=nprobe),
+                 f"q{a.big}": timed(vs, qb, k, a.repsbig, 1, per_call, nprobe=nprobe)}
+            if name in REFINED:  # the plain store at K = kc is the refined store's first stage: the rest is the re-ranking
+                kc = vs.refine_candidates(k)
+                r["kc"] = kc
+                plain = stores.get(REFINED[name])
+                for key, qs, reps, warm in (("q1", q1, a.reps1, 5), (f"q{a.big}", qb, a.repsbig, 1)):
+                    if plain is None:
+                        continue
+                    first = timed(plain, qs, kc, reps, warm, nprobe=nprobe)
+                    r[key]["first_stage_kernel_ms"] = first["kernel_ms"]
+                    r[key]["first_stage_wall_ms"] = first["wall_ms"]
+                    r[key]["refine_kernel_ms"] = r[key]["kernel_ms"] - first["kernel_ms"]
+                    r[key]["refine_bytes"] = len(qs) * kc * stored_row_bytes
+                    r[key]["refine_tbps"] = r[key]["refine_bytes"] / max(1e-9, r[key]["refine_kernel_ms"] * 1e-3) / 1e12
             rows1, _ = probed_rows(vs, q1, nprobe)
             pairs, union = probed_rows(vs, qb, nprobe)
             r["q1"]["probed_rows"] = rows1
@@ -128,7 +158,7 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
         ref = exact(qc, k).indices
         del exact
         for name, kind in kinds.items():
-            vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}")
+            vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}", k_factor=a.k_factor)
             vs.index(None, xc, f"bench-{name}-c", persist=False)
             for nprobe in a.nprobe:
                 res[name][str(nprobe)]["recall10_clustered"] = recall(vs(qc, k, nprobe=nprobe).indices, ref)
@@ -142,9 +172,10 @@ def main() -> None:
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nlist", type=int, default=4096)
     ap.add_argument("--nprobe", type=int, nargs="+", default=[8, 32, 128])
-    ap.add_argument("--modes", nargs="+", choices=MODES, default=list(MODES),
+    ap.add_argument("--modes", nargs="+", choices=MODES, default=["flat", "sq8", "pq"],
                     help="the columns beside the exact one; a mode whose list scan refuses a workload's width is skipped there")
-    ap.add_argument("--M", type=int, default=64, help="subspaces of the pq mode")
+    ap.add_argument("--M", type=int, default=64, help="subspaces of the pq and pqr modes")
+    ap.add_argument("--k-factor", type=float, default=5.0, help="k_factor of the refined modes (sq8r, pqr)")
     ap.add_argument("--workloads", nargs="+", default=["768:fp32", "3072:fp32"],
                     help="d:storage pairs (storage fp16 or fp32 = hi|lo)")
     ap.add_argument("--big", type=int, default=10_000)
