@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "lvs_common.h"
+#include "lvs_count_sort.h"
 #include "lvs_tile.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2184,12 +2185,12 @@ int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, S
     return LVS_OK;
 }
 
-// Flat and SQ8: invert a chunk's (query, probe) pairs - pair numbers q * nprobe + p grouped by list -, cut every list's
-// pairs into work items of 32 (the SQ8 scan halves them) and zero the parts (a pair whose probe named no list - never
-// with nprobe <= nlist - keeps empty slots)
+// Flat and SQ8: invert a chunk's (query, probe) pairs - pair numbers q * nprobe + p grouped by list (the bucket sort of
+// lvs_count_sort.hip) -, cut every list's pairs into work items of 32 (the SQ8 scan halves them) and zero the parts (a pair
+// whose probe named no list - never with nprobe <= nlist - keeps empty slots)
 int32_t ivf_group_pairs(const IvfLayout& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t nlist, int32_t k, u64* parts,
                         hipStream_t st, const uint32_t** pairs, const uint32_t** pair_offs) {
-    const int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, w + L.off_sort, L.sort_bytes, st, pairs, pair_offs);
+    const int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, 0, w + L.off_sort, L.sort_bytes, st, pairs, pair_offs);
     if (rc != LVS_OK) return rc;
     LVS_HIP_CHECK(lvs_ivf_tiles_launch(*pair_offs, nlist, (uint32_t*)(w + L.off_tiles), (uint32_t*)(w + L.off_items), st));
     LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
@@ -2247,7 +2248,7 @@ extern "C" int32_t lvs_ivf_build_lists(const int64_t* assign, int64_t n, int32_t
         return LVS_OK;
     }
     const uint32_t *rows = nullptr, *offs = nullptr;
-    const int32_t rc = lvs_bucket_positions(nullptr, assign, n, nlist, workspace, workspace_bytes, st, &rows, &offs);
+    const int32_t rc = lvs_bucket_positions(nullptr, assign, n, nlist, 0, workspace, workspace_bytes, st, &rows, &offs);
     if (rc != LVS_OK) return rc;
     LVS_HIP_CHECK(hipMemcpyAsync(out_rows, rows, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     LVS_HIP_CHECK(lvs_ivf_offsets_launch(offs, nlist, out_offsets, st));

@@ -1,7 +1,7 @@
 // IVF-Flat list scan: the hot kernel of lvs_ivf_search_keys (lvs_capi.hip).
 //
 // An IVF search probes nprobe of nlist inverted lists per query.  The (query, probe rank) pairs are grouped by list
-// (counting sort, lvs_bucket_positions), and one work item is one list together with a tile of up to 32 of the pairs that
+// (the bucket sort of lvs_count_sort.hip), and one work item is one list together with a tile of up to 32 of the pairs that
 // probe it:
 //   * the tile's queries live in LDS as ready-made MFMA B fragments, laid out as in lvs_stream_kernel
 //     ([nbfrag][64 lanes][16 B], lane-linear -> conflict-free ds_read_b128);

@@ -3,10 +3,9 @@
 // Assignment is the tile kernel in top-1 / squared-L2 mode (lvs_flat_search_keys with k = 1, or the certified one-pass
 // lvs_nearest_hi).  This file holds everything else of an iteration, all of it on the device so that the host only
 // enqueues launches:
-//   * lvs_kmeans_accumulate(_keys): rows are bucketed by centroid with a STABLE counting sort on the centroid ids
-//     (per-chunk histogram in LDS -> exclusive scan -> in-order scatter; hand-written - round 2 used rocPRIM's radix
-//     sort), then every (centroid, 512-dim chunk) is reduced by one wave that walks its bucket in row order - the
-//     accumulation order of faiss compute_centroids, so results are reproducible run to run;
+//   * lvs_kmeans_accumulate(_keys): rows are bucketed by centroid with the STABLE bucket sort of lvs_count_sort.hip, then
+//     every (centroid, 512-dim chunk) is reduced by one wave that walks its bucket in row order - the accumulation order
+//     of faiss compute_centroids, so results are reproducible run to run;
 //   * lvs_kmeans_objective: faiss's objective (sum of the assignment distances) from the sums the update needs anyway;
 //   * lvs_kmeans_update_centroids: centroid division, faiss's empty-cluster split (std::mt19937 replayed by one device
 //     thread: same draws, same decisions as faiss split_clusters), repacking of the centroids as fp16 hi|lo rows and the
@@ -18,170 +17,10 @@
 #include <vector>
 
 #include "lvs_common.h"
+#include "lvs_count_sort.h"
 #include "lvs_tile.h"
 
 namespace {
-
-// ---- stable counting sort of the rows by centroid id -----------------------------------------------------------------
-// bins = k + 1 (the last one collects assignments outside [0, k): ignored rows).  A launch works on chunks of KM_CHUNK
-// consecutive rows, one workgroup each:
-//   km_count_kernel    counts[bin][chunk] = rows of the chunk that go to `bin`          (histogram in LDS)
-//   km_scan*_kernel    exclusive scan over counts in (bin-major, chunk-minor) order = first output position of every
-//                      (bin, chunk) run; offsets[c] = start of bucket c, c = 0 .. k
-//   km_scatter_kernel  rows_out[position] = row, in row order inside a chunk (waves of a tile take turns, lanes rank
-//                      themselves among the lanes with the same bin by ballots over the bin's bits)
-// Rows keep their order inside a bucket, which is what makes the centroid sums independent of the launch shape.
-constexpr int KM_CHUNK = 8192;
-constexpr int KM_SCAN_SEG = 2048;   // entries per workgroup of the scan
-constexpr int KM_MAX_BINS = 24576;  // (k + 1) * 4 B of LDS per workgroup; larger k sorts by two digits
-
-template <typename KeyT>
-__device__ inline uint32_t km_bin_of(KeyT v, long long id_offset, int k);
-template <>
-__device__ inline uint32_t km_bin_of<long long>(long long c, long long, int k) {
-    return (c < 0 || c >= k) ? (uint32_t)k : (uint32_t)c;
-}
-template <>
-__device__ inline uint32_t km_bin_of<u64>(u64 key, long long id_offset, int k) {  // a result key: id in the low word
-    if (key == 0) return (uint32_t)k;
-    const long long c = (long long)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) - id_offset;
-    return (c < 0 || c >= k) ? (uint32_t)k : (uint32_t)c;
-}
-
-// digit of a row: ((bin >> shift) & mask); rows are read through `order` (nullable: identity) so that a second pass can
-// sort the output of the first
-template <typename KeyT>
-__global__ __launch_bounds__(256) void km_count_kernel(const KeyT* __restrict__ assign, const uint32_t* __restrict__ order,
-                                                       long long n, int k, long long id_offset, int shift, uint32_t mask,
-                                                       int nbins, int nchunks, uint32_t* __restrict__ counts) {
-    extern __shared__ uint32_t km_hist[];
-    for (int b = threadIdx.x; b < nbins; b += 256) km_hist[b] = 0;
-    __syncthreads();
-    const long long r0 = (long long)blockIdx.x * KM_CHUNK;
-    const long long r1 = r0 + KM_CHUNK < n ? r0 + KM_CHUNK : n;
-    for (long long i = r0 + threadIdx.x; i < r1; i += 256) {
-        const long long row = order ? (long long)order[i] : i;
-        atomicAdd(&km_hist[(km_bin_of<KeyT>(assign[row], id_offset, k) >> shift) & mask], 1u);
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < nbins; b += 256) counts[(long long)b * nchunks + blockIdx.x] = km_hist[b];
-}
-
-// exclusive scan, three launches: per-segment scan + segment totals, scan of the totals (one workgroup), add
-__global__ __launch_bounds__(256) void km_scan1_kernel(uint32_t* __restrict__ v, long long total, uint32_t* __restrict__ seg_sum) {
-    __shared__ uint32_t part[256];
-    const long long base = (long long)blockIdx.x * KM_SCAN_SEG + (long long)threadIdx.x * (KM_SCAN_SEG / 256);
-    uint32_t loc[KM_SCAN_SEG / 256], sum = 0;
-#pragma unroll
-    for (int i = 0; i < KM_SCAN_SEG / 256; ++i) {
-        loc[i] = base + i < total ? v[base + i] : 0u;
-        sum += loc[i];
-    }
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
-        const uint32_t add = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;  // exclusive prefix of this thread inside the segment
-#pragma unroll
-    for (int i = 0; i < KM_SCAN_SEG / 256; ++i) {
-        if (base + i < total) v[base + i] = run;
-        run += loc[i];
-    }
-    if (threadIdx.x == 255) seg_sum[blockIdx.x] = part[255];
-}
-__global__ __launch_bounds__(256) void km_scan2_kernel(uint32_t* __restrict__ seg_sum, int nseg) {
-    __shared__ uint32_t part[256];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < nseg; s0 += 256) {
-        const int i = s0 + threadIdx.x;
-        const uint32_t mine = i < nseg ? seg_sum[i] : 0u;
-        part[threadIdx.x] = mine;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const uint32_t add = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nseg) seg_sum[i] = carry + part[threadIdx.x] - mine;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += part[255];
-        __syncthreads();
-    }
-}
-// v += its segment's offset; offsets[b] = v[b * nchunks] for b = 0 .. nbuckets (start of every bucket; written only when
-// `offsets` is given - the last digit pass)
-__global__ __launch_bounds__(256) void km_scan3_kernel(uint32_t* __restrict__ v, long long total,
-                                                       const uint32_t* __restrict__ seg_sum, int nchunks,
-                                                       uint32_t* __restrict__ offsets, int nbuckets) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < total) {
-        const uint32_t val = v[i] + seg_sum[i / KM_SCAN_SEG];
-        v[i] = val;
-        if (offsets && i % nchunks == 0 && i / nchunks <= nbuckets) offsets[i / nchunks] = val;
-    }
-}
-
-// bucket boundaries from the SORTED rows (two-digit sorts only): offsets[c] = first position whose bin is >= c, c = 0..k
-// (no atomics: position i writes the offsets of every bucket that starts there; k + 1 writes in total)
-template <typename KeyT>
-__global__ __launch_bounds__(256) void km_bounds_kernel(const KeyT* __restrict__ assign, const uint32_t* __restrict__ rows,
-                                                        long long n, int k, long long id_offset,
-                                                        uint32_t* __restrict__ offsets) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    const long long lo = i == 0 ? 0 : (long long)km_bin_of<KeyT>(assign[rows[i - 1]], id_offset, k) + 1;
-    const long long hi = i == n ? (long long)k : (long long)km_bin_of<KeyT>(assign[rows[i]], id_offset, k);
-    for (long long c = lo; c <= hi && c <= k; ++c) offsets[c] = (uint32_t)i;
-}
-
-template <typename KeyT>
-__global__ __launch_bounds__(256) void km_scatter_kernel(const KeyT* __restrict__ assign, const uint32_t* __restrict__ order,
-                                                         long long n, int k, long long id_offset, int shift, uint32_t mask,
-                                                         int nbins, int nbits, int nchunks,
-                                                         const uint32_t* __restrict__ counts, uint32_t* __restrict__ rows_out) {
-    extern __shared__ uint32_t km_pos[];  // next output position of every bin for this chunk
-    for (int b = threadIdx.x; b < nbins; b += 256) km_pos[b] = counts[(long long)b * nchunks + blockIdx.x];
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long r0 = (long long)blockIdx.x * KM_CHUNK;
-    const long long r1 = r0 + KM_CHUNK < n ? r0 + KM_CHUNK : n;
-    for (long long t0 = r0; t0 < r1; t0 += 256) {
-        const long long i = t0 + threadIdx.x;
-        const bool live = i < r1;
-        uint32_t row = 0, bin = 0;
-        if (live) {
-            row = order ? order[i] : (uint32_t)i;
-            bin = (km_bin_of<KeyT>(assign[row], id_offset, k) >> shift) & mask;
-        }
-        // lanes of this wave holding the same bin (dead lanes match nobody)
-        u64 peers = __builtin_amdgcn_ballot_w64(live);
-        for (int b = 0; b < nbits; ++b) {
-            const u64 m = __builtin_amdgcn_ballot_w64(live && ((bin >> b) & 1u));
-            peers &= ((bin >> b) & 1u) ? m : ~m;
-        }
-        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-        const int cnt = __popcll(peers);
-        uint32_t base = 0;
-        for (int w = 0; w < 4; ++w) {  // waves take turns: rows of wave w come before those of wave w + 1
-            if (wave == w && live && rank == 0) {
-                base = km_pos[bin];
-                km_pos[bin] = base + (uint32_t)cnt;
-            }
-            __syncthreads();
-        }
-        // the leader's base -> its peers
-        const int leader = live ? __ffsll((long long)peers) - 1 : lane;
-        base = __shfl(base, leader, 64);
-        if (live) rows_out[base + (uint32_t)rank] = row;
-    }
-}
 
 // grid = (k, ceil(dpad / (64 * DPL))), one wave per workgroup: a lane owns DPL consecutive dimensions (8, 4 or 2: 16-, 8- or
 // 4-byte loads) of centroid blockIdx.x and walks the bucket in row order, U rows in flight at a time.  Per dimension the
@@ -798,110 +637,20 @@ extern "C" int32_t lvs_unpack_rows(const void* src, int32_t d, int32_t pack_mode
 }
 
 namespace {
-int km_bits(int nbins) {
-    int b = 1;
-    while ((1 << b) < nbins) ++b;
-    return b;
-}
-struct KmSortPlan {
-    int nchunks, passes, nbins[2], shift[2];
-    uint32_t mask[2];
-    int64_t off_counts, off_seg, off_rows_a, off_rows_b, off_offs, total;
-};
-bool km_sort_plan(int64_t n, int32_t k, KmSortPlan& p) {
-    if (n < 0 || k <= 0 || n >= 0xFFFFFFFFll) return false;
-    p.nchunks = (int)lvs_ceil_div(n > 0 ? n : 1, KM_CHUNK);
-    if (k + 1 <= KM_MAX_BINS) {
-        p.passes = 1;
-        p.nbins[0] = k + 1;
-        p.shift[0] = 0;
-        p.mask[0] = 0xFFFFFFFFu;
-        p.nbins[1] = 0;
-        p.shift[1] = 0;
-        p.mask[1] = 0;
-    } else {  // two stable passes: low 12 bits, then the rest
-        p.passes = 2;
-        p.nbins[0] = 4096;
-        p.shift[0] = 0;
-        p.mask[0] = 4095u;
-        p.nbins[1] = (k >> 12) + 1;
-        p.shift[1] = 12;
-        p.mask[1] = 0xFFFFFFFFu;
-        if (p.nbins[1] > KM_MAX_BINS) return false;  // k >= 2^26.5: not a k-means anyone runs
-    }
-    const int64_t maxbins = p.nbins[0] > p.nbins[1] ? p.nbins[0] : p.nbins[1];
-    int64_t off = 0;
-    p.off_counts = off;
-    off += lvs_round_up(maxbins * p.nchunks * 4, 256);
-    p.off_seg = off;
-    off += lvs_round_up(lvs_ceil_div(maxbins * p.nchunks, KM_SCAN_SEG) * 4 + 4, 256);
-    p.off_rows_a = off;
-    off += lvs_round_up(n * 4, 256);
-    p.off_rows_b = off;
-    off += p.passes > 1 ? lvs_round_up(n * 4, 256) : 0;
-    p.off_offs = off;
-    off += lvs_round_up((int64_t)(k + 2) * 4, 256);
-    p.total = off;
-    return true;
-}
-
-// rows bucketed by centroid: *rows_out [n] = row numbers, bucket after bucket, ascending inside a bucket; *offs_out [k + 1]
-template <typename KeyT>
-int32_t km_bucket_rows(const KeyT* assign, int64_t n, int32_t k, int64_t id_offset, const KmSortPlan& p, char* w,
-                       hipStream_t st, const uint32_t** rows_out, const uint32_t** offs_out) {
-    uint32_t* counts = (uint32_t*)(w + p.off_counts);
-    uint32_t* seg = (uint32_t*)(w + p.off_seg);
-    uint32_t* rows[2] = {(uint32_t*)(w + p.off_rows_a), (uint32_t*)(w + p.off_rows_b)};
-    uint32_t* offs = (uint32_t*)(w + p.off_offs);
-    const uint32_t* order = nullptr;
-    // a pass may use KM_MAX_BINS counters: > 64 KB of dynamic LDS needs the attribute
-    LVS_HIP_CHECK(lvs_arm_lds<km_count_kernel<KeyT>>((size_t)KM_MAX_BINS * 4));
-    LVS_HIP_CHECK(lvs_arm_lds<km_scatter_kernel<KeyT>>((size_t)KM_MAX_BINS * 4));
-    for (int ps = 0; ps < p.passes; ++ps) {
-        const int nbins = p.nbins[ps];
-        const size_t lds = (size_t)nbins * 4;
-        const long long total = (long long)nbins * p.nchunks;
-        const int nseg = (int)lvs_ceil_div(total, KM_SCAN_SEG);
-        const bool last = ps + 1 == p.passes;
-        hipLaunchKernelGGL((km_count_kernel<KeyT>), dim3((unsigned)p.nchunks), dim3(256), lds, st, assign, order,
-                           (long long)n, k, (long long)id_offset, p.shift[ps], p.mask[ps], nbins, p.nchunks, counts);
-        hipLaunchKernelGGL(km_scan1_kernel, dim3((unsigned)nseg), dim3(256), 0, st, counts, total, seg);
-        hipLaunchKernelGGL(km_scan2_kernel, dim3(1), dim3(256), 0, st, seg, nseg);
-        hipLaunchKernelGGL(km_scan3_kernel, dim3((unsigned)lvs_ceil_div(total, 256)), dim3(256), 0, st, counts, total,
-                           (const uint32_t*)seg, p.nchunks, (p.passes == 1 && last) ? offs : (uint32_t*)nullptr, k);
-        hipLaunchKernelGGL((km_scatter_kernel<KeyT>), dim3((unsigned)p.nchunks), dim3(256), lds, st, assign, order,
-                           (long long)n, k, (long long)id_offset, p.shift[ps], p.mask[ps], nbins, km_bits(nbins),
-                           p.nchunks, (const uint32_t*)counts, rows[ps]);
-        order = rows[ps];
-    }
-    if (p.passes > 1)
-        hipLaunchKernelGGL((km_bounds_kernel<KeyT>), dim3((unsigned)lvs_ceil_div(n + 1, 256)), dim3(256), 0, st, assign,
-                           order, (long long)n, k, (long long)id_offset, offs);
-    LVS_HIP_CHECK(hipGetLastError());
-    *rows_out = order;
-    *offs_out = offs;
-    return LVS_OK;
-}
-
-template <typename KeyT>
-int32_t km_accumulate(const void* x, int64_t n, int32_t d, int32_t pack_mode, const KeyT* assign, int64_t id_offset,
-                      int32_t k, float* sums, float* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+// exactly one of keys (result keys, ids less id_offset) and assign is given
+int32_t km_accumulate(const void* x, int64_t n, int32_t d, int32_t pack_mode, const uint64_t* keys, const int64_t* assign,
+                      int64_t id_offset, int32_t k, float* sums, float* counts, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
     LVS_REQUIRE(n >= 0 && d > 0 && k > 0, "bad shape n=%lld d=%d k=%d", (long long)n, d, k);
     LVS_REQUIRE(pack_mode == LVS_PACK_F16 || pack_mode == LVS_PACK_SPLIT, "bad pack_mode");
     LVS_REQUIRE(n < 0xFFFFFFFFll, "n must be below 2^32");
     if (n == 0) return LVS_OK;
-    LVS_REQUIRE(x && assign && sums && counts && workspace, "NULL buffer");
-    KmSortPlan p;
-    LVS_REQUIRE(km_sort_plan(n, k, p), "k=%d is beyond the bucket sort", k);
-    if (workspace_bytes < p.total) {
-        lvs_set_error("workspace too small: need %lld bytes", (long long)p.total);
-        return LVS_ENOMEM;
-    }
-    LVS_DEVICE_GUARD(stream);
+    LVS_REQUIRE(x && (keys || assign) && sums && counts && workspace, "NULL buffer");
     hipStream_t st = (hipStream_t)stream;
     const uint32_t *rows = nullptr, *offs = nullptr;
-    const int32_t rc = km_bucket_rows<KeyT>(assign, n, k, id_offset, p, (char*)workspace, st, &rows, &offs);
+    const int32_t rc = lvs_bucket_positions(keys, assign, n, k, id_offset, workspace, workspace_bytes, st, &rows, &offs);
     if (rc != LVS_OK) return rc;
+    LVS_DEVICE_GUARD(stream);
     const int dpad = (int)lvs_round_up(d, LVS_BK);
     const long long ld = pack_mode == LVS_PACK_SPLIT ? 2 * dpad : dpad;
     // column slices per bucket: two dimensions per lane (128 columns per wave; d = 768: six waves per bucket).  Measured neutral
@@ -932,51 +681,18 @@ int32_t km_accumulate(const void* x, int64_t n, int32_t d, int32_t pack_mode, co
 }
 }  // namespace
 
-namespace {
-template <typename KeyT>
-int32_t km_bucket_positions(const KeyT* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes, hipStream_t st,
-                            const uint32_t** rows_out, const uint32_t** offs_out) {
-    KmSortPlan p;
-    LVS_REQUIRE(km_sort_plan(n, k, p), "k=%d is beyond the bucket sort", k);
-    if (ws_bytes < p.total) {
-        lvs_set_error("workspace too small: need %lld bytes", (long long)p.total);
-        return LVS_ENOMEM;
-    }
-    return km_bucket_rows<KeyT>(assign, n, k, 0, p, (char*)ws, st, rows_out, offs_out);
-}
-}  // namespace
-
-// the counting sort above for other callers (the IVF lists and the inversion of an IVF search's probes, lvs_capi.hip)
-int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k) {
-    KmSortPlan p;
-    if (!km_sort_plan(n, k, p)) return LVS_EINVAL;
-    return p.total;
-}
-int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
-                             hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out) {
-    LVS_REQUIRE(n > 0 && k > 0 && (keys == nullptr) != (assign == nullptr) && ws, "bad arguments");
-    if (keys) return km_bucket_positions<u64>((const u64*)keys, n, k, ws, ws_bytes, stream, rows_out, offs_out);
-    return km_bucket_positions<long long>((const long long*)assign, n, k, ws, ws_bytes, stream, rows_out, offs_out);
-}
-
-extern "C" int64_t lvs_kmeans_accumulate_workspace_bytes(int64_t n, int32_t k) {
-    KmSortPlan p;
-    if (!km_sort_plan(n, k, p)) return LVS_EINVAL;
-    return p.total;
-}
+extern "C" int64_t lvs_kmeans_accumulate_workspace_bytes(int64_t n, int32_t k) { return lvs_bucket_workspace_bytes(n, k); }
 
 extern "C" int32_t lvs_kmeans_accumulate(const void* x, int64_t n, int32_t d, int32_t pack_mode, const int64_t* assign,
                                          int32_t k, float* sums, float* counts, void* workspace, int64_t workspace_bytes,
                                          void* stream) {
-    return km_accumulate<long long>(x, n, d, pack_mode, (const long long*)assign, 0, k, sums, counts, workspace,
-                                    workspace_bytes, stream);
+    return km_accumulate(x, n, d, pack_mode, nullptr, assign, 0, k, sums, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t lvs_kmeans_accumulate_keys(const void* x, int64_t n, int32_t d, int32_t pack_mode, const uint64_t* keys,
                                               int64_t id_offset, int32_t k, float* sums, float* counts, void* workspace,
                                               int64_t workspace_bytes, void* stream) {
-    return km_accumulate<u64>(x, n, d, pack_mode, (const u64*)keys, id_offset, k, sums, counts, workspace, workspace_bytes,
-                              stream);
+    return km_accumulate(x, n, d, pack_mode, keys, nullptr, id_offset, k, sums, counts, workspace, workspace_bytes, stream);
 }
 
 // ---- host-side pieces of faiss Clustering (bit-exact: std::mt19937 is the generator faiss uses) -------------

@@ -7,18 +7,17 @@
 // (score best-first, id ascending) order of the 64-bit result keys.  A pass works on chunks of RS_CHUNK consecutive elements
 // of ONE row, one workgroup each:
 //   rs_count    counts[row][digit][chunk] (histogram in LDS)
-//   rs_scan1-3  exclusive scan over counts in exactly that order - which makes every row's output range start at row * nb
-//               and the digits descend inside it: the segmentation costs nothing
+//   scan        exclusive scan over counts in exactly that order (lvs_scan_excl_launch) - which makes every row's output
+//               range start at row * nb and the digits descend inside it: the segmentation costs nothing
 //   rs_scatter  element -> its position, in column order inside a chunk (lanes rank themselves among the lanes with the
 //               same digit by ballots over its bits, the waves of a tile take turns)
 // HBM-bound: a pass reads 8 B and writes 8 B per element (+ 4 B for the counting read).
 #include <cstring>
 
-#include "lvs_common.h"
+#include "lvs_count_sort.h"
 
 namespace {
 constexpr int RS_CHUNK = 4096;     // elements per workgroup and pass
-constexpr int RS_SCAN_SEG = 2048;  // counters per workgroup of the scan
 
 __device__ inline uint32_t rs_digit(uint32_t ord, int shift) { return 255u - ((ord >> shift) & 255u); }  // descending
 
@@ -52,60 +51,6 @@ __global__ __launch_bounds__(256) void rs_count_kernel(const float* __restrict__
     }
     __syncthreads();
     counts[(row * 256 + threadIdx.x) * cpr + piece] = hist[threadIdx.x];
-}
-
-// exclusive scan, three launches: per-segment scan + segment totals, scan of the totals (one workgroup), add
-__global__ __launch_bounds__(256) void rs_scan1_kernel(uint32_t* __restrict__ v, long long total, uint32_t* __restrict__ seg_sum) {
-    __shared__ uint32_t part[256];
-    const long long base = (long long)blockIdx.x * RS_SCAN_SEG + (long long)threadIdx.x * (RS_SCAN_SEG / 256);
-    uint32_t loc[RS_SCAN_SEG / 256], sum = 0;
-#pragma unroll
-    for (int i = 0; i < RS_SCAN_SEG / 256; ++i) {
-        loc[i] = base + i < total ? v[base + i] : 0u;
-        sum += loc[i];
-    }
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const uint32_t add = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
-#pragma unroll
-    for (int i = 0; i < RS_SCAN_SEG / 256; ++i) {
-        if (base + i < total) v[base + i] = run;
-        run += loc[i];
-    }
-    if (threadIdx.x == 255) seg_sum[blockIdx.x] = part[255];
-}
-__global__ __launch_bounds__(256) void rs_scan2_kernel(uint32_t* __restrict__ seg_sum, long long nseg) {
-    __shared__ uint32_t part[256];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (long long s0 = 0; s0 < nseg; s0 += 256) {
-        const long long i = s0 + threadIdx.x;
-        const uint32_t mine = i < nseg ? seg_sum[i] : 0u;
-        part[threadIdx.x] = mine;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const uint32_t add = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nseg) seg_sum[i] = carry + part[threadIdx.x] - mine;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += part[255];
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(256) void rs_scan3_kernel(uint32_t* __restrict__ v, long long total,
-                                                       const uint32_t* __restrict__ seg_sum) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < total) v[i] += seg_sum[i / RS_SCAN_SEG];
 }
 
 // LAST pass writes the result keys instead of the ping-pong buffers
@@ -164,7 +109,6 @@ struct RsPlan {
     int cpr;            // chunks per row
     long long nchunks;  // workgroups per pass
     long long ncount;   // counters = nq * 256 * cpr
-    long long nseg;     // scan segments
     int64_t off_counts, off_seg, off_k0, off_v0, off_k1, off_v1, total;
 };
 bool rs_plan(int64_t nq, int64_t nb, RsPlan& p) {
@@ -173,12 +117,11 @@ bool rs_plan(int64_t nq, int64_t nb, RsPlan& p) {
     p.nchunks = nq * p.cpr;
     if (p.nchunks >= 0x7FFFFFFFll) return false;
     p.ncount = nq * 256 * p.cpr;
-    p.nseg = lvs_ceil_div(p.ncount > 0 ? p.ncount : 1, RS_SCAN_SEG);
     int64_t off = 0;
     p.off_counts = off;
     off += lvs_round_up(p.ncount * 4, 256);
     p.off_seg = off;
-    off += lvs_round_up(p.nseg * 4 + 4, 256);
+    off += lvs_round_up(lvs_scan_scratch_bytes(p.ncount > 0 ? p.ncount : 1), 256);
     const int64_t buf = lvs_round_up(nq * nb * 4, 256);
     p.off_k0 = off;
     off += buf;
@@ -221,7 +164,6 @@ extern "C" int32_t lvs_sort_rows_desc(const float* scores, int64_t nq, int64_t n
     uint32_t* kb[2] = {(uint32_t*)(w + p.off_k0), (uint32_t*)(w + p.off_k1)};
     uint32_t* vb[2] = {(uint32_t*)(w + p.off_v0), (uint32_t*)(w + p.off_v1)};
     const dim3 grid((unsigned)p.nchunks), block(256);
-    const unsigned sgrid = (unsigned)p.nseg, agrid = (unsigned)lvs_ceil_div(p.ncount, 256);
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 8 * pass;
         const uint32_t *kin = pass ? kb[(pass - 1) & 1] : nullptr, *vin = pass ? vb[(pass - 1) & 1] : nullptr;
@@ -232,9 +174,7 @@ extern "C" int32_t lvs_sort_rows_desc(const float* scores, int64_t nq, int64_t n
         else
             hipLaunchKernelGGL((rs_count_kernel<false>), grid, block, 0, st, scores, (long long)ld, kin, (long long)nb, p.cpr,
                                shift, counts);
-        hipLaunchKernelGGL(rs_scan1_kernel, dim3(sgrid), block, 0, st, counts, (long long)p.ncount, seg);
-        hipLaunchKernelGGL(rs_scan2_kernel, dim3(1), block, 0, st, seg, (long long)p.nseg);
-        hipLaunchKernelGGL(rs_scan3_kernel, dim3(agrid), block, 0, st, counts, (long long)p.ncount, (const uint32_t*)seg);
+        lvs_scan_excl_launch(counts, (long long)p.ncount, seg, st);
         if (pass == 0)
             hipLaunchKernelGGL((rs_scatter_kernel<true, false>), grid, block, 0, st, scores, (long long)ld, kin, vin,
                                (long long)nb, p.cpr, shift, (const uint32_t*)counts, kout, vout, (u64*)nullptr,

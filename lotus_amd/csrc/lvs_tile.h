@@ -288,14 +288,6 @@ bool lvs_rj_fits(int64_t nq, int64_t nb, int dpad, int k, bool has_row_ids);
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // whole 32-row blocks only: the caller adds the tail
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // the same geometry, RANGE epilogue (inner product)
 
-// ---- lvs_kmeans.hip: the stable counting sort of the k-means update, for other callers (the IVF lists and the inversion of
-// an IVF search's probes).  Positions 0 .. n-1 grouped by the id in their result key (keys[i], id_offset 0) or by assign[i]
-// (exactly one of the two non-NULL), ascending inside a bucket; ids outside [0, k) are left out.  *rows_out [n] and
-// *offs_out [k + 1] point into the workspace. ----
-int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k);
-int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, void* ws, int64_t ws_bytes,
-                             hipStream_t stream, const uint32_t** rows_out, const uint32_t** offs_out);
-
 // ---- lvs_ivf.hip: the list scan of an IVF-Flat search.  A work item is one inverted list and a tile of up to 32 of the
 // (query, probe rank) pairs that probe it; the list's rows are gathered by number from the flat image. ----
 #define LVS_IVF_TILEQ 32     // pairs per work item (MFMA N)

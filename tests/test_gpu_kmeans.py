@@ -402,6 +402,44 @@ def test_counting_sort_two_digit_path_and_ignored_rows(hip_backend):
         assert np.array_equal(s2.cpu().numpy(), r2) and np.array_equal(c2.cpu().numpy(), np.bincount(a2, minlength=k2))
 
 
+def test_counting_sort_scan_carries_across_blocks_of_segments(hip_backend):
+    """One digit, 24 001 bins x 23 chunks (the last of one row) = 552 023 counters > 256 scan segments of 2 048: the scan's
+    one-workgroup middle kernel walks more than one block of 256 segment sums with its carry."""
+    be = hip_backend
+    rng = np.random.default_rng(12)
+    n, d, k = 8192 * 22 + 1, 8, 24_000
+    x = rng.standard_normal((n, d)).astype(np.float16)
+    assign = rng.integers(0, k, n).astype(np.int64)
+    sums, counts = be.kmeans_accumulate(be.pack(x, F16), be.to_device(assign), k)
+    ref = np.zeros((k, d), np.float32)
+    np.add.at(ref, assign, x.astype(np.float32))
+    assert np.array_equal(counts.cpu().numpy(), np.bincount(assign, minlength=k).astype(np.float32))
+    assert np.array_equal(sums.cpu().numpy(), ref)
+
+
+def test_counting_sort_two_digit_path_on_result_keys_with_an_id_offset(hip_backend):
+    """The bins of result keys (id in the low word, less id_offset) through two digit passes: empty keys, ids below the offset
+    and ids at or beyond offset + k are ignored; sums stay in row order (bit-identical)."""
+    be = hip_backend
+    rng = np.random.default_rng(13)
+    n, d, k, id_offset = 70_000, 16, 30_000, 7
+    x = rng.standard_normal((n, d)).astype(np.float16)
+    ids = rng.integers(0, k, n).astype(np.int64) + id_offset
+    where = rng.permutation(n)
+    ids[where[:300]] = rng.integers(0, id_offset, 300)                         # below the offset: ignored
+    ids[where[300:600]] = id_offset + k + rng.integers(0, 1000, 300)            # beyond the last centroid: ignored
+    keys = (rng.integers(1, 2**32, n).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - ids.astype(np.uint64))
+    keys[where[600:900]] = 0                                                    # empty slots: ignored
+    c = ids - id_offset
+    ok = (c >= 0) & (c < k) & (keys != 0)
+    assert (~ok).sum() == 900
+    sums, counts = be.kmeans_accumulate_keys(be.pack(x, F16), be.to_device(keys.view(np.int64)), k, id_offset)
+    ref = np.zeros((k, d), np.float32)
+    np.add.at(ref, c[ok], x.astype(np.float32)[ok])
+    assert np.array_equal(counts.cpu().numpy(), np.bincount(c[ok], minlength=k).astype(np.float32))
+    assert np.array_equal(sums.cpu().numpy(), ref)
+
+
 @pytest.mark.parametrize("mode", [F16, SPLIT])
 def test_distance_bounds_skip_rows_without_changing_any_result(hip_backend, mode):
     """Hamerly bounds (lvs_kmeans_bounds_step): rows whose nearest centroid provably did not change are not searched again.
