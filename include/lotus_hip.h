@@ -45,7 +45,9 @@ extern "C" {
                                 IVF-SQ8 codes and search (lvs_ivf_sq8_encode, lvs_ivf_sq8_search_workspace_bytes,
                                 lvs_ivf_sq8_search_keys, LVS_KERNEL_IVF_SQ8); IVF-PQ codes and search (lvs_ivf_pq_encode,
                                 lvs_ivf_pq_search_workspace_bytes, lvs_ivf_pq_search_keys, LVS_KERNEL_IVF_PQ); exact re-ranking
-                                of a first stage's candidates (lvs_refine_keys, LVS_KERNEL_REFINE) */
+                                of a first stage's candidates (lvs_refine_keys, LVS_KERNEL_REFINE); a row selector in the
+                                three list scans (lvs_ivf_search_keys_sel, lvs_ivf_sq8_search_keys_sel,
+                                lvs_ivf_pq_search_keys_sel) - the plain entries are these with sel_bits = NULL */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -448,6 +450,17 @@ int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const f
                             const void* xq, int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric,
                             int32_t nprobe, int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace,
                             int64_t workspace_bytes, void* stream);
+/* lvs_ivf_search_keys over the SELECTED rows only (faiss SearchParametersIVF(sel=IDSelectorBitmap)).  sel_bits: device array
+ * of ceil(nb / 32) uint32 words; row r of the flat image is selected iff (sel_bits[r >> 5] >> (r & 31)) & 1; bits at or past
+ * nb are never read as rows; NULL selects every row (lvs_ivf_search_keys is this call with NULL).  The result is the exact top
+ * k over (rows of the probed lists) x (selected rows): global row numbers, equal scores in ascending row order, key 0 past
+ * the selected rows of the probed lists.  The coarse step and the probes do not depend on the selector; the scan skips
+ * whole 32-row blocks without a selected row.  Same checks, same scratch (lvs_ivf_search_workspace_bytes). */
+int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq, const int64_t* offsets,
+                                const uint32_t* rows, const uint32_t* sel_bits, int32_t nlist, const void* centroids,
+                                int32_t c_pack, const float* c_norms_sq, const void* xq, int32_t xq_pack, int64_t nq,
+                                const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- IVF-SQ8: IVF-Flat's lists and coarse step, the rows scored from 8-bit codes of their residuals (faiss
  * "IVF<nlist>,SQ8": ScalarQuantizer QT_8bit, by_residual).  Per dimension j, with vmin / vdiff trained by the caller:
@@ -481,6 +494,16 @@ int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norm
                                 int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe,
                                 int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                 void* stream);
+/* lvs_ivf_sq8_search_keys over the selected rows only: sel_bits as in lvs_ivf_search_keys_sel (bits are indexed by ROW number,
+ * not by list position; NULL: every row).  The scan skips whole 16-row blocks without a selected row.  Same checks, same
+ * scratch (lvs_ivf_sq8_search_workspace_bytes). */
+int32_t lvs_ivf_sq8_search_keys_sel(const uint8_t* codes, const float* residual_norms_sq, const float* vmin, const float* vdiff,
+                                    const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits, int64_t nb,
+                                    int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                    const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
+                                    const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                    uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                    void* stream);
 
 /* ---- IVF-PQ: IVF-Flat's lists and coarse step, the rows scored from product-quantizer codes of their residuals (faiss
  * "IVF<nlist>,PQ<M>": ProductQuantizer with 8-bit codes, by_residual).  dsub = d / M (d % M == 0), codebooks [M][ksub][dsub]
@@ -517,6 +540,16 @@ int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const fl
                                int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe,
                                int32_t k, uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
                                void* stream);
+/* lvs_ivf_pq_search_keys over the selected rows only: sel_bits as in lvs_ivf_search_keys_sel (bits are indexed by ROW number,
+ * not by list position; NULL: every row).  The scan skips a wave's 64 positions when none of them is selected.  Same checks,
+ * same scratch (lvs_ivf_pq_search_workspace_bytes). */
+int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M, int32_t ksub,
+                                   const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits, int64_t nb,
+                                   int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                   const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
+                                   const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                   uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                   void* stream);
 
 /* ---- exact re-ranking of a search's candidates (faiss `IndexRefineFlat`, "IVF<nlist>,PQ<M>,Refine(Flat)"): the second
  * stage behind lvs_ivf_sq8_search_keys / lvs_ivf_pq_search_keys run at kc >= k.  cand_keys [nq][kc]: the first stage's keys;

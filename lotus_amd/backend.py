@@ -983,20 +983,32 @@ class HipBackend:
         shapes exactly."""
         return ivf_fits(d, k, mode)
 
+    def row_bitmap(self, ids, n: int):
+        """-> (device uint32 tensor [ceil(n / 32)], distinct ids): the row selector of the three ``sel=`` searches.  Row r
+        is selected iff bit ``r & 31`` of word ``r >> 5`` is set; bits at or past ``n`` are clear.  ``ids``: host int64 row
+        numbers in [0, n), any order, duplicates allowed (the count is of distinct rows).  Built on the host - a boolean mask
+        packed little-endian, 125 KB per million rows to upload, far less than the ids - so the count needs no device sync."""
+        mask = np.zeros(-(-int(n) // 32) * 32, dtype=bool)
+        mask[np.asarray(ids, dtype=np.int64).reshape(-1)] = True
+        words = np.packbits(mask, bitorder="little").view(np.uint32)  # (a little-endian host: byte 0 is bits 0-7 of word 0)
+        return self.to_device(words), int(mask.sum())
+
     def ivf_search(self, corpus: PackedRows, lists: IvfLists, queries: PackedRows, k: int, metric: int, nprobe: int,
-                   want_probe: bool = False):
+                   want_probe: bool = False, sel=None):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] list ids of the probes, best first): the exact
-        top k over the rows of each query's ``nprobe`` best lists (``lvs_ivf_search_keys``); key 0 past those rows."""
+        top k over the rows of each query's ``nprobe`` best lists (``lvs_ivf_search_keys``); key 0 past those rows.  ``sel``
+        (``row_bitmap``'s tensor): only the selected rows of those lists take part (``lvs_ivf_search_keys_sel``)."""
         cpk = lists.centroids
         head = (_ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets), _ptr(lists.rows), lists.nlist,
                 _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms))
-        return self._ivf_search("lvs_ivf_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe)
+        return self._ivf_search("lvs_ivf_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe, sel, 6)
 
     def _ivf_search(self, entry: str, ws_extra: tuple, head: tuple, corpus: PackedRows, lists: IvfLists, queries: PackedRows,
-                    k: int, metric: int, nprobe: int, want_probe: bool):
+                    k: int, metric: int, nprobe: int, want_probe: bool, sel=None, sel_at: int = 0):
         """What the three IVF searches share: ``<entry>_keys`` with its scratch from ``<entry>_workspace_bytes``.
         ``ws_extra``: the workspace function's arguments between d and k (PQ: M); ``head``: the entry point's arguments
-        ahead of the queries."""
+        ahead of the queries.  ``sel``: a row selector - the call goes to ``<entry>_keys_sel``, whose ``sel_bits`` follows
+        ``rows``, argument ``sel_at`` of ``head``."""
         torch = self.torch
         if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
             raise ValueError("squared L2 needs both operands packed with the same scale exponent")
@@ -1008,7 +1020,12 @@ class HipBackend:
             m = f" M={ws_extra[0]}" if ws_extra else ""
             raise LotusHipError(f"{entry}_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe}{m} k={k}")
         ws = self._workspace(need)
-        self._c(entry + "_keys", *head, _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
+        name = entry + "_keys"
+        if sel is not None:
+            if int(sel.numel()) != -(-corpus.n // 32):
+                raise ValueError(f"the row selector has {int(sel.numel())} words for {corpus.n} rows")
+            name, head = name + "_sel", head[:sel_at] + (_ptr(sel),) + head[sel_at:]
+        self._c(name, *head, _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
                 int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
         return (keys, probe) if want_probe else keys
 
@@ -1070,13 +1087,13 @@ class HipBackend:
         return ivf_sq8_fits(d, k, mode)
 
     def ivf_sq8_search(self, corpus: PackedRows, lists: IvfLists, sq8: IvfSq8Lists, queries: PackedRows, k: int, metric: int,
-                       nprobe: int, want_probe: bool = False):
+                       nprobe: int, want_probe: bool = False, sel=None):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
-        query's ``nprobe`` best lists (``lvs_ivf_sq8_search_keys``); key 0 past those rows."""
+        query's ``nprobe`` best lists (``lvs_ivf_sq8_search_keys``); key 0 past those rows.  ``sel``: as ``ivf_search``."""
         cpk = lists.centroids
         head = (_ptr(sq8.codes), _ptr(sq8.rnorm), _ptr(sq8.vmin), _ptr(sq8.vdiff), _ptr(lists.offsets), _ptr(lists.rows), corpus.n,
                 lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(sq8.centroids))
-        return self._ivf_search("lvs_ivf_sq8_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe)
+        return self._ivf_search("lvs_ivf_sq8_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe, sel, 6)
 
     # ---- IVF-PQ ----
     PQ_SEED = 1234          # faiss's ClusteringParameters default, the same for every subspace
@@ -1139,13 +1156,14 @@ class HipBackend:
         return ivf_pq_fits(d, M, k, mode)
 
     def ivf_pq_search(self, corpus: PackedRows, lists: IvfLists, pq: IvfPqLists, queries: PackedRows, k: int, metric: int,
-                      nprobe: int, want_probe: bool = False):
+                      nprobe: int, want_probe: bool = False, sel=None):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
-        query's ``nprobe`` best lists (``lvs_ivf_pq_search_keys``); key 0 past those rows."""
+        query's ``nprobe`` best lists (``lvs_ivf_pq_search_keys``); key 0 past those rows.  ``sel``: as ``ivf_search``."""
         cpk = lists.centroids
         head = (_ptr(pq.codes), _ptr(pq.beta), _ptr(pq.codebooks), pq.M, pq.ksub, _ptr(lists.offsets), _ptr(lists.rows), corpus.n,
                 lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(pq.centroids))
-        return self._ivf_search("lvs_ivf_pq_search", (pq.M,), head, corpus, lists, queries, k, metric, nprobe, want_probe)
+        return self._ivf_search("lvs_ivf_pq_search", (pq.M,), head, corpus, lists, queries, k, metric, nprobe, want_probe, sel,
+                                7)
 
     # ---- exact re-ranking ("...,Refine(Flat)") ----
     REFINE_MAX_CANDIDATES = 64  # candidate slots per query of lvs_refine_keys: one per lane of the query's wave

@@ -2143,12 +2143,14 @@ struct IvfSearch {
     void* workspace;
     int64_t workspace_bytes;
     void* stream;
+    const uint32_t* sel_bits;  // the *_sel entry points' row selector for the mode's scan (NULL: every row)
 };
 
 // The host driver of the three searches: plan the scratch, then per chunk of queries the coarse step (the nprobe best
 // centroids of every query under the index's metric), the probe ids, the mode's scan and the merge of its parts.
 // scan(L, w, q0, cn, xq_c, qn_c, coarse, parts, nparts) launches the scan of queries [q0, q0 + cn) under its own
 // ScopedKernelTimer (q0 > 0: a continuation) and may lower nparts, the lists per query that it fills (nprobe on entry).
+// A row selector (s.sel_bits) concerns the scan alone: the coarse step, the pair grouping, the tiling and the merge see none.
 template <class Scan>
 int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, Scan scan) {
     IvfLayout L;
@@ -2260,12 +2262,12 @@ extern "C" int64_t lvs_ivf_search_workspace_bytes(int64_t nq, int32_t nlist, int
     return ivf_workspace_bytes(nq, nlist, nprobe, d, 1, k, pack, ivf_fits(d, k, pack), 0, true);
 }
 
-extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
-                                       const int64_t* offsets, const uint32_t* rows, int32_t nlist, const void* centroids,
-                                       int32_t c_pack, const float* c_norms_sq, const void* xq, int32_t xq_pack, int64_t nq,
-                                       const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
-                                       uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
-                                       void* stream) {
+extern "C" int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
+                                           const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits,
+                                           int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                           const void* xq, int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d,
+                                           int32_t metric, int32_t nprobe, int32_t k, uint64_t* out_keys, int32_t* out_probe,
+                                           void* workspace, int64_t workspace_bytes, void* stream) {
     const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, 1, 1, nprobe, k, xb_pack, xq_pack, c_pack);
     if (ok != LVS_OK) return ok;
     if (nq == 0) return LVS_OK;
@@ -2299,7 +2301,7 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
         a.seg_b[i] = p.seg_q[i] == 0 ? 0 : a.jper;
     }
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
-                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream};
+                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
     return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
                                              const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
@@ -2311,10 +2313,22 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
         a.xq = xq_c;
         a.qn = qn_c;
         a.nq = (int)cn;
+        a.sel = s.sel_bits;
         ScopedKernelTimer timer(st, LVS_KERNEL_IVF, q0 > 0);
         LVS_HIP_CHECK(lvs_ivf_scan_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
         return LVS_OK;
     });
+}
+
+extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
+                                       const int64_t* offsets, const uint32_t* rows, int32_t nlist, const void* centroids,
+                                       int32_t c_pack, const float* c_norms_sq, const void* xq, int32_t xq_pack, int64_t nq,
+                                       const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                       uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                       void* stream) {
+    return lvs_ivf_search_keys_sel(xb, xb_pack, nb, xb_norms_sq, offsets, rows, nullptr, nlist, centroids, c_pack, c_norms_sq, xq,
+                                   xq_pack, nq, xq_norms_sq, d, metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes,
+                                   stream);
 }
 
 // ---- IVF-SQ8: the rows scored from 8-bit residual codes
@@ -2338,13 +2352,13 @@ extern "C" int64_t lvs_ivf_sq8_search_workspace_bytes(int64_t nq, int32_t nlist,
     return ivf_workspace_bytes(nq, nlist, nprobe, d, 1, k, pack, ivf_sq8_fits(d, k), 0, true);
 }
 
-extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norms_sq, const float* vmin,
-                                           const float* vdiff, const int64_t* offsets, const uint32_t* rows, int64_t nb,
-                                           int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
-                                           const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
-                                           const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
-                                           uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
-                                           void* stream) {
+extern "C" int32_t lvs_ivf_sq8_search_keys_sel(const uint8_t* codes, const float* residual_norms_sq, const float* vmin,
+                                               const float* vdiff, const int64_t* offsets, const uint32_t* rows,
+                                               const uint32_t* sel_bits, int64_t nb, int32_t nlist, const void* centroids,
+                                               int32_t c_pack, const float* c_norms_sq, const float* centroids_f32,
+                                               const void* xq, int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d,
+                                               int32_t metric, int32_t nprobe, int32_t k, uint64_t* out_keys,
+                                               int32_t* out_probe, void* workspace, int64_t workspace_bytes, void* stream) {
     const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, 1, 1, nprobe, k, LVS_PACK_F16, xq_pack, c_pack);
     if (ok != LVS_OK) return ok;
     if (nq == 0) return LVS_OK;
@@ -2375,7 +2389,7 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
     a.ldq = a.qsplit ? 2 * a.qdpad : a.qdpad;
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
-                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream};
+                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
     return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
                                              const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
@@ -2386,10 +2400,23 @@ extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* re
         a.out = parts;
         a.xq = xq_c;
         a.nq = (int)cn;
+        a.sel = s.sel_bits;
         ScopedKernelTimer timer(st, LVS_KERNEL_IVF_SQ8, q0 > 0);
         LVS_HIP_CHECK(lvs_ivf_sq8_scan_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
         return LVS_OK;
     });
+}
+
+extern "C" int32_t lvs_ivf_sq8_search_keys(const uint8_t* codes, const float* residual_norms_sq, const float* vmin,
+                                           const float* vdiff, const int64_t* offsets, const uint32_t* rows, int64_t nb,
+                                           int32_t nlist, const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                           const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
+                                           const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                           uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+    return lvs_ivf_sq8_search_keys_sel(codes, residual_norms_sq, vmin, vdiff, offsets, rows, nullptr, nb, nlist, centroids, c_pack,
+                                       c_norms_sq, centroids_f32, xq, xq_pack, nq, xq_norms_sq, d, metric, nprobe, k, out_keys,
+                                       out_probe, workspace, workspace_bytes, stream);
 }
 
 // ---- IVF-PQ: the rows scored from product-quantizer codes
@@ -2413,13 +2440,13 @@ extern "C" int64_t lvs_ivf_pq_search_workspace_bytes(int64_t nq, int32_t nlist, 
     return ivf_workspace_bytes(nq, nlist, nprobe, d, M, k, pack, ivf_pq_fits(M, k), (int64_t)M * LVS_PQ_KSUB * 4, false);
 }
 
-extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M,
-                                          int32_t ksub, const int64_t* offsets, const uint32_t* rows, int64_t nb, int32_t nlist,
-                                          const void* centroids, int32_t c_pack, const float* c_norms_sq,
-                                          const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
-                                          const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
-                                          uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
-                                          void* stream) {
+extern "C" int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M,
+                                              int32_t ksub, const int64_t* offsets, const uint32_t* rows,
+                                              const uint32_t* sel_bits, int64_t nb, int32_t nlist, const void* centroids,
+                                              int32_t c_pack, const float* c_norms_sq, const float* centroids_f32,
+                                              const void* xq, int32_t xq_pack, int64_t nq, const float* xq_norms_sq, int32_t d,
+                                              int32_t metric, int32_t nprobe, int32_t k, uint64_t* out_keys, int32_t* out_probe,
+                                              void* workspace, int64_t workspace_bytes, void* stream) {
     const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, M, ksub, nprobe, k, LVS_PACK_F16, xq_pack, c_pack);
     if (ok != LVS_OK) return ok;
     if (nq == 0) return LVS_OK;
@@ -2449,7 +2476,7 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
     a.ldq = a.qsplit ? 2 * a.qdpad : a.qdpad;
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
-                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream};
+                         metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
     // the queries' tables, then the query-major scan: one part per range of probes
     return ivf_search_chunks(s, (int64_t)M * LVS_PQ_KSUB * 4, false,
                              [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
@@ -2463,11 +2490,24 @@ extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* bet
         a.out = parts;
         a.xq = xq_c;
         a.nq = (int)cn;
+        a.sel = s.sel_bits;
         ScopedKernelTimer timer(st, LVS_KERNEL_IVF_PQ, q0 > 0);
         LVS_HIP_CHECK(lvs_ivf_pq_lut_launch(xq_c, a.ldq, a.qsplit, a.qdpad, cn, d, M, ksub, codebooks, lut, st));
         LVS_HIP_CHECK(lvs_ivf_pq_scan_launch(a, st));
         return LVS_OK;
     });
+}
+
+extern "C" int32_t lvs_ivf_pq_search_keys(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M,
+                                          int32_t ksub, const int64_t* offsets, const uint32_t* rows, int64_t nb, int32_t nlist,
+                                          const void* centroids, int32_t c_pack, const float* c_norms_sq,
+                                          const float* centroids_f32, const void* xq, int32_t xq_pack, int64_t nq,
+                                          const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
+                                          uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+    return lvs_ivf_pq_search_keys_sel(codes, beta, codebooks, M, ksub, offsets, rows, nullptr, nb, nlist, centroids, c_pack,
+                                      c_norms_sq, centroids_f32, xq, xq_pack, nq, xq_norms_sq, d, metric, nprobe, k, out_keys,
+                                      out_probe, workspace, workspace_bytes, stream);
 }
 
 // ---- exact re-ranking of a first stage's candidates ("...,Refine(Flat)"): every check ahead of the first device call

@@ -26,7 +26,10 @@
 
 namespace {
 
-template <int U>
+// SEL: only the rows whose bit is set in a.sel (bit r & 31 of word r >> 5 for row r of the flat image) take part.  A wave
+// looks its 32 rows' bits up right after their numbers and skips the block before any row data when none is selected; the
+// 32-bit ballot of (inside the list and selected), indexed by the block row, masks the epilogue in place of the `< len` test.
+template <int U, bool SEL>
 __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const LvsIvfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TQ = LVS_IVF_TILEQ;
@@ -76,6 +79,12 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
         int rr = blk * 32 + (lane & 31);
         if (rr > len - 1) rr = len - 1;
         const uint32_t rid = a.rows[r0 + rr];
+        uint32_t selm = 0;  // SEL: bit j = block row j is inside the list and selected (lanes j and j + 32 hold the same row)
+        if constexpr (SEL) {
+            const bool on = blk * 32 + (lane & 31) < len && ((a.sel[rid >> 5] >> (rid & 31)) & 1u);
+            selm = (uint32_t)__ballot(on);
+            if (selm == 0) continue;  // wave-uniform; the block loop has no workgroup barrier
+        }
         const float bnv = a.metric == LVS_METRIC_L2 ? a.bn[rid] : 0.f;
         const _Float16* ap = xb + (long long)rid * a.ldb + (lane >> 5) * 8;
         // fragments f = seg * jper + jj; U divides jper, so a batch of U never crosses a K segment.  The batch after the
@@ -104,6 +113,7 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
         }
         // ---- block epilogue: lane holds pair slot qs, block rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
         const int brow0 = blk * 32 + 4 * (lane >> 5);
+        const uint32_t selw = selm >> (4 * (lane >> 5));  // SEL: bit j = this lane's block row 4 (lane >> 5) + j takes part
         if (a.metric == LVS_METRIC_L2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -117,13 +127,18 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
         }
         float best = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) best = brow0 + (r & 3) + 8 * (r >> 2) < len ? fmaxf(best, acc[r]) : best;
+        for (int r = 0; r < 16; ++r) {
+            if constexpr (SEL) best = (selw >> ((r & 3) + 8 * (r >> 2))) & 1u ? fmaxf(best, acc[r]) : best;
+            else best = brow0 + (r & 3) + 8 * (r >> 2) < len ? fmaxf(best, acc[r]) : best;
+        }
         const bool th = qvalid && best >= tauf;
         if (!__any(th)) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const uint32_t id = (uint32_t)__shfl((int)rid, (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), 64);
-            const bool pending = th && brow0 + (r & 3) + 8 * (r >> 2) < len && acc[r] >= tauf;
+            bool pending;
+            if constexpr (SEL) pending = th && ((selw >> ((r & 3) + 8 * (r >> 2))) & 1u) && acc[r] >= tauf;
+            else pending = th && brow0 + (r & 3) + 8 * (r >> 2) < len && acc[r] >= tauf;
             const u64 key = pending ? lvs_pack_key(acc[r], id) : 0ull;
             lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
@@ -186,10 +201,10 @@ __global__ __launch_bounds__(256) void lvs_ivf_offsets_kernel(const uint32_t* __
     if (i <= n) out[i] = (int64_t)offs[i];
 }
 
-template <int U>
+template <int U, bool SEL>
 hipError_t ivf_scan_launch_u(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream) {
-    return lvs_launch_lds<lvs_ivf_scan_kernel<U>>(dim3((unsigned)max_items), dim3(LVS_IVF_WAVES * 64),
-                                                  lvs_ivf_lds_bytes(a.nbfrag, a.kcap), stream, a);
+    return lvs_launch_lds<lvs_ivf_scan_kernel<U, SEL>>(dim3((unsigned)max_items), dim3(LVS_IVF_WAVES * 64),
+                                                       lvs_ivf_lds_bytes(a.nbfrag, a.kcap), stream, a);
 }
 
 }  // namespace
@@ -210,8 +225,9 @@ hipError_t lvs_ivf_tiles_launch(const uint32_t* pair_offs, int nlist, uint32_t* 
 hipError_t lvs_ivf_scan_launch(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream) {
     if (a.jper % 4 != 0 || a.k < 1 || a.k > a.kcap || a.kcap > 64 || a.nseg < 1 || a.nseg > 3) return hipErrorInvalidValue;
     if (max_items <= 0) return hipSuccess;
-    if (a.jper % 8 == 0) return ivf_scan_launch_u<8>(a, max_items, stream);
-    return ivf_scan_launch_u<4>(a, max_items, stream);
+    if (a.sel) return a.jper % 8 == 0 ? ivf_scan_launch_u<8, true>(a, max_items, stream) : ivf_scan_launch_u<4, true>(a, max_items, stream);
+    if (a.jper % 8 == 0) return ivf_scan_launch_u<8, false>(a, max_items, stream);
+    return ivf_scan_launch_u<4, false>(a, max_items, stream);
 }
 
 hipError_t lvs_ivf_probe_ids_launch(const u64* keys, int64_t n, int32_t* out, hipStream_t stream) {

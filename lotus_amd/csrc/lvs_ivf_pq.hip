@@ -74,7 +74,10 @@ __global__ __launch_bounds__(256) void lvs_ivf_pq_lut_kernel(const _Float16* __r
         if (q0 + i < nq) lut[((long long)(q0 + i) * M + m) * PQ_KS + j] = j < ksub ? acc[i] : 0.f;
 }
 
-// ---- the list scan: workgroup (probe range, query)
+// ---- the list scan: workgroup (probe range, query).  SEL: only the rows whose bit is set in a.sel take part: a lane reads
+// its position's row number ahead of the table lookups, folds the bit into `valid`, and a wave skips its 64 positions when
+// none is valid
+template <bool SEL>
 __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIvfPqArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -130,12 +133,18 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
     float tauf = -INFINITY;
     for (int base = wave * 64; base < total; base += PQ_THREADS) {
         const int v = base + lane;
-        const bool valid = v < total;
+        bool valid = v < total;
         const int vv = valid ? v : total - 1;
         int p = 0;
         while (p + 1 < np && poff[p + 1] <= vv) ++p;  // the probe holding virtual row vv (empty probes are skipped)
         const long long pos = a.offsets[plist[p]] + (vv - poff[p]);
         const uint8_t* cp = a.codes + pos * ldc;
+        uint32_t rid = 0;
+        if constexpr (SEL) {
+            rid = a.rows[pos];
+            valid = valid && ((a.sel[rid >> 5] >> (rid & 31)) & 1u);
+            if (!__any(valid)) continue;  // wave-uniform; the position loop has no workgroup barrier
+        }
         // sum_m LUT[m][code_m], m = 0 .. M-1 in order; the next 16 code bytes are in flight while the current ones are looked up
         float s = 0.f;
         uint4 cur = *(const uint4*)cp, nxt = cur;
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(PQ_THREADS) void lvs_ivf_pq_scan_kernel(const LvsIv
             for (int b = 0; b < tail; ++b) s += lc[b * PQ_KS + ((w[b >> 2] >> (8 * (b & 3))) & 0xFF)];
         }
         const float score = l2 ? -fmaxf((cst[p] + a.beta[pos]) - 2.0f * s, 0.f) : cst[p] + s;
-        const uint32_t rid = a.rows[pos];
+        if constexpr (!SEL) rid = a.rows[pos];
         {
             const uint32_t lo = (uint32_t)(list[k - 1] >> 32);
             tauf = fmaxf(tauf, lvs_tau(lo));
@@ -316,6 +325,8 @@ hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream) {
         return hipErrorInvalidValue;
     if (a.nq <= 0) return hipSuccess;
     const int nranges = (a.nprobe + a.prange - 1) / a.prange;
-    return lvs_launch_lds<lvs_ivf_pq_scan_kernel>(dim3((unsigned)nranges, (unsigned)a.nq), dim3(PQ_THREADS),
-                                                  lvs_ivf_pq_lds_bytes(a.M, a.kcap), stream, a);
+    const dim3 grid((unsigned)nranges, (unsigned)a.nq), block(PQ_THREADS);
+    const size_t lds = lvs_ivf_pq_lds_bytes(a.M, a.kcap);
+    if (a.sel) return lvs_launch_lds<lvs_ivf_pq_scan_kernel<true>>(grid, block, lds, stream, a);
+    return lvs_launch_lds<lvs_ivf_pq_scan_kernel<false>>(grid, block, lds, stream, a);
 }

@@ -100,7 +100,10 @@ __device__ inline void sq8_codes_to_frags(const uint4 c, half8& s0, half8& s1) {
     s1 = __builtin_bit_cast(half8, b);
 }
 
-template <int U>
+// SEL: only the rows whose bit is set in a.sel take part, as in lvs_ivf_scan_kernel: a wave looks its 16 rows' bits up right
+// after their numbers, skips the block before any code load when none is selected, and the 16-bit ballot of (inside the
+// list and selected), indexed by the block row, masks the epilogue in place of the `< len` test.
+template <int U, bool SEL>
 __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const LvsIvfSq8Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -205,6 +208,12 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
         if (rr > len - 1) rr = len - 1;
         const long long pos = pos0 + rr;
         const uint32_t rid = a.rows[pos];
+        uint32_t selm = 0;  // SEL: bit j = block row j is inside the list and selected (lanes j, j + 16, ... hold the same row)
+        if constexpr (SEL) {
+            const bool on = blk * 16 + (lane & 15) < len && ((a.sel[rid >> 5] >> (rid & 31)) & 1u);
+            selm = (uint32_t)__ballot(on) & 0xFFFFu;
+            if (selm == 0) continue;  // wave-uniform; the block loop has no workgroup barrier
+        }
         const float rn = l2 ? a.rnorm[pos] : 0.f;
         const uint8_t* cp = a.codes + pos * ldc + (lane >> 4) * 16;
         uint4 cur[U], nxt[U];
@@ -231,6 +240,7 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
         }
         // ---- block epilogue: lane holds pair slot qs, block rows 4 (lane >> 4) + r
         const int brow0 = blk * 16 + 4 * (lane >> 4);
+        const uint32_t selw = selm >> (4 * (lane >> 4));  // SEL: bit r = this lane's block row 4 (lane >> 4) + r takes part
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float dot = ldexpf(acc[r], -eq);
@@ -247,13 +257,17 @@ __global__ __launch_bounds__(SQ8_THREADS) void lvs_ivf_sq8_scan_kernel(const Lvs
         }
         float best = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) best = brow0 + r < len ? fmaxf(best, acc[r]) : best;
+        for (int r = 0; r < 4; ++r) {
+            const bool in = SEL ? (selw >> r) & 1u : brow0 + r < len;
+            best = in ? fmaxf(best, acc[r]) : best;
+        }
         const bool th = qvalid && best >= tauf;
         if (!__any(th)) continue;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const uint32_t id = (uint32_t)__shfl((int)rid, 4 * (lane >> 4) + r, 64);
-            const bool pending = th && brow0 + r < len && acc[r] >= tauf;
+            const bool in = SEL ? (selw >> r) & 1u : brow0 + r < len;
+            const bool pending = th && in && acc[r] >= tauf;
             const u64 key = pending ? lvs_pack_key(acc[r], id) : 0ull;
             lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
@@ -304,8 +318,10 @@ __global__ __launch_bounds__(256) void lvs_ivf_sq8_encode_kernel(const _Float16*
 
 template <int U>
 hipError_t sq8_scan_launch_u(const LvsIvfSq8Args& a, int64_t max_items, hipStream_t stream) {
-    return lvs_launch_lds<lvs_ivf_sq8_scan_kernel<U>>(dim3((unsigned)(2 * max_items)), dim3(SQ8_THREADS),
-                                                      lvs_ivf_sq8_lds_bytes(a.ldc, a.kcap), stream, a);
+    const dim3 grid((unsigned)(2 * max_items)), block(SQ8_THREADS);
+    const size_t lds = lvs_ivf_sq8_lds_bytes(a.ldc, a.kcap);
+    if (a.sel) return lvs_launch_lds<lvs_ivf_sq8_scan_kernel<U, true>>(grid, block, lds, stream, a);
+    return lvs_launch_lds<lvs_ivf_sq8_scan_kernel<U, false>>(grid, block, lds, stream, a);
 }
 
 }  // namespace

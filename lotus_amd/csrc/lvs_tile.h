@@ -308,6 +308,7 @@ struct LvsIvfArgs {
     int nq, nlist, nprobe, k, metric;
     int jper, nseg, nbfrag, kcap;
     int seg_c[3], seg_b[3];
+    const uint32_t* sel;         // [ceil(nb / 32)] row selector, bit r & 31 of word r >> 5 = row r takes part; NULL: every row
 };
 size_t lvs_ivf_lds_bytes(int nbfrag, int kcap);
 int lvs_ivf_kcap(int k);
@@ -339,6 +340,7 @@ struct LvsIvfSq8Args {
     u64* out;                    // [nprobe][nq][k]
     long long ldq;
     int nq, nlist, nprobe, k, metric, d, ldc, qsplit, qdpad, kcap;
+    const uint32_t* sel;         // [ceil(nb / 32)] row selector over ROW numbers (not positions); NULL: every row
 };
 size_t lvs_ivf_sq8_lds_bytes(int ldc, int kcap);
 int lvs_ivf_sq8_ldc(int d);  // code bytes per row: d rounded up to a multiple of 64
@@ -365,6 +367,7 @@ struct LvsIvfPqArgs {
     u64* out;                    // [nranges][nq][k]
     long long ldq;
     int nq, nlist, nprobe, prange, k, metric, d, M, ldc, qsplit, qdpad, kcap;
+    const uint32_t* sel;         // [ceil(nb / 32)] row selector over ROW numbers (not positions); NULL: every row
 };
 size_t lvs_ivf_pq_lds_bytes(int M, int kcap);
 int lvs_ivf_pq_ldc(int M);  // code bytes per row: M rounded up to a multiple of 16

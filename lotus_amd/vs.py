@@ -83,12 +83,13 @@ class _IvfMode:
             return be.ivf_pq_fits(ent.d, self.M, k, ent.packed.mode)
         return be.ivf_fits(ent.d, k, ent.packed.mode)
 
-    def search(self, be, ent, queries, k: int, metric: int, nprobe: int, want_probe: bool = False):
+    def search(self, be, ent, queries, k: int, metric: int, nprobe: int, want_probe: bool = False, sel=None):
+        kw = {} if sel is None else {"sel": sel}  # a backend without selectors never sees the keyword
         if self.kind == "SQ8":
-            return be.ivf_sq8_search(ent.packed, ent.ivf, ent.codes, queries, k, metric, nprobe, want_probe)
+            return be.ivf_sq8_search(ent.packed, ent.ivf, ent.codes, queries, k, metric, nprobe, want_probe, **kw)
         if self.kind == "PQ":
-            return be.ivf_pq_search(ent.packed, ent.ivf, ent.codes, queries, k, metric, nprobe, want_probe)
-        return be.ivf_search(ent.packed, ent.ivf, queries, k, metric, nprobe, want_probe)
+            return be.ivf_pq_search(ent.packed, ent.ivf, ent.codes, queries, k, metric, nprobe, want_probe, **kw)
+        return be.ivf_search(ent.packed, ent.ivf, queries, k, metric, nprobe, want_probe, **kw)
 
     def train(self, be, packed, lists, train_ids):
         """-> the codec trained on the residuals of the k-means training rows, with every row's codes (IVF-Flat: None)."""
@@ -220,12 +221,27 @@ class HipVS(VS):
             codes' own top K, re-ordered by exact score); ``__call__(..., k_factor=...)`` overrides it per call.  A finite
             number >= 1.  The candidate count is ``min(max(K, ceil(K * k_factor)), 56, n)``: unlike faiss it stops at 56, the
             list scans' one-pass bound.  Stores without ``Refine(Flat)`` ignore it.
+        ids_probe: ``False`` (default) - every ``ids`` subset is searched exactly, as above.  ``True`` - an IVF store answers
+            a strict-subset call through its lists (faiss's ``SearchParametersIVF(sel=IDSelectorBitmap)``): ``ids`` becomes a
+            bitmap over the rows (``HipBackend.row_bitmap``) and the store's list scan skips the rows - and whole blocks of
+            rows - that are not selected, so the result is the top K over (rows of the probed lists) and (``ids``), re-ranked
+            exactly on a ``Refine(Flat)`` store.  ``__call__(..., ids_probe=...)`` overrides it per call; anything but a
+            ``bool`` is a ``ValueError``.  The call takes the lists only when the plain search's conditions hold (single GPU,
+            ``K <= 56``, ``nprobe <= 2048``, a shape the scan fits) and, in addition: ``ids`` holds no duplicate (``FaissVS``
+            returns a duplicated row twice, a bitmap cannot); ``K < len(ids)``; and ``len(ids) * nlist > n * nprobe`` - the
+            scan scores about ``n * nprobe / nlist`` rows per query whatever the selection, so below that the gathered exact
+            search scores fewer rows and keeps the call.  Every other call stays exact.  Indices are the given ids (global
+            row numbers); slots are ``-1`` / ``-+FLT_MAX`` when the probed lists hold fewer than ``K`` selected rows.  Besides
+            recall, one thing differs from the exact ``ids`` path: equal scores come out in ascending ROW order here, in the
+            order of their position in ``ids`` there - the same thing for ascending ``ids``, which a frame's index gives.
+            Flat stores ignore it.  An injected backend without ``row_bitmap`` is refused.
     """
 
     def __init__(self, metric: int = METRIC_INNER_PRODUCT, storage: str = "auto", device: str | None = None,
                  shard: bool | str = False, max_resident: int = 4, backend=None, process_group=None,
                  normalize: bool = False, abi_exchange: bool = False, factory_string: str = "Flat", nprobe: int = 1,
-                 ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256, k_factor: float = 1.0) -> None:
+                 ivf_niter: int = 20, ivf_max_points_per_centroid: int = 256, k_factor: float = 1.0,
+                 ids_probe: bool = False) -> None:
         super().__init__()
         m = (re.fullmatch(r"IVF([0-9]+),(Flat|(?:SQ8|PQ([0-9]+)(?:x8)?)(,Refine\(Flat\))?)", factory_string)
              if isinstance(factory_string, str) else None)
@@ -248,6 +264,9 @@ class HipVS(VS):
             raise ValueError("factory_string must be 'Flat' or 'IVF<nlist>,Flat' or 'IVF<nlist>,SQ8' or 'IVF<nlist>,PQ<M>[x8]' "
                              f"with a backend that has no exact re-ranking ({type(backend).__name__} lacks refine_keys), got "
                              f"{factory_string!r}")
+        self.ids_probe = self._check_ids_probe(ids_probe)
+        if self.ids_probe and backend is not None and not hasattr(backend, "row_bitmap"):
+            raise ValueError(f"ids_probe=True needs a backend with row selectors ({type(backend).__name__} lacks row_bitmap)")
         self.factory_string = factory_string
         self.k_factor = self._check_k_factor(k_factor)
         if self._nlist is not None and shard is not False:
@@ -579,8 +598,19 @@ class HipVS(VS):
         k_factor = self._check_k_factor(kwargs.get("k_factor", self.k_factor))
         refine = self._mode is not None and self._mode.refine
         kc = self._refine_kc(K, k_factor, ent.n) if refine else K
-        use_ivf = (ent.ivf is not None and sub is None and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
+        ids_probe = self._check_ids_probe(kwargs.get("ids_probe", self.ids_probe))
+        use_ivf = (ent.ivf is not None and (sub is None or ids_probe) and K <= _capi.IVF_MAX_K and K < ent.n and world == 1
                    and qworld == 1 and nprobe <= _capi.MAX_K and self._mode.fits(be, ent, kc))
+        # a strict subset goes through the lists only on request (ids_probe), without duplicates (a bitmap holds a row
+        # once), with more ids than K, and when the scan scores fewer rows than the gathered exact search would: about
+        # n nprobe / nlist per query against len(ids)
+        sel = None
+        if use_ivf and sub is not None:
+            use_ivf = hasattr(be, "row_bitmap") and K < sub.size and sub.size * ent.ivf.nlist > ent.n * nprobe
+            if use_ivf:
+                sel, distinct = be.row_bitmap(sub, ent.n)
+                use_ivf = distinct == sub.size
+                sel = sel if use_ivf else None
         q_all = nq
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
             per = -(-nq // qworld)
@@ -640,7 +670,7 @@ class HipVS(VS):
                 id_map = be.to_device(order)
             world = 1  # already complete on every rank: nothing left to merge
         elif use_ivf:
-            keys = self._mode.search(be, ent, queries, kc, self.metric, nprobe)
+            keys = self._mode.search(be, ent, queries, kc, self.metric, nprobe, sel=sel)
             if refine:  # the kc best by code score -> the k_eff best of them by exact score, exact scores in the keys
                 keys = be.refine_keys(ent.packed, queries, keys, k_eff, self.metric)
         elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
@@ -704,6 +734,12 @@ class HipVS(VS):
         if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or int(nprobe) < 1:
             raise ValueError(f"nprobe must be an int >= 1, got {nprobe!r}")
         return int(nprobe)
+
+    @staticmethod
+    def _check_ids_probe(ids_probe) -> bool:
+        if not isinstance(ids_probe, (bool, np.bool_)):
+            raise ValueError(f"ids_probe must be a bool, got {ids_probe!r}")
+        return bool(ids_probe)
 
     @staticmethod
     def _check_k_factor(k_factor) -> float:

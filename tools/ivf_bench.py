@@ -17,12 +17,19 @@ search at K = kc (first_stage_kernel_ms: the same code and shape as the refined 
 (refine_kernel_ms) and the re-ranking's rate: queries x kc x bytes of a stored row over that difference (refine_tbps).
 Prints one JSON document (and writes it to --out).
 
+--select FRACTION [FRACTION ...] measures the ids subsets instead: per workload, chosen mode, nprobe and fraction a random
+ascending subset of that share of the rows goes in as ``ids`` to the same store, once with ``ids_probe=False`` (the rows are
+gathered and searched exactly: gather_exact), once with ``ids_probe=True`` (the mode's list scan with the row selector:
+probe), beside the unselected scan (plain); wall ms per call as above for 1 and --big queries, the dominant kernel of each
+path, and whether HipVS's own rows-scored rule (len(ids) * nlist > n * nprobe) would send the call through the lists.
+
 The committed profiles are records of these runs (the first two of earlier generations of this tool, whose JSON named some
 keys differently):
   profiles/ivf_bench.json      python tools/ivf_bench.py --modes flat --workloads 768:fp16 --reps1 50
   profiles/ivf_sq8_bench.json  python tools/ivf_bench.py --modes flat sq8 --workloads 768:fp16 768:fp32 1536:fp32
   profiles/ivf_pq_bench.json   python tools/ivf_bench.py
-  profiles/ivf_refine_bench.json  python tools/ivf_bench.py --modes sq8 pq sq8r pqr --k-factor 5"""
+  profiles/ivf_refine_bench.json  python tools/ivf_bench.py --modes sq8 pq sq8r pqr --k-factor 5
+  profiles/ivf_select_bench.json  python tools/ivf_bench.py --workloads 768:fp16 --nprobe 32 --select 0.5 0.1 0.01 --big 1000"""
 from __future__ import annotations
 
 import argparse
@@ -167,6 +174,43 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
     return res
 
 
+def run_select(d, storage, a, HipVS, benchdata, torch):
+    """The --select table of one workload: {mode: {nprobe: {fraction: {plain, gather_exact, probe}}}}."""
+    k = 10
+    dtype = np.float16 if storage == "fp16" else np.float32
+    res = {"n": a.n, "d": d, "storage": storage, "nlist": a.nlist, "k": k, "select": list(a.select)}
+    xb = benchdata.corpus(benchdata.CFG_SEARCH, a.n, d, dtype=dtype)
+    xq, _ = benchdata.queries(benchdata.CFG_SEARCH, xb, a.big, dtype=dtype)
+    from lotus_amd import _capi
+
+    mode = _capi.PACK_F16 if storage == "fp16" else _capi.PACK_SPLIT
+    rng = np.random.default_rng(20261018)
+    subsets = {f: np.sort(rng.choice(a.n, max(k + 1, int(round(f * a.n))), replace=False)) for f in a.select}
+    probe_be = HipVS(storage=storage, device="cuda:0").backend
+    for name, kind in columns(a, probe_be, d, k, mode).items():
+        vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}", k_factor=a.k_factor)
+        vs.index(None, xb, f"bench-sel-{name}", persist=False)
+        nlist = len(vs.ivf_lists()[1]) - 1
+        col = {}
+        for nprobe in a.nprobe:
+            per = {}
+            for key, qs, reps, warm in (("q1", xq[:1], a.reps1, 5), (f"q{a.big}", xq[:a.big], a.repsbig, 2)):
+                plain = timed(vs, qs, k, reps, warm, nprobe=nprobe)
+                for f, ids in subsets.items():
+                    r = per.setdefault(str(f), {"ids": int(ids.size), "rule_takes_the_lists": bool(ids.size * nlist > a.n * nprobe)})
+                    # ids_probe=True goes through HipVS's own rule: where it keeps the call exact, "probe" times the exact
+                    # path again and its "kernel" says so
+                    exact = timed(vs, qs, k, reps, warm, nprobe=nprobe, ids=ids, ids_probe=False)
+                    probe = timed(vs, qs, k, reps, warm, nprobe=nprobe, ids=ids, ids_probe=True)
+                    r[key] = {"plain": plain, "gather_exact": exact, "probe": probe,
+                              "probe_speedup_wall": exact["wall_ms"] / probe["wall_ms"]}
+            col[str(nprobe)] = per
+        res[name] = col
+        del vs
+        torch.cuda.empty_cache()
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -183,6 +227,8 @@ def main() -> None:
     ap.add_argument("--repsbig", type=int, default=5)
     ap.add_argument("--recall-queries", type=int, default=1000)
     ap.add_argument("--skip-clustered", action="store_true")
+    ap.add_argument("--select", type=float, nargs="+", default=None,
+                    help="fractions of the rows passed as ids: time the gathered exact path against ids_probe=True instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -196,7 +242,8 @@ def main() -> None:
     out = {"device": torch.cuda.get_device_name(0), "workloads": []}
     for wl in a.workloads:
         d, storage = wl.split(":")
-        out["workloads"].append(run_workload(int(d), storage, a, HipVS, benchdata, torch))
+        run = run_select if a.select else run_workload
+        out["workloads"].append(run(int(d), storage, a, HipVS, benchdata, torch))
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
