@@ -141,8 +141,39 @@ class _IvfMode:
         return _host(cd.codebooks) * scale, by_row(cd.codes[:, :cd.M]), by_row(cd.beta) * (scale * scale)
 
 
+@dataclass(frozen=True)
+class _CallPlan:
+    """What one ``HipVS.__call__`` does, decided by ``_plan_call`` before the queries are packed."""
+
+    K: int
+    k_eff: int  # min(K, rows to search): what the kernels are asked for, the rest of K is padding
+    sub: Any  # ``ids`` as an int64 vector; None: every row
+    route: str  # "pipelined" | "rank_all" | "ivf" | "sharded_abi" | "flat" | "subset": ``HipVS._route_<route>`` searches
+    nprobe: int  # lists probed per query (0: no lists)
+    kc: int  # candidates per query of the list scan: K, more on a Refine(Flat) store
+    refine: bool
+    sel: Any  # backend row bitmap of ``sub`` for the list scan (None: no selection)
+    qexp: Any  # scale exponent the queries are packed with: the index's, the caller's ``_query_exp``, or "auto"
+    return_device: bool
+    layout: tuple  # ``_layout()``
+
+
 def _host(t) -> np.ndarray:
     return t.cpu().numpy()
+
+
+def _ids_subset(ids, n: int) -> np.ndarray | None:
+    """``ids`` as an int64 vector, checked against the ``n`` rows of the index; None for no ``ids`` and for every row in order,
+    which is the same as an unfiltered search (``sem_sim_join.py:132-134``)."""
+    if ids is None:
+        return None
+    sub = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if sub.size and (sub.min() < 0 or sub.max() >= n):
+        raise IndexError("ids out of range for the loaded index")
+    # size, first and last element first: a long ``ids`` builds an arange only when it can match
+    if sub.size == n and (n == 0 or (sub[0] == 0 and sub[-1] == n - 1 and np.array_equal(sub, np.arange(n)))):
+        return None
+    return sub
 
 
 def _serialised(fn):
@@ -412,6 +443,12 @@ class HipVS(VS):
             x = x.astype(np.float32)
         return x
 
+    def _query_matrix(self, query_vectors, ent: _Resident):
+        q = self._as_matrix(query_vectors, "query_vectors")
+        if q.shape[1] != ent.d:
+            raise ValueError(f"query dimension {q.shape[1]} does not match index dimension {ent.d}")
+        return q
+
     def _install(self, index_dir: str, vecs, stored=None, sig=None) -> _Resident:
         """Build the device image of this rank's shard from ``vecs`` ([n,d] ndarray / memmap / CUDA tensor; only rows
         [lo, hi) are touched).  ``stored``: what ``get_vectors_from_index`` serves (None = open on demand)."""
@@ -562,33 +599,39 @@ class HipVS(VS):
     def __call__(self, query_vectors, K: int, ids: list[int] | None = None, **kwargs: dict[str, Any]) -> RMOutput:
         """Top-``K`` rows for every query vector (``faiss_vs.py:43-77``)."""
         ent = self._current()
-        q = self._as_matrix(query_vectors, "query_vectors")
-        if q.shape[1] != ent.d:
-            raise ValueError(f"query dimension {q.shape[1]} does not match index dimension {ent.d}")
+        q = self._query_matrix(query_vectors, ent)
         K = int(K)
         if K < 0:
             raise ValueError("K must be >= 0")
         nq = int(q.shape[0])
-        return_device = bool(kwargs.get("return_device", False))
-        pad_d = -FLT_MAX if self.metric == METRIC_INNER_PRODUCT else FLT_MAX
         if K == 0 or nq == 0:
-            return RMOutput(distances=np.full((nq, K), pad_d, np.float32), indices=np.full((nq, K), -1, np.int64))
+            return self._padded(nq, K)
+        plan = self._plan_call(ent, q, K, ids, kwargs)
+        if plan is None:  # no ids: nothing to search
+            return self._padded(nq, K)
+        again = (query_vectors, K, ids, kwargs)  # what _check_queries searches again with when the packed queries' flags say so
+        if plan.route == "pipelined":
+            return self._route_pipelined(plan, ent, q, again)
+        queries, score_exp, flags = self._pack_queries(plan, ent, q)
+        keys, id_map, score_exp, world_left = getattr(self, "_route_" + plan.route)(plan, ent, queries, score_exp)
+        return self._finish(plan, keys, id_map, score_exp, world_left, flags, nq, again)
 
+    def _padded(self, nq: int, K: int) -> RMOutput:
+        """The result without a row in it: faiss pads with -1 / -+FLT_MAX (Appendix A.2)."""
+        pad_d = -FLT_MAX if self.metric == METRIC_INNER_PRODUCT else FLT_MAX
+        return RMOutput(distances=np.full((nq, K), pad_d, np.float32), indices=np.full((nq, K), -1, np.int64))
+
+    def _plan_call(self, ent: _Resident, q, K: int, ids, kwargs) -> _CallPlan | None:
+        """Which route this call takes and with what, from its arguments alone - nothing is packed or searched yet; None when
+        ``ids`` is empty.  Every condition is one that all ranks of a sharded store evaluate alike."""
         be = self.backend
-        sub = None
-        if ids is not None:
-            sub = np.asarray(ids, dtype=np.int64).reshape(-1)
-            if sub.size and (sub.min() < 0 or sub.max() >= ent.n):
-                raise IndexError("ids out of range for the loaded index")
-            if sub.size == ent.n and (ent.n == 0 or (sub[0] == 0 and sub[-1] == ent.n - 1
-                                                     and np.array_equal(sub, np.arange(ent.n)))):
-                sub = None  # every row, in order: same as an unfiltered search (sem_sim_join.py:132-134)
-        n_eff = ent.n if sub is None else int(sub.size)
-        k_eff = min(K, n_eff)
+        sub = _ids_subset(ids, ent.n)
+        k_eff = min(K, ent.n if sub is None else int(sub.size))
         if k_eff == 0:
-            return RMOutput(distances=np.full((nq, K), pad_d, np.float32), indices=np.full((nq, K), -1, np.int64))
+            return None
         rank_all = k_eff > _capi.MAX_K  # K = N callers (sem_dedup.py:45, sem_filter.py:491-497): full score rows + sort
-        qrank, qworld, rank, world, pg_query, pg_corpus = self._layout()
+        layout = self._layout()
+        _, qworld, _, world = layout[:4]
         # IVF stores probe lists for the plain query only; ids subsets, K = N callers, K beyond the one-pass list scan, rows too
         # wide for its LDS image and more than 2 048 probes take the exact path below - which also ends the reference
         # sem_search's K-doubling loop (sem_search.py:120-138) once the probed lists hold fewer than K rows
@@ -611,23 +654,45 @@ class HipVS(VS):
                 sel, distinct = be.row_bitmap(sub, ent.n)
                 use_ivf = distinct == sub.size
                 sel = sel if use_ivf else None
-        q_all = nq
+        # queries share the index's power-of-two scale (required for L2; for inner products it keeps one exponent per
+        # index); they are validated while they are packed, the flag word comes back together with the results
+        qexp = kwargs.get("_query_exp", ent.packed.exp)
+        return_device = bool(kwargs.get("return_device", False))
+        if rank_all:
+            route = "rank_all"
+        elif use_ivf:
+            route = "ivf"
+        elif sub is not None:
+            route = "subset"
+        elif (world == 1 and qworld == 1 and not return_device and k_eff == K and not self._is_device_tensor(q)
+              and qexp != "auto" and hasattr(be, "search_host_pipelined") and int(q.shape[0]) >= be.CALL_PIPELINE_MIN_QUERIES
+              and not self._fp32_path(ent, q)):
+            route = "pipelined"  # the plain big call (sem_sim_join.py:132-134 -> faiss_vs.py:75)
+        elif world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
+            route = "sharded_abi"
+        else:
+            route = "flat"
+        return _CallPlan(K=K, k_eff=k_eff, sub=sub, route=route, nprobe=nprobe, kc=kc, refine=refine, sel=sel, qexp=qexp,
+                         return_device=return_device, layout=layout)
+
+    def _route_pipelined(self, plan: _CallPlan, ent: _Resident, q, again) -> RMOutput:
+        """Host queries in, host results out, transfers overlapped with the search: packs, searches and decodes in one
+        backend call, so it returns the finished result."""
+        Dh, Ih, f = self.backend.search_host_pipelined(ent.packed, q, plan.k_eff, self.metric, id_offset=ent.lo,
+                                                       normalize=self.normalize, exp=int(plan.qexp))
+        redo = self._check_queries(f, *again)
+        return redo if redo is not None else RMOutput(distances=Dh, indices=Ih)
+
+    def _pack_queries(self, plan: _CallPlan, ent: _Resident, q):
+        """-> (packed queries, score exponent of their products with the index, validation flags or None): this rank's
+        slice of the queries under a query split, packed with the index's exponent or the one the call names."""
+        be, qexp = self.backend, plan.qexp
+        qrank, qworld, _, _, pg_query, _ = plan.layout
+        nq = int(q.shape[0])
         if qworld > 1:  # this rank's contiguous slice of the queries (possibly empty)
             per = -(-nq // qworld)
             q = q[min(nq, qrank * per):min(nq, (qrank + 1) * per)]
             nq = int(q.shape[0])
-
-        # queries share the index's power-of-two scale (required for L2; for inner products it keeps one exponent per
-        # index); they are validated while they are packed, the flag word comes back together with the results
-        qexp = kwargs.get("_query_exp", ent.packed.exp)
-        if (sub is None and not rank_all and not use_ivf and world == 1 and qworld == 1 and not return_device and k_eff == K
-                and not self._is_device_tensor(q) and qexp != "auto" and hasattr(be, "search_host_pipelined")
-                and nq >= be.CALL_PIPELINE_MIN_QUERIES and not self._fp32_path(ent, q)):
-            # the plain big call (sem_sim_join.py:132-134 -> faiss_vs.py:75): transfers overlapped with the search
-            Dh, Ih, f = be.search_host_pipelined(ent.packed, q, k_eff, self.metric, id_offset=ent.lo,
-                                                 normalize=self.normalize, exp=int(qexp))
-            redo = self._check_queries(f, query_vectors, K, ids, kwargs)
-            return redo if redo is not None else RMOutput(distances=Dh, indices=Ih)
         if qexp == "auto" and qworld > 1:
             # the finished lists of all query groups are decoded with ONE score exponent: agree it from the largest magnitude
             import torch
@@ -646,87 +711,103 @@ class HipVS(VS):
 
             g = _dist.all_gather_rows(flags, pg_query)
             flags = ((g & 1).amax(0) | (g & 2).amax(0)).to(flags.dtype)
-        id_map = None
-        if rank_all:
-            # score rows of this rank's shard, exchanged so that every rank ranks the complete rows (column-sharded
-            # score matrix, one all-gather); the device sort goes through the queries in chunks of < 2^32 scores
-            # ... and in blocks of at most 2^28 scores (1 GB of float32), so that a K = N call never holds the whole Q x N
-            # matrix next to its Q x N keys (sem_dedup's reference path asks for N x N)
-            n_cols = ent.n if sub is None else int(sub.size)
-            qstep = max(1, min(nq, _RANK_BLOCK_SCORES // max(1, n_cols)))
-            parts, order = [], None
-            for q0 in range(0, nq, qstep):
-                sc, order = self._score_rows(ent, be.slice_rows(queries, q0, min(nq, q0 + qstep)), sub, world)
-                parts.append(be.rank_scores(sc)[:, :k_eff].contiguous())
-                del sc
-            if len(parts) == 1:
-                keys = parts[0]
-            else:
-                import torch
+        return queries, score_exp, flags
 
-                keys = torch.cat(parts)
-            score_exp = 0  # score rows come back in the caller's units already
-            if order is not None:
-                id_map = be.to_device(order)
-            world = 1  # already complete on every rank: nothing left to merge
-        elif use_ivf:
-            keys = self._mode.search(be, ent, queries, kc, self.metric, nprobe, sel=sel)
-            if refine:  # the kc best by code score -> the k_eff best of them by exact score, exact scores in the keys
-                keys = be.refine_keys(ent.packed, queries, keys, k_eff, self.metric)
-        elif sub is None and world > 1 and self.abi_exchange and hasattr(be, "search_sharded") and k_eff <= 56:
-            # the same row-sharded search with its two exchanges issued from INSIDE the C ABI (lvs_search_sharded): the transport
-            # is this process group's all-gather, handed over as a callback
-            from . import _dist
-
-            per = -(-ent.n // world) if ent.n else 0
-            tiles = be.seed_tiles(queries.n, per, k_eff, ent.packed.mode, queries.mode) if hasattr(be, "seed_tiles") else 0
-            keys = be.search_sharded(ent.packed, queries, k_eff, self.metric, ent.lo, world, max(0, tiles),
-                                     lambda t: _dist.all_gather_rows(t, self._pg_corpus()))
-            world = 1  # merged already
-        elif sub is None:
-            keys = be.search_keys(ent.packed, queries, k_eff, self.metric, id_offset=ent.lo,
-                                  seed_scores=self._pooled_seed_scores(ent, queries, k_eff, world))
+    # every search route: (plan, ent, packed queries, score exponent) -> (keys [nq, k_eff], id_map or None, score exponent of
+    # the keys, corpus shards whose lists are still to be merged)
+    def _route_rank_all(self, plan: _CallPlan, ent: _Resident, queries, score_exp):
+        """K = N: score rows of this rank's shard, exchanged so that every rank ranks the complete rows (column-sharded score
+        matrix, one all-gather); the device sort goes through the queries in chunks of < 2^32 scores, and this loop in blocks
+        of at most 2^28 scores (1 GB of float32), so that a K = N call never holds the whole Q x N matrix next to its Q x N
+        keys (sem_dedup's reference path asks for N x N)."""
+        be, sub, nq = self.backend, plan.sub, queries.n
+        n_cols = ent.n if sub is None else int(sub.size)
+        qstep = max(1, min(nq, _RANK_BLOCK_SCORES // max(1, n_cols)))
+        parts, order = [], None
+        for q0 in range(0, nq, qstep):
+            sc, order = self._score_rows(ent, be.slice_rows(queries, q0, min(nq, q0 + qstep)), sub, plan.layout[3])
+            parts.append(be.rank_scores(sc)[:, :plan.k_eff].contiguous())
+            del sc
+        if len(parts) == 1:
+            keys = parts[0]
         else:
-            # positions (in `ids`) of the subset rows that live in this rank's shard
-            pos = np.flatnonzero((sub >= ent.lo) & (sub < ent.hi))
-            local = be.to_device(sub[pos] - ent.lo)
-            gathered = be.gather(ent.packed, local)
-            row_ids = be.to_device(pos.astype(np.uint32).view(np.int32))
-            keys = be.search_keys(gathered, queries, k_eff, self.metric, id_offset=0, row_ids=row_ids)
-            id_map = be.to_device(sub)
-        if world > 1:
-            keys = self._allgather_merge(keys, world)
+            import torch
+
+            keys = torch.cat(parts)
+        # score rows come back in the caller's units already, and complete on every rank: nothing left to merge
+        return keys, (be.to_device(order) if order is not None else None), 0, 1
+
+    def _route_ivf(self, plan: _CallPlan, ent: _Resident, queries, score_exp):
+        """The scan of each query's ``nprobe`` best lists (over the rows ``sel`` selects), re-ranked on a Refine(Flat) store."""
+        be = self.backend
+        keys = self._mode.search(be, ent, queries, plan.kc, self.metric, plan.nprobe, sel=plan.sel)
+        if plan.refine:  # the kc best by code score -> the k_eff best of them by exact score, exact scores in the keys
+            keys = be.refine_keys(ent.packed, queries, keys, plan.k_eff, self.metric)
+        return keys, None, score_exp, 1
+
+    def _route_sharded_abi(self, plan: _CallPlan, ent: _Resident, queries, score_exp):
+        """The same row-sharded search with its two exchanges issued from INSIDE the C ABI (lvs_search_sharded): the transport
+        is this process group's all-gather, handed over as a callback."""
+        from . import _dist
+
+        be, k, world = self.backend, plan.k_eff, plan.layout[3]
+        per = -(-ent.n // world) if ent.n else 0
+        tiles = be.seed_tiles(queries.n, per, k, ent.packed.mode, queries.mode) if hasattr(be, "seed_tiles") else 0
+        keys = be.search_sharded(ent.packed, queries, k, self.metric, ent.lo, world, max(0, tiles),
+                                 lambda t: _dist.all_gather_rows(t, self._pg_corpus()))
+        return keys, None, score_exp, 1  # merged already
+
+    def _route_flat(self, plan: _CallPlan, ent: _Resident, queries, score_exp):
+        """The plain exact search of this rank's shard; the shards of a row-sharded store pool their seed scores first."""
+        world = plan.layout[3]
+        keys = self.backend.search_keys(ent.packed, queries, plan.k_eff, self.metric, id_offset=ent.lo,
+                                        seed_scores=self._pooled_seed_scores(ent, queries, plan.k_eff, world))
+        return keys, None, score_exp, world
+
+    def _route_subset(self, plan: _CallPlan, ent: _Resident, queries, score_exp):
+        """The rows ``ids`` gathered on the GPU and searched exactly; keys carry positions in ``ids``."""
+        be, sub = self.backend, plan.sub
+        # positions (in `ids`) of the subset rows that live in this rank's shard
+        pos = np.flatnonzero((sub >= ent.lo) & (sub < ent.hi))
+        local = be.to_device(sub[pos] - ent.lo)
+        gathered = be.gather(ent.packed, local)
+        row_ids = be.to_device(pos.astype(np.uint32).view(np.int32))
+        keys = be.search_keys(gathered, queries, plan.k_eff, self.metric, id_offset=0, row_ids=row_ids)
+        return keys, be.to_device(sub), score_exp, plan.layout[3]
+
+    def _finish(self, plan: _CallPlan, keys, id_map, score_exp: int, world_left: int, flags, nq: int, again) -> RMOutput:
+        """Keys of this rank's queries against its shard -> the call's result: merged across the corpus shards, gathered across
+        the query groups, decoded, the queries' flags acted on, copied to the host and padded to ``K``."""
+        be, K, k_eff = self.backend, plan.K, plan.k_eff
+        _, qworld, _, _, pg_query, _ = plan.layout
+        if world_left > 1:
+            keys = self._allgather_merge(keys, world_left)
         if qworld > 1:  # finished lists of every query group's slice, side by side: one all-gather, no merge
             import torch
             from . import _dist
 
-            per = -(-q_all // qworld)
+            per = -(-nq // qworld)
             pad = torch.zeros((per, k_eff), dtype=keys.dtype, device=keys.device)
-            pad[:nq] = keys
-            keys = _dist.all_gather_rows(pad, pg_query).reshape(qworld * per, k_eff)[:q_all].contiguous()
-            nq = q_all
-        Dd, Id = be.keys_to_result(keys, self.metric, id_map, score_exp=score_exp)
-        if return_device and k_eff == K:  # results stay in HBM (torch tensors) for a GPU-side consumer
-            if flags is not None:
-                redo = self._check_queries(int(flags.item()), query_vectors, K, ids, kwargs)
-                if redo is not None:
-                    return redo
-            return RMOutput(distances=Dd, indices=Id)
-        if hasattr(be, "to_host"):  # all copies in flight together, one synchronisation, pinned-backed result arrays
-            Dh, Ih, *fh = be.to_host(Dd, Id, *([flags] if flags is not None else []))
+            pad[:keys.shape[0]] = keys
+            keys = _dist.all_gather_rows(pad, pg_query).reshape(qworld * per, k_eff)[:nq].contiguous()
+        D, I = be.keys_to_result(keys, self.metric, id_map, score_exp=score_exp)
+        if plan.return_device and k_eff == K:  # results stay in HBM (torch tensors) for a GPU-side consumer
+            f = int(flags.item()) if flags is not None else 0
         else:
-            Dh, Ih, *fh = [t.cpu().numpy() for t in ((Dd, Id) + ((flags,) if flags is not None else ()))]
-        if fh:
-            redo = self._check_queries(int(fh[0][0]), query_vectors, K, ids, kwargs)
-            if redo is not None:
-                return redo
+            if hasattr(be, "to_host"):  # all copies in flight together, one synchronisation, pinned-backed result arrays
+                D, I, *fh = be.to_host(D, I, *([flags] if flags is not None else []))
+            else:
+                D, I, *fh = [t.cpu().numpy() for t in ((D, I) + ((flags,) if flags is not None else ()))]
+            f = int(fh[0][0]) if fh else 0
+        redo = self._check_queries(f, *again)
+        if redo is not None:
+            return redo
         if k_eff == K:
-            return RMOutput(distances=Dh, indices=Ih)
-        D = np.full((nq, K), pad_d, np.float32)  # fewer than K rows exist: faiss pads with -1 / -+FLT_MAX (Appendix A.2)
-        I = np.full((nq, K), -1, np.int64)
-        D[:, :k_eff] = Dh
-        I[:, :k_eff] = Ih
-        return RMOutput(distances=D, indices=I)
+            return RMOutput(distances=D, indices=I)
+        out = self._padded(nq, K)  # fewer than K rows exist
+        out.distances[:, :k_eff] = D
+        out.indices[:, :k_eff] = I
+        return out
 
     # ------------------------------------------------------------------------------------------------ IVF
     @staticmethod
@@ -815,9 +896,7 @@ class HipVS(VS):
         """-> int32 [nq, nprobe] ids of the lists a search probes for every query, best first (the device's coarse step).  For
         rows too wide for the list scan (searched exactly, see ``__call__``) the same coarse ranking of the centroids."""
         ent = self._ivf_current()
-        q = self._as_matrix(query_vectors, "query_vectors")
-        if q.shape[1] != ent.d:
-            raise ValueError(f"query dimension {q.shape[1]} does not match index dimension {ent.d}")
+        q = self._query_matrix(query_vectors, ent)
         nprobe = min(self._check_nprobe(self.nprobe if nprobe is None else nprobe), ent.ivf.nlist)
         if nprobe > _capi.MAX_K:
             raise ValueError(f"ivf_probe ranks at most {_capi.MAX_K} lists per query")
@@ -878,39 +957,41 @@ class HipVS(VS):
             self.backend.raise_for_flags(f, "query vectors")
             return None
         q = self._as_matrix(query_vectors, "query_vectors")
-        on_device = self._is_device_tensor(q)
-        big = self._out_of_range_rows(q, ent)
+        big, pick = self._range_split(q, ent)
         kw = dict(kwargs)
         kw["_query_exp"] = "auto"
-        if big.all() or not big.any():
+        if big is None:
             return self.__call__(q, K, ids, **kw)
-        sel_big, sel_rest = np.flatnonzero(big), np.flatnonzero(~big)
-        if on_device:
-            import torch
-
-            pick = lambda sel: q[torch.from_numpy(sel).to(q.device)]
-        else:
-            pick = lambda sel: q[sel]
-        rest = self.__call__(pick(sel_rest), K, ids, **kwargs)
-        own = self.__call__(pick(sel_big), K, ids, **kw)
+        rest = self.__call__(pick(~big), K, ids, **kwargs)
+        own = self.__call__(pick(big), K, ids, **kw)
         if self._is_device_tensor(rest.distances) or hasattr(rest.distances, "index_copy_"):  # return_device=True
             import torch
 
             D = torch.empty((len(big), K), dtype=rest.distances.dtype, device=rest.distances.device)
             I = torch.empty((len(big), K), dtype=rest.indices.dtype, device=rest.indices.device)
-            for sel, part in ((sel_rest, rest), (sel_big, own)):
-                at = torch.from_numpy(sel).to(D.device)
+            for sel, part in ((~big, rest), (big, own)):
+                at = torch.from_numpy(np.flatnonzero(sel)).to(D.device)
                 D[at], I[at] = part.distances, part.indices
             return RMOutput(distances=D, indices=I)
         D, I = np.empty((len(big), K), np.float32), np.empty((len(big), K), np.int64)
-        D[sel_rest], I[sel_rest] = rest.distances, rest.indices
-        D[sel_big], I[sel_big] = own.distances, own.indices
+        D[~big], I[~big] = rest.distances, rest.indices
+        D[big], I[big] = own.distances, own.indices
         return RMOutput(distances=D, indices=I)
 
-    def _out_of_range_rows(self, q, ent) -> np.ndarray:
-        """bool [nq]: queries with a component beyond fp16's range under the index's power-of-two scale."""
-        rowmax = q.abs().amax(dim=1).float().cpu().numpy() if self._is_device_tensor(q) else np.abs(q).max(axis=1, initial=0.0)
-        return np.asarray(rowmax, dtype=np.float64) * 2.0 ** ent.packed.exp > 65504.0
+    def _range_split(self, q, ent):
+        """-> (big, pick): ``big`` bool [nq], the queries with a component beyond fp16's range under the index's power-of-two
+        scale, and ``pick(mask)``, the rows of ``q`` (a host array or a device tensor) under a mask like it.  ``big`` is None when
+        all or none of them are: nothing to split, the batch goes to one call with ``_query_exp="auto"``."""
+        on_device = self._is_device_tensor(q)
+        rowmax = q.abs().amax(dim=1).float().cpu().numpy() if on_device else np.abs(q).max(axis=1, initial=0.0)
+        big = np.asarray(rowmax, dtype=np.float64) * 2.0 ** ent.packed.exp > 65504.0
+        if big.all() or not big.any():
+            return None, None
+        if on_device:
+            import torch
+
+            return big, lambda mask: q[torch.from_numpy(np.flatnonzero(mask)).to(q.device)]
+        return big, lambda mask: q[mask]
 
     @_serialised
     def scores(self, query_vectors, ids: list[int] | None = None, _query_exp=None):
@@ -920,17 +1001,9 @@ class HipVS(VS):
         the product; L2: minus the squared distance.  On a sharded index every rank computes the columns of its
         shard and one all-gather completes the rows."""
         ent = self._current()
-        q = self._as_matrix(query_vectors, "query_vectors")
-        if q.shape[1] != ent.d:
-            raise ValueError(f"query dimension {q.shape[1]} does not match index dimension {ent.d}")
+        q = self._query_matrix(query_vectors, ent)
         be = self.backend
-        sub = None
-        if ids is not None:
-            sub = np.asarray(ids, dtype=np.int64).reshape(-1)
-            if sub.size and (sub.min() < 0 or sub.max() >= ent.n):
-                raise IndexError("ids out of range for the loaded index")
-            if sub.size == ent.n and np.array_equal(sub, np.arange(ent.n)):
-                sub = None
+        sub = _ids_subset(ids, ent.n)
         _, world = self._dist()
         queries = be.pack(q, ent.packed.mode, normalize=self.normalize,
                           exp=ent.packed.exp if _query_exp is None else _query_exp, check="lazy")
@@ -939,15 +1012,9 @@ class HipVS(VS):
                 and _query_exp is None and ent.packed.mode == _capi.PACK_SPLIT):
             # magnitudes outside fp16's range under the index's scale: inner products allow those queries an exponent of
             # their own (the rest of the batch keeps the index's, as in __call__)
-            big = self._out_of_range_rows(q, ent)
-            if big.all() or not big.any():
+            big, pick = self._range_split(q, ent)
+            if big is None:
                 return self.scores(q, ids, _query_exp="auto")
-            if self._is_device_tensor(q):
-                import torch
-
-                pick = lambda sel: q[torch.from_numpy(np.flatnonzero(sel)).to(q.device)]
-            else:
-                pick = lambda sel: q[sel]
             rest, own = self.scores(pick(~big), ids), self.scores(pick(big), ids, _query_exp="auto")
             out = np.empty((len(big), rest.shape[1]), np.float32)
             out[~big], out[big] = rest, own
@@ -1007,14 +1074,8 @@ class HipVS(VS):
         ent = self._current()
         if ent.lo != 0 or ent.hi != ent.n:
             raise ValueError("packed_rows needs an unsharded index")
-        if ids is None:
-            return ent.packed
-        sub = np.asarray(ids, dtype=np.int64).reshape(-1)
-        if sub.size == ent.n and np.array_equal(sub, np.arange(ent.n)):
-            return ent.packed
-        if sub.size and (sub.min() < 0 or sub.max() >= ent.n):
-            raise IndexError("ids out of range for the loaded index")
-        return self.backend.gather(ent.packed, self.backend.to_device(sub))
+        sub = _ids_subset(ids, ent.n)
+        return ent.packed if sub is None else self.backend.gather(ent.packed, self.backend.to_device(sub))
 
     @_serialised
     def kmeans(self, vec_set, ncentroids: int, niter: int = 20, ids=None, return_result: bool = False, **kw):
@@ -1025,13 +1086,7 @@ class HipVS(VS):
         from .cluster import kmeans as _kmeans
 
         ent = self._current()
-        sub = None
-        if ids is not None:
-            sub = np.asarray(ids, dtype=np.int64).reshape(-1)
-            if sub.size and (sub.min() < 0 or sub.max() >= ent.n):
-                raise IndexError("ids out of range for the loaded index")
-            if sub.size == ent.n and np.array_equal(sub, np.arange(ent.n)):
-                sub = None
+        sub = _ids_subset(ids, ent.n)
         be = self.backend
         # the path is chosen from the group size - identical on every rank - never from this rank's share of the rows
         # (with ceil(n / world) >= n rank 0 holds everything while the others still enter the collectives)
