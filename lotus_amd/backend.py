@@ -86,6 +86,57 @@ def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
 
+class _Bounds:
+    """The Hamerly bounds that a squared-L2 ``nearest`` call keeps beside its search: the caller's ``bounds`` tuple
+    ``(assign, ub, lb, positions)``, the corpus statistics and the five coefficients of the search's own error bound."""
+
+    def __init__(self, be, bounds, corpus_stats, coef, id_offset):
+        self.be, self.corpus_stats, self.id_offset = be, corpus_stats, int(id_offset)
+        self.assign, self.ub, self.lb, self.pos = bounds
+        self.coef5 = (ctypes.c_float * 5)(*coef)
+
+    def of_queries(self, q0: int, q1: int) -> "_Bounds":
+        """The same bounds for the chunk [q0, q1) of the call's queries."""
+        t = self.be.torch
+        pos = self.pos[q0:q1] if self.pos is not None else t.arange(q0, q1, dtype=t.int64, device=self.be.device)
+        return _Bounds(self.be, (self.assign, self.ub, self.lb, pos), self.corpus_stats, self.coef5, self.id_offset)
+
+    def set(self, keys, sec, q_norms, nq: int) -> None:
+        """Every query's bounds from the one-pass result (see ``HipBackend.nearest``)."""
+        self.be._c("lvs_kmeans_bounds_set", _ptr(keys), 1, _ptr(sec), _ptr(q_norms), _ptr(self.pos), nq, _ptr(self.corpus_stats),
+                   ctypes.addressof(self.coef5), self.id_offset, _ptr(self.assign), _ptr(self.ub), _ptr(self.lb), self.be._stream())
+
+    def fix(self, approx, exact, q_norms, sel) -> None:
+        """The bounds of the queries ``sel`` again, from their one-pass keys ``approx`` and the ``exact`` keys that decided them."""
+        # float32 rounding of |x|^2 + |c|^2 - 2 x.c (cancellation when the row sits on a centroid): a few ulps of
+        # the largest term - 8e-6 R |x| + 4e-6 R^2; errors proportional to the distance itself are covered by the
+        # relative margin of lvs_kmeans_bounds_step
+        exact2 = (ctypes.c_float * 2)(8e-6, 4e-6)
+        pos = sel if self.pos is None else self.pos[sel]
+        self.be._c("lvs_kmeans_bounds_fix", _ptr(approx), _ptr(exact), _ptr(q_norms), _ptr(pos), int(sel.numel()),
+                   _ptr(self.corpus_stats), ctypes.addressof(self.coef5), ctypes.addressof(exact2), self.id_offset,
+                   _ptr(self.assign), _ptr(self.ub), _ptr(self.lb), self.be._stream())
+
+
+@dataclass
+class _NearestHandle:
+    """``nearest_begin`` -> ``nearest_finish``: finished keys, one handle per chunk, or ONE pending ``lvs_nearest3`` call."""
+
+    queries: PackedRows
+    done: "object" = None    # int64 [nq, 1]: nothing is pending
+    chunks: list = None      # [(q0, q1, _NearestHandle of queries [q0, q1))]
+    corpus: PackedRows = None
+    metric: int = 0
+    id_offset: int = 0
+    exact_scores: bool = True
+    bounds: _Bounds = None
+    keys: "object" = None    # int64 [nq, 1]: the one-pass winners, decided in place by the finish
+    keys2: "object" = None   # int64 [nq]: the runners-up
+    pair_idx: "object" = None  # int64 [nq]: the queries only two rows can win, ``open_idx``: those to search again, and
+    open_idx: "object" = None
+    counts: "object" = None    # int64 [2]: how many of each (read by the finish: the call's one host round trip)
+
+
 class HipBackend:
     PACK_CHUNK_ROWS = 262144
     NEAREST3_WS_BUDGET = 2 << 30  # bytes of scratch one lvs_nearest3 call may ask for; more queries go through in chunks
@@ -489,66 +540,70 @@ class HipBackend:
             if k == 1:  # the winner + runner-up certificate is the cheaper one-pass form for a single neighbour
                 return self.nearest(corpus, queries, metric, id_offset=id_offset, stats=stats)
             return self._search_keys_certified(corpus, queries, k, metric, id_offset, stats)
-        keys = torch.empty((queries.n, k), dtype=torch.int64, device=self.device)
-        need = int(self.lib.lvs_flat_search_workspace_bytes(queries.n, corpus.n, corpus.d, k, corpus.mode, queries.mode))
-        if need < 0:
-            raise LotusHipError("lvs_flat_search_workspace_bytes rejected the shape")
-        ws = self._workspace(need)
         if seed_scores is not None and int(seed_scores.shape[0]) > 0:
             if seed_scores.dim() != 2 or int(seed_scores.shape[1]) != queries.n or seed_scores.dtype != torch.float32:
                 raise ValueError("seed_scores must be float32 [rows, nq]")
             seed_scores = seed_scores.contiguous()
-            self._c("lvs_flat_search_keys_seeded", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode,
-                    queries.n, corpus.d, metric, k, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(row_ids),
-                    _ptr(seed_scores), int(seed_scores.shape[0]), _ptr(keys), _ptr(ws), int(ws.numel()), self._stream())
-            return keys
-        self._c("lvs_flat_search_keys", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode,
-                queries.n, corpus.d, metric, k, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(row_ids),
-                _ptr(keys), _ptr(ws), int(ws.numel()), self._stream())
-        return keys
+            return self._search_call("lvs_flat_search_keys_seeded", corpus, queries, k, metric, id_offset, row_ids,
+                                     seeded=(_ptr(seed_scores), int(seed_scores.shape[0])))
+        return self._search_call("lvs_flat_search_keys", corpus, queries, k, metric, id_offset, row_ids)
+
+    @staticmethod
+    def _cached_max(pk: PackedRows, name: str, compute) -> float:
+        """``compute()`` once per device image: the value is cached on the image where it accepts attributes."""
+        v = getattr(pk, name, None)
+        if v is None:
+            v = compute()
+            try:
+                setattr(pk, name, v)
+            except Exception:
+                pass
+        return v
 
     def lo_norm_max(self, pk: PackedRows) -> float:
         """Largest |lo part of a row| of a device image (0 for fp16 rows), computed once per image and cached on it."""
         if pk.mode != _capi.PACK_SPLIT or pk.n == 0:
             return 0.0
-        v = getattr(pk, "_lo_norm_max", None)
-        if v is None:
-            torch = self.torch
-            dpad = int(pk.rows.shape[1]) // 2
+
+        def compute():
+            torch, dpad = self.torch, int(pk.rows.shape[1]) // 2
             m = torch.zeros((), dtype=torch.float32, device=self.device)
             for r0 in range(0, pk.n, 1 << 18):  # in chunks: the float32 copy of 2^18 x 768 lo parts is 0.8 GB
                 m = torch.maximum(m, pk.rows[r0:r0 + (1 << 18), dpad:].float().square().sum(dim=1).max())
-            v = float(m.sqrt().item())
-            try:
-                pk._lo_norm_max = v
-            except Exception:
-                pass
-        return v
+            return float(m.sqrt().item())
+
+        return self._cached_max(pk, "_lo_norm_max", compute)
 
     def row_norm_max(self, pk: PackedRows) -> float:
         """Largest |row| of a device image, computed once per image and cached on it."""
         if pk.n == 0:
             return 0.0
-        v = getattr(pk, "_row_norm_max", None)
-        if v is None:
-            v = float(pk.norms.max().sqrt().item())
-            try:
-                pk._row_norm_max = v
-            except Exception:
-                pass
-        return v
+        return self._cached_max(pk, "_row_norm_max", lambda: float(pk.norms.max().sqrt().item()))
 
-    def _search_call(self, name: str, corpus, queries, k, metric, id_offset):
-        torch = self.torch
-        keys = torch.empty((queries.n, k), dtype=torch.int64, device=self.device)
+    def _search_call(self, name: str, corpus, queries, k, metric, id_offset, row_ids=None, banded=(), seeded=()):
+        """One flat search (``lvs_flat_search_keys`` / ``_seeded`` / ``_hi`` / ``_hi_banded``) -> keys [nq, k].  ``banded``: what goes
+        between ``k`` and the norms (the band's k, scale and slack); ``seeded``: after ``row_ids`` (the seed scores, their rows)."""
+        keys = self.torch.empty((queries.n, k), dtype=self.torch.int64, device=self.device)
         need = int(self.lib.lvs_flat_search_workspace_bytes(queries.n, corpus.n, corpus.d, k, corpus.mode, queries.mode))
         if need < 0:
-            raise LotusHipError("lvs_flat_search_workspace_bytes rejected the shape")
+            raise LotusHipError("the flat search's workspace query rejected the shape")
         ws = self._workspace(need)
         self._c(name, _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode, queries.n, corpus.d, metric,
-                k, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), None, _ptr(keys), _ptr(ws), int(ws.numel()),
-                self._stream())
+                k, *banded, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(row_ids), *seeded, _ptr(keys), _ptr(ws),
+                int(ws.numel()), self._stream())
         return keys
+
+    def _rescore(self, corpus, queries, metric, id_offset, keys) -> None:
+        """Put the exact scores into the keys [nq, k] of every query, in place (one wave per query, HBM-bound)."""
+        self._c("lvs_rescore_keys", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, queries.n, corpus.d, metric,
+                _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), int(keys.shape[1]), _ptr(keys), self._stream())
+
+    @staticmethod
+    def _count(stats: dict | None, **counts) -> None:
+        """Add the named counts into ``stats`` (when the caller gave one)."""
+        if stats is not None:
+            for name, v in counts.items():
+                stats[name] = stats.get(name, 0) + v
 
     def _search_keys_certified(self, corpus, queries, k, metric, id_offset, stats, k1=None):
         """Exact top-k of fp32-accurate operands from one MFMA pass (see ``search_keys``).
@@ -580,11 +635,6 @@ class HipBackend:
         # above max(last slot, k-th slot - CERT_BAND_SEARCH x bound): the k1-deep lists then cost the insertions of k-deep
         # ones, and a query stays open only when more than k1 - k rows crowd that band.  The certificate assumes the slightly
         # narrower CERT_BAND_CERTIFY (rounding of the two evaluations of the band can never make it claim too much).
-        keys = torch.empty((nq, k1), dtype=torch.int64, device=self.device)
-        need = int(self.lib.lvs_flat_search_workspace_bytes(nq, corpus.n, corpus.d, k1, corpus.mode, queries.mode))
-        if need < 0:
-            raise LotusHipError("lvs_flat_search_workspace_bytes rejected the shape")
-        ws = self._workspace(need)
         banded = k1 > k
         # (r6) joins of fp32 embeddings: the one pass over the hi parts runs on the register-resident-queries kernel
         # (lvs_rj_kernel: chunks of <= 32 768 queries, 0.5 instead of 0.43 of the MFMA roof) whenever the shape is its - that kernel
@@ -594,16 +644,12 @@ class HipBackend:
                 and dpad in (256, 384, 512, 768) and corpus.mode == queries.mode == _capi.PACK_SPLIT):
             banded = False
         if banded:
-            self._c("lvs_flat_search_keys_hi_banded", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode,
-                    nq, corpus.d, metric, k1, k, float(self.CERT_BAND_SEARCH * scale), float(self.CERT_BAND_SEARCH * slack),
-                    _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), None, _ptr(keys), _ptr(ws), int(ws.numel()),
-                    self._stream())
-            approx = keys
+            approx = self._search_call("lvs_flat_search_keys_hi_banded", corpus, queries, k1, metric, id_offset,
+                                       banded=(k, float(self.CERT_BAND_SEARCH * scale), float(self.CERT_BAND_SEARCH * slack)))
         else:
             approx = self._search_call("lvs_flat_search_keys_hi", corpus, queries, k1, metric, id_offset)
         exact = approx.clone()
-        self._c("lvs_rescore_keys", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, nq, corpus.d, metric,
-                _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), k1, _ptr(exact), self._stream())
+        self._rescore(corpus, queries, metric, id_offset, exact)
         self._c("lvs_sort_keys_desc", _ptr(exact), nq, k1, self._stream())
         idx = torch.empty((nq,), dtype=torch.int64, device=self.device)
         cnt = torch.zeros((1,), dtype=torch.int64, device=self.device)
@@ -625,11 +671,9 @@ class HipBackend:
             else:
                 keys[sel] = self.search_keys(corpus, sub, k, metric, id_offset=id_offset, one_pass=False)
                 n_plain = n_open
-        if stats is not None:
-            if first_round:
-                stats["uncertified"] = stats.get("uncertified", 0) + n_open
-                stats["queries"] = stats.get("queries", 0) + nq
-            stats["plain"] = stats.get("plain", 0) + n_plain
+        if first_round:
+            self._count(stats, uncertified=n_open, queries=nq)
+        self._count(stats, plain=n_plain)
         return keys
 
     def nearest(self, corpus: PackedRows, queries: PackedRows, metric: int, id_offset: int = 0, stats: dict | None = None,
@@ -650,20 +694,19 @@ class HipBackend:
         ``kmeans_finish`` leave it - the certificate's bound is then evaluated on the device (no host round trip for it).
         ``bounds``: ``(assign int32, ub float32, lb float32, positions int64 or None)`` device tensors - squared-L2 searches
         only, needs ``corpus_stats``: the rows ``positions`` (None: rows 0..nq) also get their Hamerly bounds from this
-        search (``lvs_kmeans_bounds_set``): the winner, an upper bound of its distance and a lower bound of the distance to
+        search (``_Bounds.set``): the winner, an upper bound of its distance and a lower bound of the distance to
         every other corpus row, the search's own error bound included."""
         torch = self.torch
         if bounds is not None and (corpus_stats is None or metric != _capi.METRIC_L2):
             raise ValueError("bounds need the squared-L2 metric and the corpus statistics")
         if corpus.mode == _capi.PACK_F16 and queries.mode == _capi.PACK_F16 and bounds is None:
             return self.search_keys(corpus, queries, 1, metric, id_offset=id_offset)  # nothing to certify: already exact
-        plain = dict(id_offset=id_offset, one_pass=False)
         if corpus.d != queries.d:
             raise ValueError("corpus / query dimension mismatch")
         nq = queries.n
         keys = torch.empty((nq, 1), dtype=torch.int64, device=self.device)
         if nq == 0 or corpus.n == 0:
-            return self.search_keys(corpus, queries, 1, metric, **plain)
+            return self.search_keys(corpus, queries, 1, metric, id_offset=id_offset, one_pass=False)
         # error bound per unit of |q|: E = largest lo-part norm and R = largest norm over the corpus rows (a small matrix in
         # the k-means use: the centroids).  bound = scale |q| + slack with
         #   scale = c (E + 2^-11 R [queries split] + 8e-6 R) + 2^-16 cm R     (c = 2 / 4, cm = 1 / 2 for IP / L2; 8e-6: fp32
@@ -672,22 +715,19 @@ class HipBackend:
         # 2 q.y - |y|^2, for the winner and for the runner-up): the 2^-16 terms.  |lo_q| <= 2^-11 |q| + sqrt(d) 2^-25: the
         # second term covers components in fp16's subnormal range.
         coef, dpad = self._nearest_coef(corpus, queries, metric)
+        if bounds is not None:
+            bounds = _Bounds(self, bounds, corpus_stats, coef, id_offset)
         if corpus.n <= _capi.NEAREST3_MAX_ROWS:
             # a small corpus (k-means centroids): queries streaming past resident corpus tiles + the two-candidate certificate.
             # Its scratch is 20 B per (corpus tile, query): the queries go through in chunks that keep it below a fixed budget
             # (10 M rows x 16 384 centroids would ask for 12.8 GB in one call - ADVICE r04); results are per query, so
-            # chunking changes nothing
-            step = self._nearest3_step(corpus)
-            if nq <= step:
-                return self._nearest3(corpus, queries, metric, id_offset, stats, exact_scores, corpus_stats, bounds, coef, dpad, plain)
-            for q0 in range(0, nq, step):
-                q1 = min(nq, q0 + step)
-                bsub = bounds
-                if bounds is not None:
-                    pos = bounds[3][q0:q1] if bounds[3] is not None else torch.arange(q0, q1, dtype=torch.int64, device=self.device)
-                    bsub = (bounds[0], bounds[1], bounds[2], pos)
-                keys[q0:q1] = self._nearest3(corpus, self.slice_rows(queries, q0, q1), metric, id_offset, stats, exact_scores,
-                                             corpus_stats, bsub, coef, dpad, plain)
+            # chunking changes nothing.  Every chunk is begun AND finished before the next (one chunk's tensors alive at a time)
+            for q0, q1, qs, bs in self._nearest3_chunks(corpus, queries, bounds):
+                part = self._nearest3_finish(
+                    self._nearest3_begin(corpus, qs, metric, id_offset, exact_scores, corpus_stats, bs, coef, dpad), stats)
+                if q1 - q0 == nq:
+                    return part
+                keys[q0:q1] = part
             return keys
         if corpus_stats is None:
             R = float(corpus.norms.max().sqrt().item())
@@ -710,34 +750,20 @@ class HipBackend:
             self._c("lvs_margin_select_stats", _ptr(keys), _ptr(sec), _ptr(queries.norms), nq, _ptr(corpus_stats),
                     ctypes.addressof(coef5), _ptr(idx), _ptr(cnt), self._stream())
         if bounds is not None:  # every row's bounds from the one-pass result first; the uncertified rows are redone below
-            b_assign, b_ub, b_lb, b_pos = bounds
-            coef5 = (ctypes.c_float * 5)(*coef)
-            self._c("lvs_kmeans_bounds_set", _ptr(keys), 1, _ptr(sec), _ptr(queries.norms), _ptr(b_pos), nq,
-                    _ptr(corpus_stats), ctypes.addressof(coef5), int(id_offset), _ptr(b_assign), _ptr(b_ub), _ptr(b_lb),
-                    self._stream())
+            bounds.set(keys, sec, queries.norms, nq)
         n_open = int(cnt.item())  # the call's one host round trip: the exact search below is sized by it
         # the winners are certified, their scores are still the one-pass approximations: put the exact scores in
         # (one HBM-bound pass over the queries; the k-means objective sums them)
         if exact_scores:
-            self._c("lvs_rescore_keys", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, nq, corpus.d,
-                    metric, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), 1, _ptr(keys), self._stream())
+            self._rescore(corpus, queries, metric, id_offset, keys)
         if n_open:
             sel = idx[:n_open]
             sub = self.gather(queries, sel)
-            exact_keys = self.search_keys(corpus, sub, 1, metric, **plain)  # the same exact search with or without bounds
+            exact_keys = self.search_keys(corpus, sub, 1, metric, id_offset=id_offset, one_pass=False)  # with or without bounds
             if bounds is not None:
-                # float32 rounding of |x|^2 + |c|^2 - 2 x.c (cancellation when the row sits on a centroid): a few ulps of
-                # the largest term - 8e-6 R |x| + 4e-6 R^2; errors proportional to the distance itself are covered by the
-                # relative margin of lvs_kmeans_bounds_step
-                exact2 = (ctypes.c_float * 2)(8e-6, 4e-6)
-                pos = sel if b_pos is None else b_pos[sel]
-                self._c("lvs_kmeans_bounds_fix", _ptr(keys[sel].contiguous()), _ptr(exact_keys), _ptr(sub.norms), _ptr(pos),
-                        n_open, _ptr(corpus_stats), ctypes.addressof(coef5), ctypes.addressof(exact2), int(id_offset),
-                        _ptr(b_assign), _ptr(b_ub), _ptr(b_lb), self._stream())
+                bounds.fix(keys[sel].contiguous(), exact_keys, sub.norms, sel)
             keys[sel] = exact_keys
-        if stats is not None:
-            stats["uncertified"] = stats.get("uncertified", 0) + n_open
-            stats["queries"] = stats.get("queries", 0) + nq
+        self._count(stats, uncertified=n_open, queries=nq)
         return keys
 
     @staticmethod
@@ -752,17 +778,30 @@ class HipBackend:
                 1e-6 + (0.0 if ip else 2.0 ** -16)]
         return coef, dpad
 
-    def _nearest3(self, corpus, queries, metric, id_offset, stats, exact_scores, corpus_stats, bounds, coef, dpad, plain):
+    def _nearest3_step(self, corpus) -> int:
+        """Most queries one ``lvs_nearest3`` call may take inside the scratch budget (20 B per corpus tile and query)."""
+        per_q = max(1, int(self.lib.lvs_nearest3_workspace_bytes(1 << 20, corpus.n, corpus.d)) >> 20)
+        return max(1 << 16, (self.NEAREST3_WS_BUDGET // per_q) >> 16 << 16)
+
+    def _nearest3_chunks(self, corpus, queries, bounds):
+        """The queries in chunks of ``_nearest3_step``: yields (q0, q1, queries [q0, q1), the bounds of those queries).  Queries
+        that fit one call come back as they are."""
+        step = self._nearest3_step(corpus)
+        if queries.n <= step:
+            yield 0, queries.n, queries, bounds
+            return
+        for q0 in range(0, queries.n, step):
+            q1 = min(queries.n, q0 + step)
+            yield q0, q1, self.slice_rows(queries, q0, q1), (None if bounds is None else bounds.of_queries(q0, q1))
+
+    def _nearest3_begin(self, corpus, queries, metric, id_offset, exact_scores, corpus_stats, bounds, coef, dpad):
         """``nearest`` for a corpus of at most 16 384 rows (``lvs_nearest3``): the one-pass search also returns the runner-up's
         id and the THIRD score, so a query whose best-second margin is inside the error bound but whose best-third margin is
         not has only two possible winners - two exact dot products (``lvs_resolve_pairs``) decide it instead of an exact
         search over every row; only queries with three or more rows inside the bound take that search.  The three-way split
-        depends on a query's own scores and the corpus alone, never on which other queries share the call."""
-        h = self._nearest3_begin(corpus, queries, metric, id_offset, exact_scores, corpus_stats, bounds, coef, dpad, plain)
-        return self._nearest3_finish(h, stats)
+        depends on a query's own scores and the corpus alone, never on which other queries share the call.
 
-    def _nearest3_begin(self, corpus, queries, metric, id_offset, exact_scores, corpus_stats, bounds, coef, dpad, plain):
-        """Launches only: the one-pass search and the three-way split; nothing is read back.  -> handle for ``_nearest3_finish``
+        Launches only: the one-pass search and the three-way split; nothing is read back.  -> handle for ``_nearest3_finish``
         (which may run on another stream once these launches are done - ``nearest_begin`` / ``nearest_finish``)."""
         torch = self.torch
         nq = queries.n
@@ -770,10 +809,9 @@ class HipBackend:
             E2 = (corpus.rows[:, dpad:].float().square().sum(dim=1).max() if corpus.mode == _capi.PACK_SPLIT
                   else torch.zeros((), dtype=torch.float32, device=self.device))
             corpus_stats = torch.stack([corpus.norms.max(), E2]).to(torch.float32)
-        keys = torch.empty((nq, 1), dtype=torch.int64, device=self.device)
-        keys2 = torch.empty((nq,), dtype=torch.int64, device=self.device)
-        sec = torch.empty((nq,), dtype=torch.float32, device=self.device)
-        third = torch.empty((nq,), dtype=torch.float32, device=self.device)
+        i64 = dict(dtype=torch.int64, device=self.device)
+        keys, keys2 = torch.empty((nq, 1), **i64), torch.empty((nq,), **i64)
+        sec, third = (torch.empty((nq,), dtype=torch.float32, device=self.device) for _ in range(2))
         need = int(self.lib.lvs_nearest3_workspace_bytes(nq, corpus.n, corpus.d))
         if need < 0:
             raise LotusHipError("lvs_nearest3_workspace_bytes rejected the shape")
@@ -781,63 +819,41 @@ class HipBackend:
         self._c("lvs_nearest3", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode, nq, corpus.d, metric,
                 _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(keys), _ptr(keys2), _ptr(sec), _ptr(third),
                 _ptr(ws), int(ws.numel()), self._stream())
-        pair_idx = torch.empty((nq,), dtype=torch.int64, device=self.device)
-        open_idx = torch.empty((nq,), dtype=torch.int64, device=self.device)
-        counts = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        pair_idx, open_idx, counts = torch.empty((nq,), **i64), torch.empty((nq,), **i64), torch.zeros((2,), **i64)
         coef5 = (ctypes.c_float * 5)(*coef)
         self._c("lvs_nearest3_select", _ptr(keys), _ptr(keys2), _ptr(sec), _ptr(third), _ptr(queries.norms), nq,
                 _ptr(corpus_stats), ctypes.addressof(coef5), _ptr(pair_idx), _ptr(open_idx), _ptr(counts), self._stream())
         if bounds is not None:  # every row's bounds from the one-pass result first; the uncertified rows are redone below
-            b_assign, b_ub, b_lb, b_pos = bounds
-            self._c("lvs_kmeans_bounds_set", _ptr(keys), 1, _ptr(sec), _ptr(queries.norms), _ptr(b_pos), nq,
-                    _ptr(corpus_stats), ctypes.addressof(coef5), int(id_offset), _ptr(b_assign), _ptr(b_ub), _ptr(b_lb),
-                    self._stream())
-        return dict(corpus=corpus, queries=queries, metric=metric, id_offset=id_offset, exact_scores=exact_scores,
-                    corpus_stats=corpus_stats, bounds=bounds, coef5=coef5, plain=plain, keys=keys, keys2=keys2, sec=sec,
-                    third=third, pair_idx=pair_idx, open_idx=open_idx, counts=counts)
+            bounds.set(keys, sec, queries.norms, nq)
+        return _NearestHandle(queries=queries, corpus=corpus, metric=metric, id_offset=id_offset, exact_scores=exact_scores,
+                              bounds=bounds, keys=keys, keys2=keys2, pair_idx=pair_idx, open_idx=open_idx, counts=counts)
 
     def _nearest3_finish(self, h, stats):
         """The call's one host round trip (how many queries are pairs / open) and what follows from it: two exact dot products
         for the pairs, the exact search for the open queries.  -> keys [nq, 1]."""
-        corpus, queries, metric, id_offset = h["corpus"], h["queries"], h["metric"], h["id_offset"]
-        corpus_stats, bounds, coef5, plain = h["corpus_stats"], h["bounds"], h["coef5"], h["plain"]
-        keys, keys2, pair_idx, open_idx, counts = h["keys"], h["keys2"], h["pair_idx"], h["open_idx"], h["counts"]
-        nq = queries.n
-        if bounds is not None:
-            b_assign, b_ub, b_lb, b_pos = bounds
-        n_pair, n_open = (int(v) for v in counts.tolist())  # the call's one host round trip
+        corpus, queries, metric, id_offset, bounds, keys = h.corpus, h.queries, h.metric, h.id_offset, h.bounds, h.keys
+        pair_idx, open_idx = h.pair_idx, h.open_idx
+        n_pair, n_open = (int(v) for v in h.counts.tolist())  # the call's one host round trip
         psel = pair_idx[:n_pair]
-        # the one-pass keys of the rows decided below, as lvs_kmeans_bounds_fix needs them (taken before any exact score goes in)
+        # the one-pass keys of the rows decided below, as the bounds' fix needs them (taken before any exact score goes in)
         approx_pair = keys[psel].contiguous() if (bounds is not None and n_pair) else None
         approx_open = keys[open_idx[:n_open]].contiguous() if (bounds is not None and n_open) else None
-        if h["exact_scores"]:
-            self._c("lvs_rescore_keys", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, nq, corpus.d,
-                    metric, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), 1, _ptr(keys), self._stream())
-        exact2 = (ctypes.c_float * 2)(8e-6, 4e-6)  # float32 rounding of an exact distance, see nearest()
+        if h.exact_scores:
+            self._rescore(corpus, queries, metric, id_offset, keys)
         if n_pair:
             self._c("lvs_resolve_pairs", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, corpus.d, metric,
-                    _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(pair_idx), _ptr(counts), n_pair, _ptr(keys),
-                    _ptr(keys2), self._stream())
+                    _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(pair_idx), _ptr(h.counts), n_pair, _ptr(keys),
+                    _ptr(h.keys2), self._stream())
             if bounds is not None:
-                pos = psel if b_pos is None else b_pos[psel]
-                self._c("lvs_kmeans_bounds_fix", _ptr(approx_pair), _ptr(keys[psel].contiguous()),
-                        _ptr(queries.norms[psel].contiguous()), _ptr(pos), n_pair, _ptr(corpus_stats), ctypes.addressof(coef5),
-                        ctypes.addressof(exact2), int(id_offset), _ptr(b_assign), _ptr(b_ub), _ptr(b_lb), self._stream())
+                bounds.fix(approx_pair, keys[psel].contiguous(), queries.norms[psel].contiguous(), psel)
         if n_open:
             sel = open_idx[:n_open]
             sub = self.gather(queries, sel)
-            exact_keys = self.search_keys(corpus, sub, 1, metric, **plain)
+            exact_keys = self.search_keys(corpus, sub, 1, metric, id_offset=id_offset, one_pass=False)
             if bounds is not None:
-                pos = sel if b_pos is None else b_pos[sel]
-                self._c("lvs_kmeans_bounds_fix", _ptr(approx_open), _ptr(exact_keys), _ptr(sub.norms), _ptr(pos),
-                        n_open, _ptr(corpus_stats), ctypes.addressof(coef5), ctypes.addressof(exact2), int(id_offset),
-                        _ptr(b_assign), _ptr(b_ub), _ptr(b_lb), self._stream())
+                bounds.fix(approx_open, exact_keys, sub.norms, sel)
             keys[sel] = exact_keys
-        if stats is not None:
-            stats["uncertified"] = stats.get("uncertified", 0) + n_open + n_pair
-            stats["pairs"] = stats.get("pairs", 0) + n_pair
-            stats["open"] = stats.get("open", 0) + n_open
-            stats["queries"] = stats.get("queries", 0) + nq
+        self._count(stats, uncertified=n_open + n_pair, pairs=n_pair, open=n_open, queries=queries.n)
         return keys
 
     def nearest_begin(self, corpus: PackedRows, queries: PackedRows, metric: int, id_offset: int = 0, exact_scores: bool = True,
@@ -849,39 +865,26 @@ class HipBackend:
         stream ``nearest_finish`` ran on has been joined (its tensors were allocated on the stream of ``nearest_begin``)."""
         small = corpus.n <= _capi.NEAREST3_MAX_ROWS and not (corpus.mode == _capi.PACK_F16 and queries.mode == _capi.PACK_F16)
         if not small or queries.n == 0 or corpus.n == 0 or corpus.d != queries.d:
-            return {"keys_now": self.nearest(corpus, queries, metric, id_offset=id_offset, exact_scores=exact_scores,
-                                             corpus_stats=corpus_stats), "queries": queries}
+            return _NearestHandle(queries=queries, done=self.nearest(corpus, queries, metric, id_offset=id_offset,
+                                                                     exact_scores=exact_scores, corpus_stats=corpus_stats))
         coef, dpad = self._nearest_coef(corpus, queries, metric)
-        plain = dict(id_offset=id_offset, one_pass=False)
-        step = self._nearest3_step(corpus)
-        if queries.n <= step:
-            return self._nearest3_begin(corpus, queries, metric, id_offset, exact_scores, corpus_stats, None, coef, dpad, plain)
         # the same scratch budget as nearest() (ADVICE r05: a 3 M-row range x 16 384 centroids asked for 3.8 GB in one call):
         # the queries go through in chunks, one handle each; the launches of chunk i + 1 reuse the stream's scratch behind chunk
         # i's (same stream: ordered)
-        chunks = []
-        for q0 in range(0, queries.n, step):
-            q1 = min(queries.n, q0 + step)
-            chunks.append((q0, q1, self._nearest3_begin(corpus, self.slice_rows(queries, q0, q1), metric, id_offset, exact_scores,
-                                                        corpus_stats, None, coef, dpad, plain)))
-        return {"chunks": chunks, "queries": queries}
-
-    def _nearest3_step(self, corpus) -> int:
-        """Most queries one ``lvs_nearest3`` call may take inside the scratch budget (20 B per corpus tile and query)."""
-        per_q = max(1, int(self.lib.lvs_nearest3_workspace_bytes(1 << 20, corpus.n, corpus.d)) >> 20)
-        return max(1 << 16, (self.NEAREST3_WS_BUDGET // per_q) >> 16 << 16)
+        chunks = [(q0, q1, self._nearest3_begin(corpus, qs, metric, id_offset, exact_scores, corpus_stats, None, coef, dpad))
+                  for q0, q1, qs, _ in self._nearest3_chunks(corpus, queries, None)]
+        return chunks[0][2] if len(chunks) == 1 else _NearestHandle(queries=queries, chunks=chunks)
 
     def nearest_finish(self, handle, stats: dict | None = None):
-        if "keys_now" in handle:
-            if stats is not None:
-                stats["queries"] = stats.get("queries", 0) + handle["queries"].n
-            return handle["keys_now"]
-        if "chunks" in handle:
-            keys = self.torch.empty((handle["queries"].n, 1), dtype=self.torch.int64, device=self.device)
-            for q0, q1, h in handle["chunks"]:
-                keys[q0:q1] = self._nearest3_finish(h, stats)
-            return keys
-        return self._nearest3_finish(handle, stats)
+        if handle.done is not None:
+            self._count(stats, queries=handle.queries.n)
+            return handle.done
+        if handle.chunks is None:
+            return self._nearest3_finish(handle, stats)
+        keys = self.torch.empty((handle.queries.n, 1), dtype=self.torch.int64, device=self.device)
+        for q0, q1, h in handle.chunks:
+            keys[q0:q1] = self._nearest3_finish(h, stats)
+        return keys
 
     def kmeans_centroid_shift(self, c_old, c_new):
         """-> (delta float32 [k], top2 float32 [3]): how far every centroid moved, the largest and second largest shift."""
@@ -1315,13 +1318,9 @@ class HipBackend:
 
     def kmeans_accumulate_keys(self, x: PackedRows, keys, k: int, id_offset: int = 0):
         """The same straight from the assignment search's result keys [n(,1)] (no decode pass in between)."""
-        torch = self.torch
-        sums = torch.zeros((k, x.d), dtype=torch.float32, device=self.device)
-        counts = torch.zeros((k,), dtype=torch.float32, device=self.device)
-        need = int(self.lib.lvs_kmeans_accumulate_workspace_bytes(x.n, k))
-        ws = self._workspace(need)
-        self._c("lvs_kmeans_accumulate_keys", _ptr(x.rows), x.n, x.d, x.mode, _ptr(keys), int(id_offset), k, _ptr(sums),
-                _ptr(counts), _ptr(ws), int(ws.numel()), self._stream())
+        sums = self.torch.zeros((k, x.d), dtype=self.torch.float32, device=self.device)
+        counts = self.torch.zeros((k,), dtype=self.torch.float32, device=self.device)
+        self.kmeans_accumulate_keys_into(x, keys, k, sums, counts, id_offset)
         return sums, counts
 
     def kmeans_accumulate_keys_into(self, x: PackedRows, keys, k: int, sums, counts, id_offset: int = 0, workspace=None) -> None:
@@ -1346,32 +1345,31 @@ class HipBackend:
         self._c("lvs_kmeans_objective", _ptr(centroids), _ptr(sums), _ptr(counts), k, d, _ptr(x2), _ptr(out),
                 _ptr(self._obj_ws), int(self._obj_ws.numel()), self._stream())
 
+    def _centroid_image(self, centroids, mode: int, exp: int):
+        """-> (PackedRows for the image of ``centroids`` [k,d], float32 [2] for its statistics), both still to be written."""
+        torch = self.torch
+        k, d = int(centroids.shape[0]), int(centroids.shape[1])
+        rows = torch.empty((k, int(self.lib.lvs_packed_ld(d, mode))), dtype=torch.float16, device=self.device)
+        norms = torch.empty((k,), dtype=torch.float32, device=self.device)
+        cstats = torch.empty((2,), dtype=torch.float32, device=self.device)
+        return PackedRows(rows=rows, norms=norms, n=k, d=d, mode=mode, exp=int(exp)), cstats
+
     def kmeans_pack_centroids(self, centroids, mode: int, exp: int = 0):
         """-> (PackedRows of the centroids, device float32 [2] = (largest |c|^2, largest |lo part|^2)).  ``centroids`` are
         in the points' scaled domain already (``exp``: the points' pack exponent, recorded on the result)."""
-        torch = self.torch
-        k, d = int(centroids.shape[0]), int(centroids.shape[1])
-        ld = int(self.lib.lvs_packed_ld(d, mode))
-        rows = torch.empty((k, ld), dtype=torch.float16, device=self.device)
-        norms = torch.empty((k,), dtype=torch.float32, device=self.device)
-        cstats = torch.empty((2,), dtype=torch.float32, device=self.device)
-        self._c("lvs_kmeans_pack_centroids", _ptr(centroids), k, d, mode, _ptr(rows), _ptr(norms), _ptr(cstats),
+        pk, cstats = self._centroid_image(centroids, mode, exp)
+        self._c("lvs_kmeans_pack_centroids", _ptr(centroids), pk.n, pk.d, mode, _ptr(pk.rows), _ptr(pk.norms), _ptr(cstats),
                 self._stream())
-        return PackedRows(rows=rows, norms=norms, n=k, d=d, mode=mode, exp=int(exp)), cstats
+        return pk, cstats
 
     def kmeans_finish(self, sums, counts, centroids, n_train: int, mode: int, nsplit_out=None, exp: int = 0):
         """The rest of a faiss iteration after the sums, one C-ABI call, nothing read back: centroids (device float32
         [k,d], in place) = sums / counts where counts > 0 (compute_centroids), faiss's empty-cluster split on the device
         (``nsplit_out``: device int32 [1]), and the repacked centroids -> (PackedRows, stats) as ``kmeans_pack_centroids``."""
-        torch = self.torch
-        k, d = int(centroids.shape[0]), int(centroids.shape[1])
-        ld = int(self.lib.lvs_packed_ld(d, mode))
-        rows = torch.empty((k, ld), dtype=torch.float16, device=self.device)
-        norms = torch.empty((k,), dtype=torch.float32, device=self.device)
-        cstats = torch.empty((2,), dtype=torch.float32, device=self.device)
-        self._c("lvs_kmeans_update_centroids", _ptr(sums), _ptr(counts), k, d, int(n_train), _ptr(centroids),
-                _ptr(nsplit_out), mode, _ptr(rows), _ptr(norms), _ptr(cstats), self._stream())
-        return PackedRows(rows=rows, norms=norms, n=k, d=d, mode=mode, exp=int(exp)), cstats
+        pk, cstats = self._centroid_image(centroids, mode, exp)
+        self._c("lvs_kmeans_update_centroids", _ptr(sums), _ptr(counts), pk.n, pk.d, int(n_train), _ptr(centroids),
+                _ptr(nsplit_out), mode, _ptr(pk.rows), _ptr(pk.norms), _ptr(cstats), self._stream())
+        return pk, cstats
 
     def kmeans_iteration(self, x: PackedRows, x2, k: int, n_train_total: int, centroids, cpk: PackedRows, cstats, keys_out,
                          obj_out, nsplit_out=None, all_reduce=None, stats: dict | None = None) -> None:
@@ -1411,12 +1409,8 @@ class HipBackend:
             if errors:
                 raise errors[0]
             raise
-        if stats is not None:
-            n_pair, n_open = int(host_counts[0]), int(host_counts[1])
-            stats["uncertified"] = stats.get("uncertified", 0) + n_pair + n_open
-            stats["pairs"] = stats.get("pairs", 0) + n_pair
-            stats["open"] = stats.get("open", 0) + n_open
-            stats["queries"] = stats.get("queries", 0) + x.n
+        n_pair, n_open = int(host_counts[0]), int(host_counts[1])
+        self._count(stats, uncertified=n_open + n_pair, pairs=n_pair, open=n_open, queries=x.n)
 
     def kmeans_update_centroids(self, sums, counts, centroids) -> None:
         """centroids (device float32 [k,d], in place) = sums / counts where counts > 0 (faiss compute_centroids) - the

@@ -52,6 +52,230 @@ class KMeansResult:
     train_ids: np.ndarray  # rows used for training
 
 
+class _Rows:
+    """Where the rows of the ``n``-row matrix are: all in ``packed`` on every rank, or - ``sharded`` - only those at the
+    (ascending) positions ``local_pos``."""
+
+    def __init__(self, be, packed, n, local_pos, shard, process_group):
+        self.be, self.packed, self.n, self.process_group = be, packed, n, process_group
+        self.dist, self.rank, self.world = _dist.context(shard, process_group)
+        self.sharded = packed.n != n  # this rank holds only the rows at local_pos
+        self.local_pos = None if local_pos is None else np.asarray(local_pos, dtype=np.int64)
+        if self.sharded:
+            if local_pos is None:
+                raise ValueError("a partial device image needs local_pos (the positions of its rows)")
+            if len(self.local_pos) != packed.n:
+                raise ValueError("local_pos must name every row of the device image")
+            if self.dist is None:
+                raise ValueError("a partial device image needs shard=True and an initialised process group")
+
+    def local_rows(self, ids: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """(mask of `ids` held by this rank, their row numbers in `packed`)."""
+        if not self.sharded:
+            return np.ones(len(ids), bool), ids
+        local_pos = self.local_pos
+        at = np.searchsorted(local_pos, ids)
+        at[at >= len(local_pos)] = 0
+        held = local_pos[at] == ids if len(local_pos) else np.zeros(len(ids), bool)
+        return held, at[held]
+
+    def share(self, m: int) -> tuple[int, int]:
+        """This rank's contiguous slice [lo, hi) of ``m`` replicated rows."""
+        per = -(-m // self.world)
+        return min(m, self.rank * per), min(m, (self.rank + 1) * per)
+
+    def centroid_rows(self, ids: np.ndarray):
+        """float32 [len(ids), d] values of the rows `ids` on the device (every rank gets all of them)."""
+        be, packed = self.be, self.packed
+        held, rows = self.local_rows(ids)
+        if not self.sharded:
+            return be.unpack(packed, be.to_device(rows), raw=True)
+        import torch
+
+        vals = torch.zeros((len(ids), packed.d), dtype=torch.float32, device=packed.rows.device)
+        if held.any():
+            vals[be.to_device(np.flatnonzero(held))] = be.unpack(packed, be.to_device(rows), raw=True)
+        _dist.all_reduce_sum_([vals], self.process_group)  # every row is held by exactly one rank: x + 0 + ... is exact
+        return vals
+
+    def training_rows(self, train_ids: np.ndarray):
+        """The training rows this rank works on, as a device image."""
+        be, packed = self.be, self.packed
+        if self.sharded:
+            return be.gather(packed, be.to_device(self.local_rows(train_ids)[1]))
+        if self.dist is not None:
+            lo, hi = self.share(len(train_ids))
+            return be.gather(packed, be.to_device(train_ids[lo:hi]))
+        if len(train_ids) == self.n:
+            return packed
+        return be.gather(packed, be.to_device(train_ids))
+
+    def final_assignment(self, cpk, cstats) -> np.ndarray:
+        """Cluster id of every one of the ``n`` rows; with several ranks each assigns its rows and one all-gather follows."""
+        be, packed, n = self.be, self.packed, self.n
+        if self.dist is None:
+            mine = packed
+        elif self.sharded:
+            mine, pos = packed, self.local_pos
+        else:  # replicated rows: contiguous row slices
+            lo, hi = self.share(n)
+            mine, pos = be.slice_rows(packed, lo, hi), np.arange(lo, hi, dtype=np.int64)
+        keys = be.nearest(cpk, mine, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats)  # ids only: no rescoring pass
+        _, I = be.keys_to_result(keys, _capi.METRIC_L2)
+        if self.dist is None:
+            return np.asarray(I.reshape(-1).cpu().numpy(), dtype=np.int64)  # already int64: no copy
+        import torch
+
+        # ranks may hold different numbers of rows: exchange (position, cluster id) pairs padded to the largest share
+        cnt = torch.tensor([mine.n], dtype=torch.int64, device=I.device)
+        cmax = int(_dist.all_gather_rows(cnt, self.process_group).max().item())
+        pair = torch.full((2, cmax), -1, dtype=torch.int64, device=I.device)
+        pair[0, :mine.n] = be.to_device(pos)
+        pair[1, :mine.n] = I.reshape(-1)
+        allp = _dist.all_gather_rows(pair, self.process_group).cpu().numpy()  # [world, 2, cmax]
+        assign = np.full(n, -1, np.int64)
+        for r in range(self.world):
+            ok = allp[r, 0] >= 0
+            assign[allp[r, 0][ok]] = allp[r, 1][ok]
+        return assign
+
+
+class _Loop:
+    """The training loop's state: what every iteration reads (the rows, the centroids and their packed image) and what one
+    iteration leaves for the next.  ``choose`` picks the kind of iteration ONCE and sets up what that kind carries."""
+
+    def __init__(self, be, train, k, nt, niter, cmode, pexp, centroids, stats, rows: _Rows, want_keys: bool):
+        import torch
+
+        self.be, self.train, self.k, self.nt, self.cmode, self.pexp, self.stats = be, train, k, nt, cmode, pexp, stats
+        self.dist, self.process_group = rows.dist, rows.process_group
+        self.dev = dev = train.rows.device
+        self.centroids = centroids  # float32 [k,d], the rows' scaled domain; updated in place
+        self.cpk, self.cstats = be.kmeans_pack_centroids(centroids, cmode, exp=pexp)
+        self.x2 = train.norms.double().sum().reshape(1)  # sum of |x_i|^2 over this rank's training rows (constant over the iterations)
+        self.obj = torch.zeros((max(niter, 1),), dtype=torch.float64, device=dev)
+        self.nsplit = torch.zeros((max(niter, 1),), dtype=torch.int32, device=dev)
+        self.want_keys = want_keys  # the caller records a trace: every kind also returns its assignment's keys
+        self.c_old = None  # the bounds kind: the centroids before the update (kmeans_centroid_shift closes the common tail)
+
+    def choose(self, bounds, parts, niter):
+        """-> (the iteration: ``f(it) -> (sums, counts, keys)``, whether the common tail follows it), by today's conditions."""
+        import torch
+
+        be, train, k, dev = self.be, self.train, self.k, self.dev
+        use_bounds = bounds if bounds is not None else (train.n >= (1 << 20))
+        if bool(use_bounds) and self.cmode == _capi.PACK_SPLIT and hasattr(be, "kmeans_bounds_step") and k >= 2:
+            self.b_assign = torch.full((train.n,), -1, dtype=torch.int32, device=dev)
+            self.b_ub, self.b_lb = (torch.zeros((train.n,), dtype=torch.float32, device=dev) for _ in range(2))
+            self.keys = self.shift = self.top2 = None  # keys: the last assignment, None before the first
+            return self.with_bounds, True
+        if parts is None:
+            parts = PARTS_DEFAULT if train.n >= (1 << 21) else 1
+        fracs = [1.0 / int(parts)] * int(parts) if isinstance(parts, int) else [float(f) for f in parts]
+        if hasattr(be, "kmeans_accumulate_keys_into") and dev.type == "cuda" and len(fracs) > 1 and min(fracs) * train.n >= 65536:
+            self.side = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
+            self.side_ws = torch.empty(int(be.lib.lvs_kmeans_accumulate_workspace_bytes(train.n, k)) + 256, dtype=torch.uint8, device=dev)
+            self.cuts = range_cuts(train.n, fracs)
+            self.pipelined = PIPELINE_CERTIFICATES and hasattr(be, "nearest_begin")
+            return self.ranges, True
+        # one range, no distance bounds, fp32-accurate centroids of at most 16 384: the iteration is the ABI's single call
+        if (USE_ITERATION_OP and self.cmode == _capi.PACK_SPLIT and hasattr(be, "kmeans_iteration")
+                and k <= _capi.NEAREST3_MAX_ROWS and dev.type == "cuda" and niter > 0):
+            self.iter_keys = torch.empty((train.n,), dtype=torch.int64, device=dev)
+            return self.iteration_op, False
+        return self.all_rows, True
+
+    def nearest(self, rows, **kw):
+        return self.be.nearest(self.cpk, rows, _capi.METRIC_L2, exact_scores=False, corpus_stats=self.cstats, stats=self.stats, **kw)
+
+    def ranges(self, it):
+        """Ranges of rows: search range i, then its sums on the side stream while range i + 1 is searched.  Pipelined, the rest of
+        the certificate (the host's read of its two counts, the exact dot products of the pairs, the exact search of the open
+        rows: ``nearest_finish``) runs on the side stream too: range i - 1 settles once range i's search is queued."""
+        import torch
+
+        be, train, k, side = self.be, self.train, self.k, self.side
+        main = torch.cuda.current_stream(self.dev)
+        sums = torch.zeros((k, train.d), dtype=torch.float32, device=self.dev)
+        counts = torch.zeros((k,), dtype=torch.float32, device=self.dev)
+        held, kparts, last = [], [], None  # held: alive until the side stream is done with them (the wait below)
+
+        def settle(sub, found, searched_ev):
+            nonlocal last
+            with torch.cuda.stream(side):
+                side.wait_event(searched_ev)
+                kp = be.nearest_finish(found, stats=self.stats) if self.pipelined else found
+                be.kmeans_accumulate_keys_into(sub, kp, k, sums, counts, workspace=self.side_ws)
+                last = side.record_event()
+            kparts.append(kp)
+
+        searched = []  # ranges whose search is queued and whose tail is not: at most one, and only when pipelined
+        for i in range(len(self.cuts) - 1):
+            sub = be.slice_rows(train, self.cuts[i], self.cuts[i + 1])
+            if self.pipelined:
+                found = be.nearest_begin(self.cpk, sub, _capi.METRIC_L2, exact_scores=False, corpus_stats=self.cstats)
+            else:
+                found = self.nearest(sub)
+            searched.append((sub, found, main.record_event()))
+            held.append((sub, found))
+            if len(searched) > int(self.pipelined):
+                settle(*searched.pop(0))
+        for s in searched:
+            settle(*s)
+        main.wait_event(last)
+        return sums, counts, (torch.cat(kparts) if self.want_keys else None)
+
+    def iteration_op(self, it):
+        """The whole iteration - assignment, sums, objective, all-reduce, division + split + repack - is ONE C-ABI call
+        (lvs_kmeans_iteration): the same launches in the same order as the other kinds and the common tail issue one by one."""
+        reduce = (lambda t: _dist.all_reduce_sum_([t], self.process_group)) if self.dist is not None else None
+        self.be.kmeans_iteration(self.train, self.x2, self.k, self.nt, self.centroids, self.cpk, self.cstats, self.iter_keys,
+                                 self.obj[it:it + 1], self.nsplit[it:it + 1], all_reduce=reduce, stats=self.stats)
+        return None, None, self.iter_keys.reshape(-1, 1)
+
+    def all_rows(self, it):
+        keys = self.nearest(self.train)  # ids only ...
+        return (*self.be.kmeans_accumulate_keys(self.train, keys, self.k), keys)
+
+    def with_bounds(self, it):
+        be, train = self.be, self.train
+        # bounds moved by the last update: which rows may have changed their centroid?
+        act = be.kmeans_bounds_step(self.b_assign, self.b_ub, self.b_lb, self.shift, self.top2) if self.keys is not None else None
+        if self.keys is None or int(act.numel()) > train.n // 2:  # (almost) everything moved: search all rows in place
+            self.keys = self.nearest(train, bounds=(self.b_assign, self.b_ub, self.b_lb, None))
+            searched = train.n
+        else:
+            searched = int(act.numel())
+            if searched:
+                self.keys[act] = self.nearest(be.gather(train, act), bounds=(self.b_assign, self.b_ub, self.b_lb, act))
+        if self.stats is not None:
+            self.stats.setdefault("searched_rows", []).append(searched)
+        self.c_old = self.centroids.clone()
+        return (*be.kmeans_accumulate_keys(train, self.keys, self.k), self.keys)
+
+    def tail(self, it, sums, counts):
+        """What follows the sums in every kind but the iteration op (which does the same inside its call)."""
+        be = self.be
+        # ... because the objective (faiss: sum of the assignment distances) follows from the sums the update needs
+        # anyway:  sum_i |x_i - c_a(i)|^2 = sum_i |x_i|^2 - 2 sum_j c_j . S_j + sum_j n_j |c_j|^2   (float64, [k,d])
+        be.kmeans_objective(self.centroids, sums, counts, self.x2, self.obj[it:it + 1])
+        if self.dist is not None:
+            _dist.all_reduce_sum_([sums, counts, self.obj[it:it + 1]], self.process_group)
+        # centroid division + faiss split_clusters (same RNG stream on every rank) + repack, nothing read back
+        self.cpk, self.cstats = be.kmeans_finish(sums, counts, self.centroids, self.nt, self.cmode, self.nsplit[it:it + 1], exp=self.pexp)
+        if self.c_old is not None:
+            self.shift, self.top2 = be.kmeans_centroid_shift(self.c_old, self.centroids)
+
+
+def _mark(dev):
+    """A timing event recorded on the device's current stream."""
+    import torch
+
+    ev = torch.cuda.Event(enable_timing=True)
+    ev.record(torch.cuda.current_stream(dev))
+    return ev
+
+
 def kmeans(x, k: int, niter: int = 20, seed: int = 1234, max_points_per_centroid: int | None = 256, backend=None,
            pack_mode: int | None = None, packed=None, shard: bool = False, process_group=None,
            final_assign: bool = True, centroid_precision: str = "fp32", n_total: int | None = None,
@@ -106,7 +330,6 @@ def kmeans(x, k: int, niter: int = 20, seed: int = 1234, max_points_per_centroid
         if pack_mode is None:
             pack_mode = _capi.PACK_F16 if x.dtype == np.float16 else _capi.PACK_SPLIT
         packed = be.pack(x, pack_mode, exp="auto", check=True)
-    d = packed.d
     pexp = int(getattr(packed, "exp", 0))  # the device rows hold x * 2^pexp: centroids, sums and objectives below live in
     # that scaled domain (power-of-two scaling commutes with every float32 operation of the loop) and are unscaled at the end
     n = int(n_total) if n_total is not None else packed.n
@@ -116,225 +339,38 @@ def kmeans(x, k: int, niter: int = 20, seed: int = 1234, max_points_per_centroid
     if centroid_precision not in ("fp32", "fp16"):
         raise ValueError("centroid_precision must be 'fp32' or 'fp16'")
     cmode = _capi.PACK_SPLIT if centroid_precision == "fp32" else packed.mode
-    dist, rank, world = _dist.context(shard, process_group)
-    sharded_rows = packed.n != n  # this rank holds only the rows at local_pos
-    if sharded_rows:
-        if local_pos is None:
-            raise ValueError("a partial device image needs local_pos (the positions of its rows)")
-        local_pos = np.asarray(local_pos, dtype=np.int64)
-        if len(local_pos) != packed.n:
-            raise ValueError("local_pos must name every row of the device image")
-        if dist is None and packed.n != n:
-            raise ValueError("a partial device image needs shard=True and an initialised process group")
-
-    def local_rows(ids: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-        """(mask of `ids` held by this rank, their row numbers in `packed`)."""
-        if not sharded_rows:
-            return np.ones(len(ids), bool), ids
-        at = np.searchsorted(local_pos, ids)
-        at[at >= len(local_pos)] = 0
-        held = local_pos[at] == ids if len(local_pos) else np.zeros(len(ids), bool)
-        return held, at[held]
+    rows = _Rows(be, packed, n, local_pos, shard, process_group)
 
     train_ids = np.arange(n, dtype=np.int64)
     if max_points_per_centroid is not None and n > k * max_points_per_centroid:
         train_ids = be.rand_perm(n, seed, k * max_points_per_centroid)  # only the prefix is used: O(k * 256) host work
     nt = len(train_ids)
-    obj = np.zeros(niter, np.float32)
-    nsplit = np.zeros(niter, np.int64)
-
-    def centroid_rows(ids: np.ndarray):
-        """float32 [len(ids), d] values of the rows `ids` on the device (every rank gets all of them)."""
-        held, rows = local_rows(ids)
-        if not sharded_rows:
-            return be.unpack(packed, be.to_device(rows), raw=True)
-        import torch
-
-        vals = torch.zeros((len(ids), d), dtype=torch.float32, device=packed.rows.device)
-        if held.any():
-            vals[be.to_device(np.flatnonzero(held))] = be.unpack(packed, be.to_device(rows), raw=True)
-        _dist.all_reduce_sum_([vals], process_group)  # every row is held by exactly one rank: x + 0 + ... is exact
-        return vals
-
+    obj, nsplit = np.zeros(niter, np.float32), np.zeros(niter, np.int64)
     if nt == k:
-        centroids = centroid_rows(train_ids)  # faiss: "n == k: copy points as centroids and stop"
+        centroids = rows.centroid_rows(train_ids)  # faiss: "n == k: copy points as centroids and stop"
     else:
         perm = be.rand_perm(nt, seed + 1, k)
-        centroids = centroid_rows(train_ids[perm[:k]])
-        # the training rows this rank works on
-        if sharded_rows:
-            held, rows = local_rows(train_ids)
-            train = be.gather(packed, be.to_device(rows))
-        elif dist is not None:
-            per = -(-nt // world)
-            lo, hi = min(nt, rank * per), min(nt, (rank + 1) * per)
-            train = be.gather(packed, be.to_device(train_ids[lo:hi]))
-        elif nt == n:
-            train = packed
-        else:
-            train = be.gather(packed, be.to_device(train_ids))
-        import torch
-
-        dev = train.rows.device
-        x2 = train.norms.double().sum().reshape(1)  # sum of |x_i|^2 over this rank's training rows (constant over the iterations)
-        obj_dev = torch.zeros((max(niter, 1),), dtype=torch.float64, device=dev)
-        nsplit_dev = torch.zeros((max(niter, 1),), dtype=torch.int32, device=dev)
-        cpk, cstats = be.kmeans_pack_centroids(centroids, cmode, exp=pexp)
-        use_bounds = bounds if bounds is not None else (train.n >= (1 << 20))
-        use_bounds = bool(use_bounds) and cmode == _capi.PACK_SPLIT and hasattr(be, "kmeans_bounds_step") and k >= 2
-        if use_bounds:
-            b_assign = torch.full((train.n,), -1, dtype=torch.int32, device=dev)
-            b_ub = torch.zeros((train.n,), dtype=torch.float32, device=dev)
-            b_lb = torch.zeros((train.n,), dtype=torch.float32, device=dev)
-            keys = None
+        centroids = rows.centroid_rows(train_ids[perm[:k]])
+        loop = _Loop(be, rows.training_rows(train_ids), k, nt, niter, cmode, pexp, centroids, stats, rows, trace is not None)
+        iterate, then_tail = loop.choose(bounds, parts, niter)
         # stats["time_iterations"] = True: device time of every iteration from events on the launch stream -> stats["iteration_ms"]
-        timed = stats is not None and bool(stats.get("time_iterations")) and dev.type == "cuda"
-        marks = []
-        if parts is None:
-            parts = PARTS_DEFAULT if train.n >= (1 << 21) else 1
-        fracs = [1.0 / int(parts)] * int(parts) if isinstance(parts, int) else [float(f) for f in parts]
-        can_overlap = not use_bounds and hasattr(be, "kmeans_accumulate_keys_into") and dev.type == "cuda"
-        nparts = len(fracs) if (can_overlap and min(fracs) * train.n >= 65536) else 1
-        pipelined = nparts > 1 and PIPELINE_CERTIFICATES and hasattr(be, "nearest_begin")
-        # one range, no distance bounds, fp32-accurate centroids of at most 16 384: the iteration is the ABI's single call
-        use_iter_op = (USE_ITERATION_OP and nparts == 1 and not use_bounds and cmode == _capi.PACK_SPLIT and hasattr(be, "kmeans_iteration")
-                       and k <= _capi.NEAREST3_MAX_ROWS and dev.type == "cuda" and niter > 0)
-        if use_iter_op:
-            iter_keys = torch.empty((train.n,), dtype=torch.int64, device=dev)
-        if nparts > 1:
-            side = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
-            side_ws = torch.empty(int(be.lib.lvs_kmeans_accumulate_workspace_bytes(train.n, k)) + 256, dtype=torch.uint8, device=dev)
-            cuts = range_cuts(train.n, fracs)
+        marks = [] if (stats is not None and bool(stats.get("time_iterations")) and loop.dev.type == "cuda") else None
         for it in range(niter):
-            if timed:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record(torch.cuda.current_stream(dev))
-                marks.append(ev)
-            if nparts > 1:
-                # ranges of rows: search range i, then its sums on the side stream while range i + 1 is searched
-                main = torch.cuda.current_stream(dev)
-                sums = torch.zeros((k, d), dtype=torch.float32, device=dev)
-                counts = torch.zeros((k,), dtype=torch.float32, device=dev)
-                held, kparts, last = [], [], None
-
-                def settle(sub, handle, searched_ev):
-                    # everything of a range that follows its one-pass search - the host's read of the certificate's two counts,
-                    # the exact dot products of the pairs, the exact search of the open rows, the in-row-order sums - on the
-                    # side stream, while the main stream already runs the next range's search
-                    nonlocal last
-                    with torch.cuda.stream(side):
-                        side.wait_event(searched_ev)
-                        kp = be.nearest_finish(handle, stats=stats)
-                        be.kmeans_accumulate_keys_into(sub, kp, k, sums, counts, workspace=side_ws)
-                        last = side.record_event()
-                    kparts.append(kp)
-
-                pending = None
-                for i in range(nparts):
-                    sub = be.slice_rows(train, cuts[i], cuts[i + 1])
-                    if pipelined:
-                        handle = be.nearest_begin(cpk, sub, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats)
-                        ev = main.record_event()
-                        held.append((sub, handle))  # alive until the side stream is done with them (the wait below)
-                        if pending is not None:
-                            settle(*pending)  # range i - 1 settles while range i's search (already queued) runs
-                        pending = (sub, handle, ev)
-                        continue
-                    kp = be.nearest(cpk, sub, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats, stats=stats)
-                    searched_ev = main.record_event()
-                    with torch.cuda.stream(side):
-                        side.wait_event(searched_ev)
-                        be.kmeans_accumulate_keys_into(sub, kp, k, sums, counts, workspace=side_ws)
-                        last = side.record_event()
-                    held.append(kp)  # alive until the side stream is done with it (the wait below)
-                    kparts.append(kp)
-                if pending is not None:
-                    settle(*pending)
-                main.wait_event(last)
-                if trace is not None:
-                    trace.append({"centroids": centroids.clone(), "keys": torch.cat(kparts)})
-                del held, kparts, pending
-            elif not use_bounds and use_iter_op:
-                # the whole iteration - assignment, sums, objective, all-reduce, division + split + repack - is ONE C-ABI call
-                # (lvs_kmeans_iteration): the same launches in the same order as the branches below issue one by one
-                if trace is not None:
-                    c_before = centroids.clone()
-                be.kmeans_iteration(train, x2, k, nt, centroids, cpk, cstats, iter_keys, obj_dev[it:it + 1], nsplit_dev[it:it + 1],
-                                    all_reduce=(lambda t: _dist.all_reduce_sum_([t], process_group)) if dist is not None else None,
-                                    stats=stats)
-                if trace is not None:
-                    trace.append({"centroids": c_before, "keys": iter_keys.clone().reshape(-1, 1)})
-                continue
-            elif not use_bounds:
-                keys = be.nearest(cpk, train, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats, stats=stats)  # ids only ...
-            else:
-                act = None
-                if keys is not None:  # bounds moved by the last update: which rows may have changed their centroid?
-                    act = be.kmeans_bounds_step(b_assign, b_ub, b_lb, shift, top2)
-                if keys is None or int(act.numel()) > train.n // 2:  # (almost) everything moved: search all rows in place
-                    keys = be.nearest(cpk, train, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats, stats=stats,
-                                      bounds=(b_assign, b_ub, b_lb, None))
-                    searched = train.n
-                elif int(act.numel()):
-                    sub = be.gather(train, act)
-                    keys[act] = be.nearest(cpk, sub, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats, stats=stats,
-                                           bounds=(b_assign, b_ub, b_lb, act))
-                    searched = int(act.numel())
-                else:
-                    searched = 0
-                if stats is not None:
-                    stats.setdefault("searched_rows", []).append(searched)
-                c_old = centroids.clone()
-            if nparts == 1:
-                if trace is not None:
-                    trace.append({"centroids": centroids.clone(), "keys": keys.clone()})
-                sums, counts = be.kmeans_accumulate_keys(train, keys, k)
-            # ... because the objective (faiss: sum of the assignment distances) follows from the sums the update needs
-            # anyway:  sum_i |x_i - c_a(i)|^2 = sum_i |x_i|^2 - 2 sum_j c_j . S_j + sum_j n_j |c_j|^2   (float64, [k,d])
-            be.kmeans_objective(centroids, sums, counts, x2, obj_dev[it:it + 1])
-            if dist is not None:
-                _dist.all_reduce_sum_([sums, counts, obj_dev[it:it + 1]], process_group)
-            # centroid division + faiss split_clusters (same RNG stream on every rank) + repack, nothing read back
-            cpk, cstats = be.kmeans_finish(sums, counts, centroids, nt, cmode, nsplit_dev[it:it + 1], exp=pexp)
-            if use_bounds:
-                shift, top2 = be.kmeans_centroid_shift(c_old, centroids)
-        if timed and marks:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record(torch.cuda.current_stream(dev))
-            ev.synchronize()
-            marks.append(ev)
+            if marks is not None:
+                marks.append(_mark(loop.dev))
+            c_before = centroids.clone() if trace is not None else None
+            sums, counts, keys = iterate(it)
+            if trace is not None:
+                trace.append({"centroids": c_before, "keys": keys.clone()})
+            if then_tail:  # objective, all-reduce, division + split + repack; the iteration op has done them inside its call
+                loop.tail(it, sums, counts)
+        if marks:
+            marks.append(_mark(loop.dev))
+            marks[-1].synchronize()
             stats["iteration_ms"] = [float(a.elapsed_time(b)) for a, b in zip(marks[:-1], marks[1:])]
-        obj[:] = (obj_dev[:niter].cpu().numpy() * 2.0 ** (-2 * pexp)).astype(np.float32)
-        nsplit[:] = nsplit_dev[:niter].cpu().numpy()
-    assign = np.zeros(0, np.int64)
-    if final_assign:
-        cpk, cstats = be.kmeans_pack_centroids(centroids, cmode, exp=pexp)
-        if dist is None:
-            keys = be.nearest(cpk, packed, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats)  # ids only: no rescoring pass
-            _, I = be.keys_to_result(keys, _capi.METRIC_L2)
-            assign = np.asarray(I.reshape(-1).cpu().numpy(), dtype=np.int64)  # already int64: no copy
-        else:
-            import torch
-
-            if sharded_rows:
-                mine, pos = packed, local_pos
-            else:  # replicated rows: contiguous row slices
-                per = -(-n // world)
-                lo, hi = min(n, rank * per), min(n, (rank + 1) * per)
-                mine, pos = be.slice_rows(packed, lo, hi), np.arange(lo, hi, dtype=np.int64)
-            keys = be.nearest(cpk, mine, _capi.METRIC_L2, exact_scores=False, corpus_stats=cstats)
-            _, I = be.keys_to_result(keys, _capi.METRIC_L2)
-            # ranks may hold different numbers of rows: exchange (position, cluster id) pairs padded to the largest share
-            cnt = torch.tensor([mine.n], dtype=torch.int64, device=I.device)
-            cmax = int(_dist.all_gather_rows(cnt, process_group).max().item())
-            pair = torch.full((2, cmax), -1, dtype=torch.int64, device=I.device)
-            pair[0, :mine.n] = be.to_device(pos)
-            pair[1, :mine.n] = I.reshape(-1)
-            allp = _dist.all_gather_rows(pair, process_group).cpu().numpy()  # [world, 2, cmax]
-            assign = np.full(n, -1, np.int64)
-            for r in range(world):
-                ok = allp[r, 0] >= 0
-                assign[allp[r, 0][ok]] = allp[r, 1][ok]
+        obj[:] = (loop.obj[:niter].cpu().numpy() * 2.0 ** (-2 * pexp)).astype(np.float32)
+        nsplit[:] = loop.nsplit[:niter].cpu().numpy()
+    assign = rows.final_assignment(*be.kmeans_pack_centroids(centroids, cmode, exp=pexp)) if final_assign else np.zeros(0, np.int64)
     cent = np.asarray(centroids.cpu().numpy(), np.float32)
     if pexp:
         cent = (cent * np.float32(2.0 ** -pexp)).astype(np.float32)  # exact

@@ -678,13 +678,51 @@ def test_nearest_begin_chunks_its_queries_inside_the_scratch_budget(hip_backend,
     assert be._nearest3_step(cb) == 1 << 16
     stats = {}
     h = be.nearest_begin(cb, cq, L2, exact_scores=False)
-    assert "chunks" in h and len(h["chunks"]) == 3
+    assert h.chunks is not None and len(h.chunks) == 3
     two = be.nearest_finish(h, stats=stats)
     assert stats["queries"] == nq
     chunked = be.nearest(cb, cq, L2, exact_scores=False)
     import torch
 
     assert bool(torch.equal(two, whole)) and bool(torch.equal(chunked, whole))
+
+
+def test_chunked_nearest_with_bounds_equals_the_single_call(hip_backend, monkeypatch):
+    """`nearest(..., bounds=...)` beyond one chunk of `_nearest3_step` queries (the bounds tests above stay below it): with a
+    budget that forces a first, a middle and a last chunk the keys and the Hamerly bounds are, bit for bit, those of the single
+    call - with the bounds at the queries' own positions and at a fixed permutation of them.  Three equal corpus rows and two
+    equal ones put open rows and pairs (both uses of the bounds' fix) into every chunk."""
+    import torch
+
+    be = hip_backend
+    rng = np.random.default_rng(78)
+    nq, nb, d = 150_000, 64, 96
+    xb = rng.standard_normal((nb, d)).astype(np.float32)
+    xb[1] = xb[2] = xb[0]
+    xb[4] = xb[3]
+    xq = (xb[rng.integers(0, nb, nq)] + 0.3 * rng.standard_normal((nq, d))).astype(np.float32)
+    cq = be.pack(xq, SPLIT)
+    cb, cstats = be.kmeans_pack_centroids(be.to_device(xb), SPLIT)
+
+    def run(positions):
+        assign = torch.full((nq,), -1, dtype=torch.int32, device=be.device)
+        ub = torch.zeros((nq,), dtype=torch.float32, device=be.device)
+        lb = torch.zeros((nq,), dtype=torch.float32, device=be.device)
+        stats = {}
+        keys = be.nearest(cb, cq, L2, exact_scores=False, corpus_stats=cstats, stats=stats, bounds=(assign, ub, lb, positions))
+        assert stats["queries"] == nq and stats["pairs"] > 0 and stats["open"] > 0
+        return keys, assign, ub, lb
+
+    whole = run(None)
+    assert int(whole[1].min()) >= 0  # every row got its bounds
+    per_q = max(1, int(be.lib.lvs_nearest3_workspace_bytes(1 << 20, nb, d)) >> 20)
+    monkeypatch.setattr(type(be), "NEAREST3_WS_BUDGET", per_q * (1 << 16))  # step = 65 536 queries -> 3 chunks
+    assert be._nearest3_step(cb) == 1 << 16
+    assert all(bool(torch.equal(a, b)) for a, b in zip(run(None), whole))
+    perm = be.to_device(np.random.default_rng(79).permutation(nq).astype(np.int64))
+    keys, *moved = run(perm)
+    assert bool(torch.equal(keys, whole[0]))
+    assert all(bool(torch.equal(a[perm], b)) for a, b in zip(moved, whole[1:]))
 
 
 @pytest.mark.parametrize("mode", [F16, SPLIT])

@@ -23,7 +23,7 @@ for rnd in range(2):
     for skew in ("0", "1"):
         os.environ["LVS_ASSIGN_SKEW"] = skew
         coef, dpad = be._nearest_coef(cpk, pk, _capi.METRIC_L2)
-        one_pass = lambda: be._nearest3_begin(cpk, pk, _capi.METRIC_L2, 0, False, cstats, None, coef, dpad, {})["keys"]
+        one_pass = lambda: be._nearest3_begin(cpk, pk, _capi.METRIC_L2, 0, False, cstats, None, coef, dpad).keys
         keys = one_pass()
         be.synchronize()
         be.timing_enable(True)
