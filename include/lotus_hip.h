@@ -47,7 +47,9 @@ extern "C" {
                                 lvs_ivf_pq_search_workspace_bytes, lvs_ivf_pq_search_keys, LVS_KERNEL_IVF_PQ); exact re-ranking
                                 of a first stage's candidates (lvs_refine_keys, LVS_KERNEL_REFINE); a row selector in the
                                 three list scans (lvs_ivf_search_keys_sel, lvs_ivf_sq8_search_keys_sel,
-                                lvs_ivf_pq_search_keys_sel) - the plain entries are these with sel_bits = NULL */
+                                lvs_ivf_pq_search_keys_sel) - the plain entries are these with sel_bits = NULL; the threshold
+                                search through the lists (lvs_ivf_range_workspace_bytes, lvs_ivf_range_search,
+                                LVS_KERNEL_IVF_RANGE) */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -462,6 +464,31 @@ int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int64_t nb, con
                                 const float* xq_norms_sq, int32_t d, int32_t metric, int32_t nprobe, int32_t k,
                                 uint64_t* out_keys, int32_t* out_probe, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- IVF threshold search (faiss `IndexIVF::range_search`): every row of a query's probed lists whose EXACT score exceeds a
+ * threshold, instead of the k best.  The rows are scored from the flat image whatever codes a store keeps beside it. ---- */
+/* scratch of lvs_ivf_range_search (centroids and queries packed with `pack`), chunked and bounded as
+ * lvs_ivf_search_workspace_bytes.  LVS_EUNSUPPORTED: lvs_ivf_range_kernel keeps a tile's 32 queries in LDS (and nothing else:
+ * no candidate lists) and cannot take this d - hi|lo queries: d > 1216; fp16 queries: d > 2496; search such shapes with
+ * lvs_range_join; lvs_ivf_range_search returns the same status for them.  LVS_EINVAL: bad arguments. */
+int64_t lvs_ivf_range_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t pack);
+/* Threshold search through the lists, everything on `stream`, no synchronisation:
+ *   1. + 2. the coarse step and the grouping of the (query, probe rank) pairs by list, exactly lvs_ivf_search_keys's;
+ *   3. lvs_ivf_range_kernel: per list, its rows gathered from xb against the queries that probe it; every (query, row) with
+ *      score > threshold * 2^score_exp - strict, compared in fp32 in the kernel's scaled domain like lvs_range_join - is
+ *      appended to (out_q, out_j, out_s): the query's number in THIS call, the global row number, score * 2^-score_exp.
+ * The score is the inner product, or MINUS the squared L2 distance (a radius r^2 is threshold = -r^2).  sel_bits: as in
+ * lvs_ivf_search_keys_sel (NULL: every row).  q_rows (nullable, device uint32 [nq]): the row that query i IS - never paired
+ * with it (a self-join).  *out_count (device, zeroed by the caller) counts every hit of the call; only the first `capacity`
+ * are stored and nothing is written at or past `capacity`: a caller that reads a count above its capacity runs again with
+ * larger buffers.  The pair order is unspecified; a (query, row) appears once (a row is in one list, a query probes a list
+ * once).  1 <= nprobe <= min(nlist, 2048).  The norms: squared L2 only. */
+int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq, const int64_t* offsets,
+                             const uint32_t* rows, const uint32_t* sel_bits, int32_t nlist, const void* centroids,
+                             int32_t c_pack, const float* c_norms_sq, const void* xq, int32_t xq_pack, int64_t nq,
+                             const float* xq_norms_sq, const uint32_t* q_rows, int32_t d, int32_t metric, int32_t nprobe,
+                             float threshold, int32_t score_exp, int64_t capacity, int64_t* out_q, int64_t* out_j, float* out_s,
+                             uint64_t* out_count, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- IVF-SQ8: IVF-Flat's lists and coarse step, the rows scored from 8-bit codes of their residuals (faiss
  * "IVF<nlist>,SQ8": ScalarQuantizer QT_8bit, by_residual).  Per dimension j, with vmin / vdiff trained by the caller:
  *   r = x - c_l (x: the stored row value, c_l: its list's centroid), code_j = floor(255 clamp((r_j - vmin_j) / vdiff_j, 0, 1))
@@ -581,6 +608,8 @@ int32_t lvs_timing_read(double* out_total_ms, int64_t* out_launches);
 #define LVS_KERNEL_IVF_PQ 6 /* lvs_ivf_pq_lut_kernel + lvs_ivf_pq_scan_kernel: one query's table x its probed lists' PQ codes
                                (lvs_ivf_pq_search_keys) */
 #define LVS_KERNEL_REFINE 7 /* lvs_refine_kernel: one wave re-scores a query's candidate rows exactly (lvs_refine_keys) */
+#define LVS_KERNEL_IVF_RANGE 8 /* lvs_ivf_range_kernel: one inverted list x up to 32 probing queries, hits above a threshold
+                                  (lvs_ivf_range_search) */
 int32_t lvs_timing_read_calls(double* out_total_ms, int64_t* out_launches, int64_t* out_calls, int32_t* out_kernel);
 
 #ifdef __cplusplus

@@ -116,6 +116,9 @@ SIGNATURES = {
                                       _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "lvs_ivf_pq_search_keys_sel": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32,
                                           _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "lvs_ivf_range_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "lvs_ivf_range_search": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32,
+                                    _i32, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "lvs_refine_keys": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "lvs_timing_enable": (_i32, [_i32]),
     "lvs_timing_read": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

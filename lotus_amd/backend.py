@@ -40,6 +40,11 @@ def ivf_fits(d: int, k: int, mode: int) -> bool:
     return int(_capi.load().lvs_ivf_search_workspace_bytes(1, 1, 1, int(d), int(k), int(mode))) >= 0
 
 
+def ivf_range_fits(d: int, mode: int) -> bool:
+    """Host-only query of the library: does ``lvs_ivf_range_search`` take this dimension and pack mode?"""
+    return int(_capi.load().lvs_ivf_range_workspace_bytes(1, 1, 1, int(d), int(mode))) >= 0
+
+
 @dataclass
 class IvfSq8Lists:
     """The 8-bit residual codes of an IVF-SQ8 index beside its ``IvfLists``, all in the image's stored scale (values x 2^exp)."""
@@ -1032,6 +1037,66 @@ class HipBackend:
                 int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
         return (keys, probe) if want_probe else keys
 
+    # ---- threshold search through the lists ----
+    IVF_RANGE_CHUNK_ROWS = 65536  # query rows per C call, each with its own pair buffer (as RANGE_CHUNK_ROWS)
+
+    def ivf_range_fits(self, d: int, mode: int) -> bool:
+        """Can ``lvs_ivf_range_kernel`` serve queries of dimension ``d`` packed with ``mode``?  Its LDS image holds a tile's
+        queries and no lists, so the bound is wider than ``ivf_fits``'s; callers join the other shapes exactly."""
+        return ivf_range_fits(d, mode)
+
+    def ivf_range_search(self, corpus: PackedRows, lists: IvfLists, queries: PackedRows, threshold: float, metric: int,
+                         nprobe: int, q_rows=None, sel=None, capacity: int = 1 << 22):
+        """All (query, row, score) with score > threshold over the rows of each query's ``nprobe`` best lists
+        (``lvs_ivf_range_search``): three device tensors (int64, int64, float32), order unspecified.  The score is the inner
+        product or minus the squared distance, exact whatever codes the store keeps.  ``q_rows`` (device int32 tensor holding
+        uint32 row numbers, [nq]): query i is that row and is not paired with it.  ``sel``: ``row_bitmap``'s selector.
+
+        The queries go through in chunks with ``range_join``'s count-then-rerun protocol: a chunk that counted more than
+        ``capacity`` pairs - and only that chunk - runs again with buffers of the counted size."""
+        torch = self.torch
+        if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
+            raise ValueError("squared L2 needs both operands packed with the same scale exponent")
+        if sel is not None and int(sel.numel()) != -(-corpus.n // 32):
+            raise ValueError(f"the row selector has {int(sel.numel())} words for {corpus.n} rows")
+        if q_rows is not None and int(q_rows.numel()) != queries.n:
+            raise ValueError(f"q_rows names {int(q_rows.numel())} rows for {queries.n} queries")
+        cpk = lists.centroids
+        step = self.IVF_RANGE_CHUNK_ROWS
+        outs = []
+        cnt = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        oq = oj = os_ = None
+        for c0 in range(0, queries.n, step):
+            c1 = min(queries.n, c0 + step)
+            qs = self.slice_rows(queries, c0, c1)
+            need = int(self.lib.lvs_ivf_range_workspace_bytes(qs.n, lists.nlist, int(nprobe), corpus.d, qs.mode))
+            if need < 0:
+                raise LotusHipError(f"lvs_ivf_range_workspace_bytes rejected nq={qs.n} nlist={lists.nlist} nprobe={nprobe} "
+                                    f"d={corpus.d}")
+            ws = self._workspace(need)
+            cap = int(capacity)
+            while True:
+                if oq is None or oq.numel() < cap:
+                    oq = torch.empty((cap,), dtype=torch.int64, device=self.device)
+                    oj = torch.empty((cap,), dtype=torch.int64, device=self.device)
+                    os_ = torch.empty((cap,), dtype=torch.float32, device=self.device)
+                cnt.zero_()
+                self._c("lvs_ivf_range_search", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets),
+                        _ptr(lists.rows), _ptr(sel), lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(qs.rows),
+                        qs.mode, qs.n, _ptr(qs.norms), _ptr(q_rows[c0:c1]) if q_rows is not None else None, corpus.d, metric,
+                        int(nprobe), float(threshold), self.score_exp_of(corpus, qs), cap, _ptr(oq), _ptr(oj), _ptr(os_),
+                        _ptr(cnt), _ptr(ws), int(ws.numel()), self._stream())
+                n = int(cnt.item())
+                if n <= cap:
+                    break
+                cap = n  # counted but not stored: size the buffers and run this chunk again
+            if n:
+                outs.append((oq[:n] + c0, oj[:n].clone(), os_[:n].clone()))
+        if not outs:
+            e = torch.empty((0,), dtype=torch.int64, device=self.device)
+            return e, e.clone(), torch.empty((0,), dtype=torch.float32, device=self.device)
+        return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), torch.cat([o[2] for o in outs]))
+
     # ---- IVF-SQ8 ----
     SQ8_TRAIN_CHUNK_ROWS = 65536  # training rows unpacked at a time while the residual ranges are taken
 
@@ -1442,7 +1507,7 @@ class HipBackend:
         _capi.check(self.lib.lvs_timing_enable(int(on)))
 
     KERNEL_NAMES = {0: "lvs_tile_kernel", 1: "lvs_stream_kernel", 2: "lvs_rq_kernel", 3: "lvs_rj_kernel", 4: "lvs_ivf_scan_kernel",
-                    5: "lvs_ivf_sq8_scan_kernel", 6: "lvs_ivf_pq_scan_kernel", 7: "lvs_refine_kernel"}
+                    5: "lvs_ivf_sq8_scan_kernel", 6: "lvs_ivf_pq_scan_kernel", 7: "lvs_refine_kernel", 8: "lvs_ivf_range_kernel"}
 
     def timing_read(self):
         """-> (total ms of the dominant kernel's launches, searches that timed at least one): total / searches = kernel time per

@@ -2331,6 +2331,114 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
                                    stream);
 }
 
+// ---- threshold search through the lists (faiss IndexIVF::range_search): lvs_ivf_range_kernel over the full-precision rows
+namespace {
+// does lvs_ivf_range_kernel's LDS image (the tile's query fragments + the slot table, no lists) fit?  hi|lo queries: d <= 1216;
+// fp16 queries: d <= 2496
+bool ivf_range_fits(int32_t d, int32_t xq_pack) {
+    const int jper = (int)(lvs_round_up(d, LVS_BK) / 16);
+    return lvs_ivf_range_lds_bytes((xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper) <= 160 * 1024;
+}
+// the scratch of a chunk is the tiled searches' without parts (k = 0): no lists come back, the pairs go to the caller's buffers
+bool ivf_range_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t c_pack, int32_t xq_pack, IvfLayout& L) {
+    return ivf_plan(nq, nlist, nprobe, d, 0, c_pack, xq_pack, 0, true, L);
+}
+}  // namespace
+
+extern "C" int64_t lvs_ivf_range_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t pack) {
+    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0) return LVS_EINVAL;
+    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
+    if (!ivf_range_fits(d, pack)) return LVS_EUNSUPPORTED;  // the caller joins such shapes exactly
+    IvfLayout L;
+    if (!ivf_range_plan(nq, nlist, nprobe, d, pack, pack, L)) return LVS_EINVAL;
+    return L.total;
+}
+
+// The driver is ivf_search_chunks's sibling: the same plan, coarse step, pair grouping and tiling per chunk of queries; where
+// the searches scan into parts and merge them, every chunk's launch appends to the call's one pair list.
+extern "C" int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
+                                        const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits, int32_t nlist,
+                                        const void* centroids, int32_t c_pack, const float* c_norms_sq, const void* xq,
+                                        int32_t xq_pack, int64_t nq, const float* xq_norms_sq, const uint32_t* q_rows, int32_t d,
+                                        int32_t metric, int32_t nprobe, float threshold, int32_t score_exp, int64_t capacity,
+                                        int64_t* out_q, int64_t* out_j, float* out_s, uint64_t* out_count, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+    const int32_t ok = ivf_check_search(metric, nb, nq, d, nlist, 1, 1, nprobe, 1, xb_pack, xq_pack, c_pack);
+    if (ok != LVS_OK) return ok;
+    LVS_REQUIRE(score_exp >= -120 && score_exp <= 120, "score_exp %d out of range", score_exp);
+    LVS_REQUIRE(capacity >= 0 && out_count, "bad output buffers");
+    if (nq == 0) return LVS_OK;
+    LVS_REQUIRE(xb && offsets && rows && centroids && xq && workspace && (capacity == 0 || (out_q && out_j && out_s)), "NULL buffer");
+    LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
+    Plan p;
+    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p) == LVS_OK, "bad plan");
+    if (!ivf_range_fits(d, xq_pack)) {
+        lvs_set_error("d=%d does not fit the threshold scan's LDS (see lvs_ivf_range_workspace_bytes)", d);
+        return LVS_EUNSUPPORTED;
+    }
+    IvfLayout L;
+    LVS_REQUIRE(ivf_range_plan(nq, nlist, nprobe, d, c_pack, xq_pack, L), "shape beyond the IVF search");
+    if (workspace_bytes < L.total) {
+        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
+        return LVS_ENOMEM;
+    }
+    LvsIvfRangeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xb = xb;
+    a.bn = xb_norms_sq;
+    a.rows = rows;
+    a.offsets = offsets;
+    a.sel = sel_bits;
+    a.out_q = (long long*)out_q;
+    a.out_j = (long long*)out_j;
+    a.out_s = out_s;
+    a.out_count = (unsigned long long*)out_count;
+    a.capacity = capacity;
+    a.ldb = p.ldb;
+    a.ldq = p.ldq;
+    a.nlist = nlist;
+    a.nprobe = nprobe;
+    a.metric = metric;
+    a.jper = p.dpad / 16;
+    a.nseg = p.nseg;
+    a.nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * a.jper;
+    for (int i = 0; i < 3; ++i) {
+        a.seg_c[i] = p.seg_c[i];
+        a.seg_b[i] = p.seg_q[i] == 0 ? 0 : a.jper;
+    }
+    a.threshold = threshold * ldexpf(1.0f, score_exp);  // the device scores are 2^score_exp x the caller's (exact)
+    a.out_scale = ldexpf(1.0f, -score_exp);
+    LVS_DEVICE_GUARD(stream);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)workspace;
+    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
+    const size_t qrow_bytes = (size_t)p.ldq * 2;
+    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
+        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
+        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
+        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
+        {
+            TimingPause pause;
+            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq, qn_c,
+                                                    0, nullptr, coarse, w, L.flat_bytes, stream);
+            if (rc != LVS_OK) return rc;
+        }
+        const int32_t rc = lvs_bucket_positions(coarse, nullptr, cn * nprobe, nlist, 0, w + L.off_sort, L.sort_bytes, st, &a.pairs,
+                                                &a.pair_offs);
+        if (rc != LVS_OK) return rc;
+        LVS_HIP_CHECK(lvs_ivf_tiles_launch(a.pair_offs, nlist, (uint32_t*)(w + L.off_tiles), (uint32_t*)(w + L.off_items), st));
+        a.tile_offs = (const uint32_t*)(w + L.off_tiles);
+        a.item_list = (const uint32_t*)(w + L.off_items);
+        a.xq = xq_c;
+        a.qn = qn_c;
+        a.q_rows = q_rows ? q_rows + q0 : nullptr;
+        a.q_base = q0;
+        ScopedKernelTimer timer(st, LVS_KERNEL_IVF_RANGE, q0 > 0);
+        LVS_HIP_CHECK(lvs_ivf_range_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
+    }
+    return LVS_OK;
+}
+
 // ---- IVF-SQ8: the rows scored from 8-bit residual codes
 extern "C" int32_t lvs_ivf_sq8_encode(const void* xb, int32_t xb_pack, int64_t n, int32_t d, const int64_t* offsets,
                                       const uint32_t* rows, int32_t nlist, const float* centroids, const float* vmin,

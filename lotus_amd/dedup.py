@@ -39,6 +39,30 @@ def threshold_pairs(backend, packed, threshold: float, metric: int = _capi.METRI
     return q[order].astype(np.int64), j[order].astype(np.int64), s[order].astype(np.float32)
 
 
+def threshold_pairs_ivf(vs, threshold: float, ids=None, nprobe: int | None = None):
+    """``threshold_pairs`` through the lists of an IVF ``HipVS`` -> (i, j, score): positions into ``ids`` (row numbers without
+    ``ids``), ``i < j``, sorted by (i, j), each pair once.  Approximate, opt-in.  The rule: with the store's rows as the
+    queries (``HipVS.ivf_self_pairs``), a pair is returned iff its score exceeds the threshold (strict, fp32, exact scores)
+    AND list(j) is among the ``nprobe`` lists row i probes OR list(i) among those row j probes; ``nprobe = nlist`` is the
+    exact join.  Near-duplicates share a list or sit in neighbouring ones, so a few probes find almost all of them while
+    scoring about 2 nprobe / nlist of the pairs.
+
+    Both directions of a pair come back from the device; the record whose query was the smaller position is kept when it
+    exists (the scores of (i, j) and (j, i) may differ in the last bit on hi|lo rows: the hi.lo and lo.hi segments swap)."""
+    q, j, s = vs.ivf_self_pairs(threshold, ids=ids, nprobe=nprobe)
+    if ids is not None:  # row numbers -> positions in ids
+        sub = np.asarray(ids, dtype=np.int64).reshape(-1)
+        pos = np.empty(int(sub.max()) + 1 if sub.size else 0, np.int64)
+        pos[sub] = np.arange(sub.size)
+        q, j = pos[q], pos[j]
+    lo, hi = np.minimum(q, j), np.maximum(q, j)
+    order = np.lexsort((q != lo, hi, lo))  # per pair, the record asked from the smaller side first
+    lo, hi, s = lo[order], hi[order], s[order]
+    first = np.ones(len(lo), bool)
+    first[1:] = (lo[1:] != lo[:-1]) | (hi[1:] != hi[:-1])
+    return lo[first].astype(np.int64), hi[first].astype(np.int64), s[first].astype(np.float32)
+
+
 def component_labels(n: int, i: np.ndarray, j: np.ndarray) -> np.ndarray:
     """Connected-component label of every node = smallest node id in its component."""
     if len(i) == 0:

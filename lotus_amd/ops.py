@@ -176,20 +176,36 @@ def _joined_frame(df1, df2, qpos, left_ids, right_ids, scores, lsuffix, rsuffix,
     return pd.concat([left, middle, right], axis=1, copy=False)
 
 
-def sem_dedup(df: pd.DataFrame, col_name: str, threshold: float, rm=None, vs=None, shard: bool = False) -> pd.DataFrame:
+def sem_dedup(df: pd.DataFrame, col_name: str, threshold: float, rm=None, vs=None, shard: bool = False,
+              nprobe: int | None = None) -> pd.DataFrame:
     """``df.sem_dedup`` (``sem_dedup.py:32-91``) through the GPU threshold self-join: O(pairs) memory instead of
     O(N^2).  Survivor of each duplicate group = its first value in frame order.
 
     ``threshold`` is compared with the similarity score exactly as the reference does (``_scores > threshold``,
     ``sem_dedup.py:46``).  That only means something for a similarity metric: with an L2 vector store the reference's
     ``_scores`` are squared distances (larger = farther) and its dedup keeps the wrong side; here an L2 store is
-    refused instead of silently thresholding the negated distance."""
+    refused instead of silently thresholding the negated distance.
+
+    ``nprobe`` (None: the exact join above, unchanged): an int joins through the lists of an IVF store instead
+    (``dedup.threshold_pairs_ivf``) - approximate: a duplicate pair is found when one row's list is among the ``nprobe`` lists
+    the other probes; ``nprobe = nlist`` is the exact join.  It needs an ``"IVF..."`` ``HipVS``, the inner-product metric
+    and ``shard=False``; anything else is a ``ValueError`` - as is a frame whose index names a row twice, which the exact
+    join accepts: the lists are searched with a bitmap over the rows, and a bitmap holds a row once."""
     rm, vs = _settings(rm, vs)
     if getattr(vs, "metric", 0) != 0:
         raise ValueError("sem_dedup thresholds a similarity: configure the vector store with METRIC_INNER_PRODUCT")
+    if nprobe is not None:
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or int(nprobe) < 1:
+            raise ValueError(f"nprobe must be None or an int >= 1, got {nprobe!r}")
+        if shard or not hasattr(vs, "ivf_self_pairs"):  # a store without lists says so itself once its index is loaded
+            raise ValueError("sem_dedup(nprobe=...) joins through the lists of an IVF HipVS (factory_string='IVF<nlist>,...') "
+                             "with shard=False")
     col_index_dir = df.attrs["index_dirs"][col_name]
     if vs.index_dir != col_index_dir:
         vs.load_index(col_index_dir)
+    if nprobe is not None:
+        i, j, _ = _dedup.threshold_pairs_ivf(vs, threshold, ids=np.asarray(df.index), nprobe=int(nprobe))
+        return df[_dedup.keep_mask(df[col_name].tolist(), i, j)]
     packed = vs.packed_rows(df.index)
     i, j, _ = _dedup.threshold_pairs(vs.backend, packed, threshold, vs.metric, shard=shard)
     mask = _dedup.keep_mask(df[col_name].tolist(), i, j)

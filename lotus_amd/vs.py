@@ -911,6 +911,91 @@ class HipVS(VS):
         keys = be.search_keys(ent.ivf.centroids, queries, nprobe, self.metric, one_pass=False).cpu().numpy().view(np.uint64)
         return np.where(keys == 0, -1, 0xFFFFFFFF - (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int32)
 
+    def _range_args(self, ent: _Resident, ids, nprobe, what: str):
+        """What ``range_search`` and ``ivf_self_pairs`` check alike -> (``ids`` as a vector or None for every row, lists probed
+        per query or 0 without lists, whether the threshold scan takes the call).  Refused: a store whose rows or queries
+        are in fact split over several ranks (``shard="auto"`` on one GPU splits nothing), ``ids`` that name a row twice (a
+        bitmap holds a row once and a range result lists it once), an ``nprobe`` that is no int >= 1."""
+        lay = self._layout()
+        if lay[1] > 1 or lay[3] > 1:
+            raise ValueError(f"{what} needs an unsharded store: this one is split over {lay[1]} x {lay[3]} ranks")
+        sub = _ids_subset(ids, ent.n)
+        if sub is not None and np.unique(sub).size != sub.size:
+            raise ValueError("ids holds a row more than once: a threshold search returns a row once")
+        if ent.ivf is None:
+            return sub, 0, False
+        be = self.backend
+        nprobe = min(self._check_nprobe(self.nprobe if nprobe is None else nprobe), ent.ivf.nlist)
+        return sub, nprobe, (nprobe <= _capi.MAX_K and hasattr(be, "ivf_range_search")
+                             and be.ivf_range_fits(ent.d, ent.packed.mode))
+
+    @_serialised
+    def range_search(self, query_vectors, threshold: float, ids=None, nprobe: int | None = None, exact: bool = False):
+        """faiss's ``range_search``: every row past a threshold for every query -> ``(lims int64 [nq + 1], D float32, I
+        int64)``; query i's results are ``D[lims[i]:lims[i + 1]]`` / ``I[...]``, best first, ascending id among equal scores.
+        ``METRIC_INNER_PRODUCT``: the rows with product ``> threshold``; ``METRIC_L2``: the rows with squared distance
+        ``< threshold`` (faiss's radius), ``D`` the squared distances, ascending.  Both compares are strict, in fp32.
+
+        An IVF store of any mode answers through its lists (``HipBackend.ivf_range_search``, faiss's
+        ``IndexIVF::range_search``): the rows of each query's ``nprobe`` best lists (default: the store's) are scored EXACTLY
+        from the full-precision image - the codes of an SQ8 / PQ store are not used - so the result is the exact one
+        restricted to the probed lists, and ``nprobe = nlist`` is the exact result.  ``ids``: only those rows take part (a
+        bitmap over the rows in the list scan); duplicates are a ``ValueError``.  ``exact=True``, ``"Flat"`` stores, rows too
+        wide for the threshold scan (``HipBackend.ivf_range_fits``) and ``nprobe > 2048`` score every row, or every row of
+        ``ids``, through ``HipBackend.range_join``.  Single GPU: a store split over several ranks is refused."""
+        if not isinstance(exact, (bool, np.bool_)):
+            raise ValueError(f"exact must be a bool, got {exact!r}")
+        ent = self._current()
+        q = self._query_matrix(query_vectors, ent)
+        nq, be = int(q.shape[0]), self.backend
+        threshold = float(threshold)
+        if not np.isfinite(threshold):
+            raise ValueError(f"threshold must be finite, got {threshold!r}")
+        sub, nprobe, fits = self._range_args(ent, ids, nprobe, "range_search")
+        use_lists = fits and not exact
+        queries = be.pack(q, ent.packed.mode, normalize=self.normalize, exp=ent.packed.exp, check=True)
+        empty = (np.zeros(nq + 1, np.int64), np.zeros(0, np.float32), np.zeros(0, np.int64))
+        if nq == 0 or ent.n == 0 or (sub is not None and sub.size == 0):
+            return empty
+        # the kernels keep score > threshold with larger = better: a squared distance below the radius is -distance > -radius
+        better = threshold if self.metric == METRIC_INNER_PRODUCT else -threshold
+        if use_lists:
+            sel = be.row_bitmap(sub, ent.n)[0] if sub is not None else None
+            qi, j, s = be.ivf_range_search(ent.packed, ent.ivf, queries, better, self.metric, nprobe, sel=sel)
+            qi, j, s = _host(qi), _host(j), _host(s)
+        else:
+            corpus = ent.packed if sub is None else be.gather(ent.packed, be.to_device(sub))
+            qi, j, s = be.range_join(corpus, queries, better, self.metric)
+            qi, j, s = _host(qi), _host(j), _host(s)
+            j = j if sub is None else sub[j]
+        order = np.lexsort((j, -s.astype(np.float64), qi))
+        lims = np.zeros(nq + 1, np.int64)
+        np.cumsum(np.bincount(qi, minlength=nq), out=lims[1:])
+        s = s[order].astype(np.float32)
+        return lims, (s if self.metric == METRIC_INNER_PRODUCT else np.float32(0.0) - s), j[order].astype(np.int64)
+
+    @_serialised
+    def ivf_self_pairs(self, threshold: float, ids=None, nprobe: int | None = None):
+        """The store's own rows (all, or the rows ``ids``) as the queries of a threshold search through its lists -> host arrays
+        ``(q, j, score)`` of ROW numbers: every ordered pair with ``q != j``, both in ``ids``, ``list(j)`` among the ``nprobe``
+        lists row ``q`` probes, and score (the product, or minus the squared distance) ``> threshold``.  A pair usually comes
+        back from both sides; ``dedup.threshold_pairs_ivf`` makes one record of the two.  The whole image is the query
+        matrix as it stands (a view); a subset is gathered.  Needs an unsharded IVF store whose rows the threshold scan fits."""
+        ent = self._ivf_current()
+        be = self.backend
+        sub, nprobe, fits = self._range_args(ent, ids, nprobe, "the list self-join")
+        if not fits:
+            raise ValueError(f"the threshold scan does not take d={ent.d} with nprobe={nprobe}: join exactly (nprobe=None)")
+        if sub is None:
+            queries, rows, sel = be.slice_rows(ent.packed, 0, ent.n), np.arange(ent.n, dtype=np.int64), None
+        else:
+            queries, rows, sel = be.gather(ent.packed, be.to_device(sub)), sub, be.row_bitmap(sub, ent.n)[0]
+        if rows.size == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+        q_rows = be.to_device(rows.astype(np.uint32).view(np.int32))
+        q, j, s = be.ivf_range_search(ent.packed, ent.ivf, queries, float(threshold), self.metric, nprobe, q_rows=q_rows, sel=sel)
+        return rows[_host(q)], _host(j).astype(np.int64), _host(s).astype(np.float32)
+
     @_serialised
     def sq8_codes(self):
         """-> (vmin float32 [d], vdiff float32 [d], codes uint8 [n, d] in ROW order, residual norms float32 [n]) of an
