@@ -2108,7 +2108,7 @@ int64_t ivf_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d
     return L.total;
 }
 
-// the argument checks of the three searches, in the order they are reported.  A mode without rows of its own passes
+// the argument checks of the searches through the lists, in the order they are reported.  A mode without rows of its own passes
 // xb_pack = LVS_PACK_F16, a mode without a product quantizer M = ksub = 1: those checks then always hold
 int32_t ivf_check_search(int32_t metric, int64_t nb, int64_t nq, int32_t d, int32_t nlist, int32_t M, int32_t ksub,
                          int32_t nprobe, int32_t k, int32_t xb_pack, int32_t xq_pack, int32_t c_pack) {
@@ -2127,7 +2127,7 @@ int32_t ivf_check_search(int32_t metric, int64_t nb, int64_t nq, int32_t d, int3
     return LVS_OK;
 }
 
-// the arguments the three searches hand to the driver unchanged
+// the arguments the searches hand to the driver unchanged (the threshold search: k = 0, no out_keys)
 struct IvfSearch {
     int32_t nlist;
     const void* centroids;
@@ -2146,10 +2146,12 @@ struct IvfSearch {
     const uint32_t* sel_bits;  // the *_sel entry points' row selector for the mode's scan (NULL: every row)
 };
 
-// The host driver of the three searches: plan the scratch, then per chunk of queries the coarse step (the nprobe best
-// centroids of every query under the index's metric), the probe ids, the mode's scan and the merge of its parts.
+// The host driver of the four searches through the lists (top-k over the rows, the SQ8 codes and the PQ codes; the threshold
+// search): plan the scratch, then per chunk of queries the coarse step (the nprobe best centroids of every query under the
+// index's metric), the probe ids, the mode's scan and the merge of its parts.
 // scan(L, w, q0, cn, xq_c, qn_c, coarse, parts, nparts) launches the scan of queries [q0, q0 + cn) under its own
 // ScopedKernelTimer (q0 > 0: a continuation) and may lower nparts, the lists per query that it fills (nprobe on entry).
+// s.k = 0 (the threshold search): the scan appends to the caller's own buffers - no parts region and nothing to merge.
 // A row selector (s.sel_bits) concerns the scan alone: the coarse step, the pair grouping, the tiling and the merge see none.
 template <class Scan>
 int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, Scan scan) {
@@ -2181,6 +2183,7 @@ int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, S
         int32_t nparts = s.nprobe;
         int32_t rc = scan(L, w, q0, cn, xq_c, qn_c, coarse, parts, nparts);
         if (rc != LVS_OK) return rc;
+        if (s.k == 0) continue;
         rc = lvs_merge_keys((const uint64_t*)parts, nparts, cn, s.k, s.out_keys + q0 * s.k, s.stream);
         if (rc != LVS_OK) return rc;
     }
@@ -2189,13 +2192,47 @@ int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, S
 
 // Flat and SQ8: invert a chunk's (query, probe) pairs - pair numbers q * nprobe + p grouped by list (the bucket sort of
 // lvs_count_sort.hip) -, cut every list's pairs into work items of 32 (the SQ8 scan halves them) and zero the parts (a pair
-// whose probe named no list - never with nprobe <= nlist - keeps empty slots)
+// whose probe named no list - never with nprobe <= nlist - keeps empty slots; k = 0: there are none)
 int32_t ivf_group_pairs(const IvfLayout& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t nlist, int32_t k, u64* parts,
                         hipStream_t st, const uint32_t** pairs, const uint32_t** pair_offs) {
     const int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, 0, w + L.off_sort, L.sort_bytes, st, pairs, pair_offs);
     if (rc != LVS_OK) return rc;
     LVS_HIP_CHECK(lvs_ivf_tiles_launch(*pair_offs, nlist, (uint32_t*)(w + L.off_tiles), (uint32_t*)(w + L.off_items), st));
-    LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+    if (k > 0) LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+    return LVS_OK;
+}
+
+// the gathered-row scans' shared arguments (lvs_ivf_scan_kernel, lvs_ivf_range_kernel) that do not change from chunk to chunk
+void ivf_gather_args(LvsIvfGatherArgs& g, const Plan& p, int32_t xq_pack, const void* xb, const float* xb_norms_sq,
+                     const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits, int32_t nlist, int32_t nprobe,
+                     int32_t metric) {
+    g.xb = xb;
+    g.bn = xb_norms_sq;
+    g.rows = rows;
+    g.offsets = offsets;
+    g.sel = sel_bits;
+    g.ldb = p.ldb;
+    g.ldq = p.ldq;
+    g.nlist = nlist;
+    g.nprobe = nprobe;
+    g.metric = metric;
+    g.jper = p.dpad / 16;
+    g.nseg = p.nseg;
+    g.nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * g.jper;
+    for (int i = 0; i < 3; ++i) {
+        g.seg_c[i] = p.seg_c[i];
+        g.seg_b[i] = p.seg_q[i] == 0 ? 0 : g.jper;
+    }
+}
+// ... and those that do: the chunk's queries and its work items (ivf_group_pairs)
+int32_t ivf_gather_chunk(LvsIvfGatherArgs& g, const IvfLayout& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t k,
+                         u64* parts, hipStream_t st, const void* xq_c, const float* qn_c) {
+    const int32_t rc = ivf_group_pairs(L, w, coarse, npairs, g.nlist, k, parts, st, &g.pairs, &g.pair_offs);
+    if (rc != LVS_OK) return rc;
+    g.tile_offs = (const uint32_t*)(w + L.off_tiles);
+    g.item_list = (const uint32_t*)(w + L.off_items);
+    g.xq = xq_c;
+    g.qn = qn_c;
     return LVS_OK;
 }
 
@@ -2281,39 +2318,18 @@ extern "C" int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int6
     }
     LvsIvfArgs a;
     memset(&a, 0, sizeof(a));
-    a.xb = xb;
-    a.bn = xb_norms_sq;
-    a.rows = rows;
-    a.offsets = offsets;
-    a.nb = nb;
-    a.ldb = p.ldb;
-    a.ldq = p.ldq;
-    a.nlist = nlist;
-    a.nprobe = nprobe;
+    ivf_gather_args(a.g, p, xq_pack, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
     a.k = k;
-    a.metric = metric;
-    a.jper = p.dpad / 16;
-    a.nseg = p.nseg;
-    a.nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * a.jper;
     a.kcap = lvs_ivf_kcap(k);
-    for (int i = 0; i < 3; ++i) {
-        a.seg_c[i] = p.seg_c[i];
-        a.seg_b[i] = p.seg_q[i] == 0 ? 0 : a.jper;
-    }
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
     return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
                                              const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
-        const int32_t rc = ivf_group_pairs(L, w, coarse, cn * nprobe, nlist, k, parts, st, &a.pairs, &a.pair_offs);
+        const int32_t rc = ivf_gather_chunk(a.g, L, w, coarse, cn * nprobe, k, parts, st, xq_c, qn_c);
         if (rc != LVS_OK) return rc;
-        a.tile_offs = (const uint32_t*)(w + L.off_tiles);
-        a.item_list = (const uint32_t*)(w + L.off_items);
         a.out = parts;
-        a.xq = xq_c;
-        a.qn = qn_c;
         a.nq = (int)cn;
-        a.sel = s.sel_bits;
         ScopedKernelTimer timer(st, LVS_KERNEL_IVF, q0 > 0);
         LVS_HIP_CHECK(lvs_ivf_scan_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
         return LVS_OK;
@@ -2339,23 +2355,18 @@ bool ivf_range_fits(int32_t d, int32_t xq_pack) {
     const int jper = (int)(lvs_round_up(d, LVS_BK) / 16);
     return lvs_ivf_range_lds_bytes((xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper) <= 160 * 1024;
 }
-// the scratch of a chunk is the tiled searches' without parts (k = 0): no lists come back, the pairs go to the caller's buffers
-bool ivf_range_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t c_pack, int32_t xq_pack, IvfLayout& L) {
-    return ivf_plan(nq, nlist, nprobe, d, 0, c_pack, xq_pack, 0, true, L);
-}
 }  // namespace
 
 extern "C" int64_t lvs_ivf_range_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t pack) {
     if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0) return LVS_EINVAL;
     if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
     if (!ivf_range_fits(d, pack)) return LVS_EUNSUPPORTED;  // the caller joins such shapes exactly
-    IvfLayout L;
-    if (!ivf_range_plan(nq, nlist, nprobe, d, pack, pack, L)) return LVS_EINVAL;
+    IvfLayout L;  // the tiled searches' scratch without parts (k = 0): the pairs go to the caller's buffers
+    if (!ivf_plan(nq, nlist, nprobe, d, 0, pack, pack, 0, true, L)) return LVS_EINVAL;
     return L.total;
 }
 
-// The driver is ivf_search_chunks's sibling: the same plan, coarse step, pair grouping and tiling per chunk of queries; where
-// the searches scan into parts and merge them, every chunk's launch appends to the call's one pair list.
+// Where the top-k searches scan into parts that the driver merges, every chunk's launch appends to the call's one pair list.
 extern "C" int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
                                         const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits, int32_t nlist,
                                         const void* centroids, int32_t c_pack, const float* c_norms_sq, const void* xq,
@@ -2376,67 +2387,29 @@ extern "C" int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t
         lvs_set_error("d=%d does not fit the threshold scan's LDS (see lvs_ivf_range_workspace_bytes)", d);
         return LVS_EUNSUPPORTED;
     }
-    IvfLayout L;
-    LVS_REQUIRE(ivf_range_plan(nq, nlist, nprobe, d, c_pack, xq_pack, L), "shape beyond the IVF search");
-    if (workspace_bytes < L.total) {
-        lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
-        return LVS_ENOMEM;
-    }
     LvsIvfRangeArgs a;
     memset(&a, 0, sizeof(a));
-    a.xb = xb;
-    a.bn = xb_norms_sq;
-    a.rows = rows;
-    a.offsets = offsets;
-    a.sel = sel_bits;
+    ivf_gather_args(a.g, p, xq_pack, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
     a.out_q = (long long*)out_q;
     a.out_j = (long long*)out_j;
     a.out_s = out_s;
     a.out_count = (unsigned long long*)out_count;
     a.capacity = capacity;
-    a.ldb = p.ldb;
-    a.ldq = p.ldq;
-    a.nlist = nlist;
-    a.nprobe = nprobe;
-    a.metric = metric;
-    a.jper = p.dpad / 16;
-    a.nseg = p.nseg;
-    a.nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * a.jper;
-    for (int i = 0; i < 3; ++i) {
-        a.seg_c[i] = p.seg_c[i];
-        a.seg_b[i] = p.seg_q[i] == 0 ? 0 : a.jper;
-    }
     a.threshold = threshold * ldexpf(1.0f, score_exp);  // the device scores are 2^score_exp x the caller's (exact)
     a.out_scale = ldexpf(1.0f, -score_exp);
-    LVS_DEVICE_GUARD(stream);
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
-    const size_t qrow_bytes = (size_t)p.ldq * 2;
-    for (int64_t q0 = 0; q0 < nq; q0 += L.chunk) {
-        const int64_t cn = nq - q0 < L.chunk ? nq - q0 : L.chunk;
-        const void* xq_c = (const char*)xq + (size_t)q0 * qrow_bytes;
-        const float* qn_c = xq_norms_sq ? xq_norms_sq + q0 : nullptr;
-        {
-            TimingPause pause;
-            const int32_t rc = lvs_flat_search_keys(centroids, c_pack, nlist, xq_c, xq_pack, cn, d, metric, nprobe, c_norms_sq, qn_c,
-                                                    0, nullptr, coarse, w, L.flat_bytes, stream);
-            if (rc != LVS_OK) return rc;
-        }
-        const int32_t rc = lvs_bucket_positions(coarse, nullptr, cn * nprobe, nlist, 0, w + L.off_sort, L.sort_bytes, st, &a.pairs,
-                                                &a.pair_offs);
+    const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
+                         metric, nprobe, 0, nullptr, nullptr, workspace, workspace_bytes, stream, sel_bits};
+    return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
+                                             const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
+        hipStream_t st = (hipStream_t)stream;
+        const int32_t rc = ivf_gather_chunk(a.g, L, w, coarse, cn * nprobe, 0, parts, st, xq_c, qn_c);
         if (rc != LVS_OK) return rc;
-        LVS_HIP_CHECK(lvs_ivf_tiles_launch(a.pair_offs, nlist, (uint32_t*)(w + L.off_tiles), (uint32_t*)(w + L.off_items), st));
-        a.tile_offs = (const uint32_t*)(w + L.off_tiles);
-        a.item_list = (const uint32_t*)(w + L.off_items);
-        a.xq = xq_c;
-        a.qn = qn_c;
         a.q_rows = q_rows ? q_rows + q0 : nullptr;
         a.q_base = q0;
         ScopedKernelTimer timer(st, LVS_KERNEL_IVF_RANGE, q0 > 0);
         LVS_HIP_CHECK(lvs_ivf_range_launch(a, lvs_ivf_max_items(cn * nprobe, nlist), st));
-    }
-    return LVS_OK;
+        return LVS_OK;
+    });
 }
 
 // ---- IVF-SQ8: the rows scored from 8-bit residual codes

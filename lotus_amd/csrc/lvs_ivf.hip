@@ -2,16 +2,8 @@
 //
 // An IVF search probes nprobe of nlist inverted lists per query.  The (query, probe rank) pairs are grouped by list
 // (the bucket sort of lvs_count_sort.hip), and one work item is one list together with a tile of up to 32 of the pairs that
-// probe it:
-//   * the tile's queries live in LDS as ready-made MFMA B fragments, laid out as in lvs_stream_kernel
-//     ([nbfrag][64 lanes][16 B], lane-linear -> conflict-free ds_read_b128);
-//   * the list's rows are GATHERED by number from the flat packed image: lane (r, h) of a wave reads 16 B of row
-//     rows[offsets[l] + 32 b + r] per fragment - lvs_stream_kernel's lane-to-row load with an indexed row base instead of a
-//     linear one.  A gathered row is 1-3 KB read in 128-B lines, which HBM serves at the rate of a sweep, so the corpus is
-//     never copied into list order;
-//   * each wave takes every fourth 32-row block of the list: v_mfma_f32_32x32x16_f16 on 32 rows x 32 queries per K step,
-//     hi|lo operands as the K segments hi.hi + hi.lo + lo.hi (fp32-accurate, like the flat path); the fragments of the next
-//     K step are loaded while the current ones are multiplied;
+// probe it.  The work item, the tile's queries in LDS, the gathered rows and the MFMA loop that scores a 32-row block against
+// the tile are lvs_ivf_gather.h's.  This kernel's own part is what happens to a score:
 //   * hits go through the wave-cooperative sorted insertion (lvs_list_insert, lvs_common.h) into per-query lists in LDS (one
 //     lock per query: the four waves share the tile).  Keys carry the GLOBAL row number, so ties between rows of different
 //     lists keep the oracle's total order when the per-probe lists are merged (lvs_merge_keys);
@@ -21,14 +13,11 @@
 // 8 TB/s = 1.5 us, in practice bounded by the latency of a few dozen workgroups; 10 000 queries are 120 GFLOP (48 us at
 // 2.5 PFLOP/s), but every work item reads its whole list and a list serves ~3 tiles, so ~4.6 GB of row reads make this
 // tiling bandwidth-bound at ~0.58 ms.  The LDS image bounds d: lvs_ivf_search_workspace_bytes.
-#include "lvs_common.h"
-#include "lvs_tile.h"
+#include "lvs_ivf_gather.h"
 
 namespace {
 
-// SEL: only the rows whose bit is set in a.sel (bit r & 31 of word r >> 5 for row r of the flat image) take part.  A wave
-// looks its 32 rows' bits up right after their numbers and skips the block before any row data when none is selected; the
-// 32-bit ballot of (inside the list and selected), indexed by the block row, masks the epilogue in place of the `< len` test.
+// SEL: only the rows whose bit is set in a.g.sel (bit r & 31 of word r >> 5 for row r of the flat image) take part.
 template <int U, bool SEL>
 __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const LvsIvfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -37,108 +26,51 @@ __global__ __launch_bounds__(LVS_IVF_WAVES * 64) void lvs_ivf_scan_kernel(const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int KCAP = a.kcap;
     half8* bfrag = (half8*)smem;                                            // [nbfrag][64]
-    u64* lists = (u64*)(smem + (size_t)a.nbfrag * 1024);                    // [TQ][KCAP]
+    u64* lists = (u64*)(smem + (size_t)a.g.nbfrag * 1024);                  // [TQ][KCAP]
     uint32_t* locks = (uint32_t*)((char*)lists + (size_t)TQ * KCAP * 8);    // [TQ]
     int* slot_q = (int*)(locks + TQ);                                       // [TQ] query of every pair slot
     int* slot_p = slot_q + TQ;                                              // [TQ] its probe rank
 
-    // ---- work item -> (list, tile of pairs)
-    const uint32_t wi = blockIdx.x;
-    if (wi >= a.tile_offs[a.nlist]) return;  // the grid is an upper bound of the work items
-    const int l = (int)a.item_list[wi];
-    const uint32_t p0 = a.pair_offs[l] + (wi - a.tile_offs[l]) * TQ;
-    const uint32_t pend = a.pair_offs[l + 1];
-    const int npair = (int)(pend - p0 < (uint32_t)TQ ? pend - p0 : (uint32_t)TQ);  // >= 1
-    lvs_ivf_tile_begin<TQ, LVS_IVF_WAVES * 64>(a.pairs, p0, npair, a.nprobe, tid, lists, KCAP, locks, slot_q, slot_p);
-    // ---- queries -> LDS as B fragments: fragment f, lane v = pair slot (v & 31), halfs (v >> 5) * 8 .. + 8
-    const _Float16* xq = (const _Float16*)a.xq;
-    for (int idx = tid; idx < a.nbfrag * 64; idx += LVS_IVF_WAVES * 64) {
-        const int v = idx & 63, f = idx >> 6;
-        const int part = f / a.jper, jj = f - part * a.jper;  // part 0: columns [0, dpad), part 1: [dpad, 2 dpad)
-        const long long q = slot_q[v & 31];
-        bfrag[idx] = *(const half8*)(xq + q * a.ldq + part * a.jper * 16 + jj * 16 + (v >> 5) * 8);
-    }
-    __syncthreads();
+    const LvsIvfItem it = lvs_ivf_work_item(a.g, blockIdx.x);
+    if (!it.ok) return;
+    const int npair = it.npair;
+    lvs_ivf_tile_begin<TQ, LVS_IVF_WAVES * 64>(a.g.pairs, it.p0, npair, a.g.nprobe, tid, lists, KCAP, locks, slot_q, slot_p);
+    lvs_ivf_stage_queries(a.g, slot_q, bfrag, tid);
 
     const int qs = lane & 31;  // this lane's pair slot (lanes l and l + 32 share it)
     const bool qvalid = qs < npair;
-    const float qnv = a.metric == LVS_METRIC_L2 ? a.qn[slot_q[qs]] : 0.f;
+    const float qnv = a.g.metric == LVS_METRIC_L2 ? a.g.qn[slot_q[qs]] : 0.f;
     float tauf = -INFINITY;
     const int k = a.k;
 
-    const _Float16* xb = (const _Float16*)a.xb;
-    const long long r0 = a.offsets[l];
-    const int len = (int)(a.offsets[l + 1] - r0);
-    const int nblk = (len + 31) / 32;
-    const int jper = a.jper, nj = a.nseg * jper;
-    const int segc0 = a.seg_c[0], segc1 = a.seg_c[1], segc2 = a.seg_c[2];
-    const int segb0 = a.seg_b[0], segb1 = a.seg_b[1], segb2 = a.seg_b[2];
-
-    for (int blk = wave; blk < nblk; blk += LVS_IVF_WAVES) {
-        // the row this lane loads: row (lane & 31) of the block; past the list's end the last row is repeated (masked below)
-        int rr = blk * 32 + (lane & 31);
-        if (rr > len - 1) rr = len - 1;
-        const uint32_t rid = a.rows[r0 + rr];
-        uint32_t selm = 0;  // SEL: bit j = block row j is inside the list and selected (lanes j and j + 32 hold the same row)
-        if constexpr (SEL) {
-            const bool on = blk * 32 + (lane & 31) < len && ((a.sel[rid >> 5] >> (rid & 31)) & 1u);
-            selm = (uint32_t)__ballot(on);
-            if (selm == 0) continue;  // wave-uniform; the block loop has no workgroup barrier
-        }
-        const float bnv = a.metric == LVS_METRIC_L2 ? a.bn[rid] : 0.f;
-        const _Float16* ap = xb + (long long)rid * a.ldb + (lane >> 5) * 8;
-        // fragments f = seg * jper + jj; U divides jper, so a batch of U never crosses a K segment.  The batch after the
-        // current one is in flight while the current one is multiplied.
-        half8 cur[U], nxt[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = *(const half8*)(ap + segc0 + u * 16);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        for (int f0 = 0; f0 < nj; f0 += U) {
-            const int seg = f0 / jper, jj = f0 - seg * jper;
-            if (f0 + U < nj) {
-                const int nseg_ = (f0 + U) / jper, njj = f0 + U - nseg_ * jper;
-                const int coff = nseg_ == 0 ? segc0 : (nseg_ == 1 ? segc1 : segc2);
-                const _Float16* sp = ap + coff + njj * 16;
-#pragma unroll
-                for (int u = 0; u < U; ++u) nxt[u] = *(const half8*)(sp + u * 16);
-            }
-            const int boff = seg == 0 ? segb0 : (seg == 1 ? segb1 : segb2);
-            const half8* bp = bfrag + (long long)(boff + jj) * 64 + lane;
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur[u], bp[u * 64], acc, 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-        }
-        // ---- block epilogue: lane holds pair slot qs, block rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    const LvsIvfList L = lvs_ivf_list(a.g, it.list);
+    for (int blk = wave; blk < L.nblk; blk += LVS_IVF_WAVES) {
+        const LvsIvfRows b = lvs_ivf_block_rows<SEL>(a.g, L, blk, lane);
+        if (SEL && b.mask == 0) continue;  // wave-uniform; the block loop has no workgroup barrier
+        const uint32_t rid = b.rid;
+        const f32x16 acc = lvs_ivf_block_scores<U, true>(a.g, L, bfrag, rid, qnv, lane);
+        // ---- block epilogue: lane holds pair slot qs, block rows lvs_ivf_acc_row(r) + 4 (lane >> 5)
+        const uint32_t selw = b.mask >> (4 * (lane >> 5));  // bit j = this lane's block row 4 (lane >> 5) + j takes part
         const int brow0 = blk * 32 + 4 * (lane >> 5);
-        const uint32_t selw = selm >> (4 * (lane >> 5));  // SEL: bit j = this lane's block row 4 (lane >> 5) + j takes part
-        if (a.metric == LVS_METRIC_L2) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float bv = __shfl(bnv, (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), 64);
-                acc[r] = -fmaxf((qnv + bv) - 2.0f * acc[r], 0.f);
-            }
-        }
+        // does the row of acc[r] take part?  Without a selector `< len` says the same as the mask's bit, and the 768-wide
+        // scan is 0.5-1.5 % faster with the compare (profiles/ivf_gather_refactor_ab.json)
+        auto on = [&](int r) -> bool {
+            if constexpr (SEL) return (selw >> lvs_ivf_acc_row(r)) & 1u;
+            else return brow0 + lvs_ivf_acc_row(r) < L.len;
+        };
         {
             const uint32_t lo = (uint32_t)(lists[qs * KCAP + k - 1] >> 32);
             tauf = fmaxf(tauf, lvs_tau(lo));
         }
         float best = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (SEL) best = (selw >> ((r & 3) + 8 * (r >> 2))) & 1u ? fmaxf(best, acc[r]) : best;
-            else best = brow0 + (r & 3) + 8 * (r >> 2) < len ? fmaxf(best, acc[r]) : best;
-        }
+        for (int r = 0; r < 16; ++r) best = on(r) ? fmaxf(best, acc[r]) : best;
         const bool th = qvalid && best >= tauf;
         if (!__any(th)) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const uint32_t id = (uint32_t)__shfl((int)rid, (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), 64);
-            bool pending;
-            if constexpr (SEL) pending = th && ((selw >> ((r & 3) + 8 * (r >> 2))) & 1u) && acc[r] >= tauf;
-            else pending = th && brow0 + (r & 3) + 8 * (r >> 2) < len && acc[r] >= tauf;
+            const uint32_t id = (uint32_t)__shfl((int)rid, lvs_ivf_acc_row(r) + 4 * (lane >> 5), 64);
+            const bool pending = th && on(r) && acc[r] >= tauf;
             const u64 key = pending ? lvs_pack_key(acc[r], id) : 0ull;
             lvs_list_insert(__ballot(pending), key, qs, lists, KCAP, locks, k, lane, tauf);
         }
@@ -204,7 +136,7 @@ __global__ __launch_bounds__(256) void lvs_ivf_offsets_kernel(const uint32_t* __
 template <int U, bool SEL>
 hipError_t ivf_scan_launch_u(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream) {
     return lvs_launch_lds<lvs_ivf_scan_kernel<U, SEL>>(dim3((unsigned)max_items), dim3(LVS_IVF_WAVES * 64),
-                                                       lvs_ivf_lds_bytes(a.nbfrag, a.kcap), stream, a);
+                                                       lvs_ivf_lds_bytes(a.g.nbfrag, a.kcap), stream, a);
 }
 
 }  // namespace
@@ -223,10 +155,10 @@ hipError_t lvs_ivf_tiles_launch(const uint32_t* pair_offs, int nlist, uint32_t* 
 
 // jper = dpad / 16 is a multiple of 4 (dpad is a multiple of 64): batches of 8 fragments where they divide it, else 4
 hipError_t lvs_ivf_scan_launch(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream) {
-    if (a.jper % 4 != 0 || a.k < 1 || a.k > a.kcap || a.kcap > 64 || a.nseg < 1 || a.nseg > 3) return hipErrorInvalidValue;
+    if (a.g.jper % 4 != 0 || a.k < 1 || a.k > a.kcap || a.kcap > 64 || a.g.nseg < 1 || a.g.nseg > 3) return hipErrorInvalidValue;
     if (max_items <= 0) return hipSuccess;
-    if (a.sel) return a.jper % 8 == 0 ? ivf_scan_launch_u<8, true>(a, max_items, stream) : ivf_scan_launch_u<4, true>(a, max_items, stream);
-    if (a.jper % 8 == 0) return ivf_scan_launch_u<8, false>(a, max_items, stream);
+    if (a.g.sel) return a.g.jper % 8 == 0 ? ivf_scan_launch_u<8, true>(a, max_items, stream) : ivf_scan_launch_u<4, true>(a, max_items, stream);
+    if (a.g.jper % 8 == 0) return ivf_scan_launch_u<8, false>(a, max_items, stream);
     return ivf_scan_launch_u<4, false>(a, max_items, stream);
 }
 

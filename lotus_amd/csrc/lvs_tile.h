@@ -292,7 +292,8 @@ hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // 
 // (query, probe rank) pairs that probe it; the list's rows are gathered by number from the flat image. ----
 #define LVS_IVF_TILEQ 32     // pairs per work item (MFMA N)
 #define LVS_IVF_WAVES 4
-struct LvsIvfArgs {
+// what every scan over gathered rows reads (lvs_ivf_gather.h): the image, the lists, a chunk's queries and its work items
+struct LvsIvfGatherArgs {
     const void* xb;              // the flat packed image [nb][ldb]
     const float* bn;             // [nb] |row|^2 (L2 only)
     const uint32_t* rows;        // [n] row numbers, list after list
@@ -303,12 +304,16 @@ struct LvsIvfArgs {
     const uint32_t* pair_offs;   // [nlist + 1] first pair of every list
     const uint32_t* tile_offs;   // [nlist + 1] first work item of every list (lvs_ivf_tiles_launch)
     const uint32_t* item_list;   // [work items] list of every work item
-    u64* out;                    // [nprobe][nq][k]
-    long long nb, ldb, ldq;
-    int nq, nlist, nprobe, k, metric;
-    int jper, nseg, nbfrag, kcap;
-    int seg_c[3], seg_b[3];
     const uint32_t* sel;         // [ceil(nb / 32)] row selector, bit r & 31 of word r >> 5 = row r takes part; NULL: every row
+    long long ldb, ldq;
+    int nlist, nprobe, metric;
+    int jper, nseg, nbfrag;
+    int seg_c[3], seg_b[3];
+};
+struct LvsIvfArgs {
+    LvsIvfGatherArgs g;
+    u64* out;                    // [nprobe][nq][k]
+    int nq, k, kcap;
 };
 size_t lvs_ivf_lds_bytes(int nbfrag, int kcap);
 int lvs_ivf_kcap(int k);
@@ -320,30 +325,16 @@ hipError_t lvs_ivf_scan_launch(const LvsIvfArgs& a, int64_t max_items, hipStream
 hipError_t lvs_ivf_probe_ids_launch(const u64* keys, int64_t n, int32_t* out, hipStream_t stream);
 hipError_t lvs_ivf_offsets_launch(const uint32_t* offs, int nlist, int64_t* out, hipStream_t stream);
 
-// ---- lvs_ivf_range.hip: the threshold search over the lists (lvs_ivf_range_search).  The work items are lvs_ivf_scan_kernel's;
+// ---- lvs_ivf_range.hip: the threshold search over the lists (lvs_ivf_range_search).  The same work items and block scores;
 // every (query, row) of a probed list with score > threshold goes to one pair list behind one counter. ----
 struct LvsIvfRangeArgs {
-    const void* xb;              // the flat packed image [nb][ldb]
-    const float* bn;             // [nb] |row|^2 (L2 only)
-    const uint32_t* rows;        // [n] row numbers, list after list
-    const int64_t* offsets;      // [nlist + 1]
-    const void* xq;              // queries of this chunk [nq][ldq]
-    const float* qn;             // [nq] |q|^2 (L2 only)
+    LvsIvfGatherArgs g;
     const uint32_t* q_rows;      // nullable [nq]: the row each query of this chunk IS - that row is never paired with it
-    const uint32_t* pairs;       // [nq * nprobe] pair numbers q * nprobe + p, bucketed by list
-    const uint32_t* pair_offs;   // [nlist + 1] first pair of every list
-    const uint32_t* tile_offs;   // [nlist + 1] first work item of every list (lvs_ivf_tiles_launch)
-    const uint32_t* item_list;   // [work items] list of every work item
-    const uint32_t* sel;         // [ceil(nb / 32)] row selector as in LvsIvfArgs; NULL: every row
     long long* out_q;            // [capacity] query number in the CALL (q_base + the chunk's)
     long long* out_j;            // [capacity] row number
     float* out_s;                // [capacity] score * out_scale
     unsigned long long* out_count;  // hits of the whole call, counted past the capacity too
     long long capacity, q_base;
-    long long ldb, ldq;
-    int nlist, nprobe, metric;
-    int jper, nseg, nbfrag;
-    int seg_c[3], seg_b[3];
     float threshold, out_scale;  // a hit: score > threshold in the kernel's (scaled) fp32 domain
 };
 size_t lvs_ivf_range_lds_bytes(int nbfrag);

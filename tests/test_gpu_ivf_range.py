@@ -40,14 +40,18 @@ def _setup(be, nb, d, nq, mode, metric, nlist, seed):
     return xb_s, xq_s, packed, lists, be.pack(xq, mode), off, rows
 
 
-def _accept(xb_s, xq_s, metric, thr, off, rows, probe, q, j, s, mask=None, queries=None):
-    """``queries``: check these queries only (the reference of a long call is taken on a sample)."""
+def _accept(xb_s, xq_s, metric, thr, off, rows, probe, q, j, s, mask=None, queries=None, own=None):
+    """``queries``: check these queries only (the reference of a long call is taken on a sample).  ``own``: the row every
+    query is (``q_rows``) - the reference is taken without those pairs."""
     q, j, s = _np(q), _np(j), _np(s)
     if queries is not None:
         keep = np.isin(q, queries)
         q, j, s = np.searchsorted(queries, q[keep]), j[keep], s[keep]
         xq_s, probe = xq_s[queries], probe[queries]
+        own = None if own is None else own[queries]
     want, near = ivf_range_reference(xb_s, xq_s, thr, metric, off, rows, probe, sel=mask)
+    if own is not None:
+        want, near = want[want[:, 1] != own[want[:, 0]]], near[near[:, 1] != own[near[:, 0]]]
     print(f"want {len(want)} near {len(near)} got {len(q)}")
     assert len(want) >= 1000 and len(near) <= 0.01 * len(want), (len(want), len(near))
     got = np.stack([q, j], axis=1)
@@ -120,6 +124,28 @@ def test_beyond_one_in_call_chunk(hip_backend):
     rng = np.random.default_rng(4)
     sample = np.unique(np.concatenate([[0, 16383, 16384, 16385, 32767, 32768, 32769, nq - 1], rng.choice(nq, 200, replace=False)]))
     _accept(xb_s, xq_s, IP, 0.30, off, rows, _probe(be, packed, lists, qp, IP, 4), q, j, s, queries=sample)
+
+
+# 4b. own rows across an in-call chunk boundary: test 4's index searched with its 20 000 rows as the queries (two in-call
+# chunks), q_rows = their numbers - the second chunk's launch reads q_rows from its own first query on
+def test_own_rows_across_an_in_call_chunk_boundary(hip_backend):
+    import torch
+
+    be = hip_backend
+    nq = 20000
+    xb_s, _, packed, lists, _, off, rows = _setup(be, nq, 64, 1, F16, IP, 64, seed=11)
+    qp = be.pack(xb_s.astype(np.float16), F16)
+    rng = np.random.default_rng(4)
+    sample = np.unique(np.concatenate([[0, 16383, 16384, 16385, nq - 1], rng.choice(nq, 200, replace=False)]))
+    probe = _probe(be, packed, lists, qp, IP, 4)
+    q_rows = torch.arange(nq, dtype=torch.int32, device=be.device)
+    q, j, s = _search(be, packed, lists, qp, IP, 0.30, 4, q_rows=q_rows)
+    got = _accept(xb_s, xb_s, IP, 0.30, off, rows, probe, q, j, s, queries=sample, own=np.arange(nq))
+    assert np.all(_np(q) != _np(j)) and np.all(sample[got[:, 0]] != got[:, 1])
+    # teeth: without q_rows every sampled query comes back paired with itself (its own list is among its probes, score 1)
+    q, j, s = _search(be, packed, lists, qp, IP, 0.30, 4)
+    q, j = _np(q), _np(j)
+    assert np.array_equal(np.sort(q[(q == j) & np.isin(q, sample)]), sample)
 
 
 # 5. + 6. share one index
