@@ -1161,15 +1161,25 @@ hipError_t launch_merge(bool wide, const u64* parts, int nparts, int64_t nq, int
 }
 
 // Chunked calls of lvs_rq_kernel / lvs_rj_kernel: a chunk is 4 096 queries (16 groups x 16 corpus ranges) or 8 192 x 2^i
-// (32 / 64 / 128 / 256 groups x 8 / 4 / 2 / 1 ranges: a multiple of 32 groups - lvs_rq_item), the largest such size up to
-// `want`; what is left at the end goes out in launches of 8 192, 4 096 and one of <= 4 096 queries (rq_chunk_len).
+// (32 / 64 / 128 / 256 groups x 8 / 4 / 2 / 1 ranges: a multiple of 32 groups - lvs_rq_item).  rq_chunk_size: the largest such
+// size up to `want`, the call's maximum.  A call is cut greedily (rq_chunk_len): every chunk is the largest of 65 536, 32 768,
+// 16 384, 8 192 that is <= the queries left and <= the maximum, then one of 4 096 while more than 4 096 are left, then the rest -
+// 100 000 = 65 536 + 32 768 + 1 696, 50 000 = 32 768 + 16 384 + 848.  (Before this rule whatever was left below the maximum went out
+// in 8 192s - the slowest of these geometries: 100 000 at a maximum of 65 536 ran 65 536 + 4 x 8 192 + 1 696, which is what the
+// "65 536" lines of profiles/r10j_join_variants.log and r12d_knobs.log measured.)
 int64_t rq_chunk_size(int64_t want) {
     int64_t c = LVS_RQ_MAXQ;
     while (2 * c <= want && 2 * c <= LVS_RQ_CHUNK_MAX) c *= 2;
     return c;
 }
-int64_t rq_chunk_len(int64_t left, int64_t chunk) {
-    return left >= chunk ? chunk : (left >= 8192 ? 8192 : (left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left));
+int64_t rq_chunk_len(int64_t left, int64_t chunk_max) {
+    for (int64_t c = chunk_max; c >= 8192; c /= 2)
+        if (left >= c) return c;
+    return left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left;
+}
+// the threshold join's cut (lvs_range_join), unchanged: chunks of LVS_RANGE_CHUNK rows, what is left in 8 192s, 4 096, the rest
+int64_t range_chunk_len(int64_t left) {
+    return left >= LVS_RANGE_CHUNK ? LVS_RANGE_CHUNK : (left >= 8192 ? 8192 : (left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left));
 }
 
 // What a flat search does beyond its operands (the lvs_flat_search_keys variants)
@@ -1278,7 +1288,9 @@ int32_t search_two_phase(const SearchCall& sc, const uint32_t** pred) {
 }
 
 // ---- lvs_rq_kernel / lvs_rj_kernel, one launch per chunk of queries (rq_chunk_size): a query belongs to one chunk, so every
-// chunk is a complete search of its own (own seeds, own lists, own merge) ----
+// chunk is a complete search of its own (own seeds, own lists, own merge - or, with one list per query, no merge: a launch of
+// lvs_rj_kernel with ONE corpus range and no nb % 32 tail rows writes [1][cn][k] = the chunk's [cn][k] of out_keys itself; a
+// one-part merge_keys_kernel is a plain copy of a sorted, zero-padded list) ----
 int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
     const Plan& p = sc.p;
     const int64_t nq = sc.nq, nb = sc.nb;
@@ -1342,6 +1354,12 @@ int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
         // (r6) one wave per SIMD, 64 queries per wave (lvs_rj.hip) for the launches it takes: whole 32-row blocks there, the
         // corpus' last nb % 32 rows through lvs_rq_kernel as one more list per query
         if (lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_rj_fits(cn, nb, p.dpad, k, sc.row_ids != nullptr)) {
+            if (nb % 32 == 0 && lvs_rj_parts(cn, nb) == 1 && lvs_tune("LVS_RJ_SOLO", LVS_RJ_SOLO_DEFAULT) != 0) {
+                ra.out = sc.out_keys + c0 * k;
+                ScopedKernelTimer timer(st, LVS_KERNEL_RJ, c0 > 0);
+                LVS_HIP_CHECK(lvs_rj_launch(ra, p.dpad, st));
+                continue;
+            }
             {
                 ScopedKernelTimer timer(st, LVS_KERNEL_RJ, c0 > 0);
                 LVS_HIP_CHECK(lvs_rj_launch(ra, p.dpad, st));
@@ -1948,8 +1966,8 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
         return LVS_OK;
     };
     // (r6) fp16 rows, inner product, one rank's tiles: the register-resident-queries kernel in RANGE mode (lvs_rj.hip) - chunks of
-    // <= 32 768 queries, each against the rows that can still pair with it (a self-join skips the rows below the chunk's first
-    // query: j > i), whole 32-row blocks; the corpus' last nb % 32 rows and chunks left with a short corpus go through the list
+    // <= 32 768 queries (LVS_RANGE_CHUNK, its own constant), each against the rows that can still pair with it (a self-join skips
+    // the rows below the chunk's first query: j > i), whole 32-row blocks; the corpus' last nb % 32 rows and chunks left with a short corpus go through the list
     // kernel.  Same pairs (keys are scores of the same MFMA sequence), one shared counter.
     const bool rj_range = lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_tune("LVS_RJ_RANGE", 1) != 0 && xb_pack == LVS_PACK_F16 &&
                           xq_pack == LVS_PACK_F16 && metric == LVS_METRIC_IP && qt_stride == 1 && nq >= 2048 &&
@@ -1957,7 +1975,7 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
     if (!rj_range) return tile_launch(0, nq, 0, nb, qt_stride, qt_phase, false);
     bool first = true;
     for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
-        cn = rq_chunk_len(nq - c0, LVS_RQ_CHUNK_DEFAULT);
+        cn = range_chunk_len(nq - c0);
         // rows that can pair with this chunk's queries: all of them, or (self-join) those above the chunk's first query row
         int64_t r0 = 0;
         if (q_row0 >= 0) {

@@ -146,9 +146,14 @@ struct RjGeom {
 // NJ = K / 16; KCAP = list slots per query (k <= KCAP); L2: squared-L2 scores (the rows' |y|^2 ride in with the block)
 // RANGE: the threshold join of sem_dedup (lvs_range_join) on the same frame - no lists, no thresholds to exchange: a score above
 // the (one, constant) threshold goes straight to the global pair list
-template <int NJ, int KCAP, bool L2, int DBG = 0, bool RANGE = false>
+// SOLO: a top-k launch with ONE corpus range (a.nparts == 1: every workgroup owns its 256 queries over the whole shard, nobody else
+// holds a list for them) - nothing to take in and nobody to publish to: no threshold side words (squared L2 keeps the rows'
+// |y|^2), no side-word read or widened waits in a block's last unit, no atomicMax.  The thresholds start from the seeds in
+// a.gtau and tighten from the wave's own lists in `drain`, as in the shared form - which stays correct at one range.
+template <int NJ, int KCAP, bool L2, int DBG = 0, bool RANGE = false, bool SOLO = false>
 __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
     static_assert(!RANGE || !L2, "the RANGE epilogue is built for inner-product scores");
+    static_assert(!SOLO || (!RANGE && DBG == 0), "SOLO is a form of the shipped top-k kernel");
     using G = RjGeom<NJ>;
     constexpr int UK = G::UK, U = G::U, LPW = G::LPW, AD = RJ_AD, RING = G::ring(KCAP), NB_RING = G::nb_ring(RING);
     static_assert(RING >= 4, "LDS budget: the ring must hold the unit being read, the certified one and two in flight");
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
     half8 bv[G::NB_VGPR > 0 ? G::NB_VGPR : 1];
     auto qidx_of = [&](int qb) { return qbase + (qb * 4 + wave) * 32 + (lane & 31); };  // (recomputed where needed: registers)
     float tauf[2], qnv[2];
-    uint32_t pub[2];  // the k-th key's score (ordered) this lane last saw published for its query
+    [[maybe_unused]] uint32_t pub[2];  // the k-th key's score (ordered) this lane last saw published for its query (SOLO: the seed only)
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
         const int qi = qidx_of(qb);
@@ -243,13 +248,15 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
             rj_glds16(is_src, soff[i], dst + (unsigned)((wave * LPW + i) * 1024));
         } else {
             if ((is_n & 3) == wave) rj_glds16(is_src, soff[LPW], dst + (unsigned)(UK * 1024));
-            if (!RANGE && is_kh == 0 && is_n < total_units) {
+            if (!RANGE && (!SOLO || L2) && is_kh == 0 && is_n < total_units) {
                 // the block's side words, one 4-byte DMA per query block: lanes 0 .. 31 -> |y|^2 of its rows (any valid word under
                 // inner product), lanes 32 .. 63 -> the shared thresholds of this wave's queries as the other workgroups left them
                 const long long row0 = (b0 + is_blk) * 32;
                 // (inner product: ONE 4-byte DMA - words 0 .. 31 the thresholds of query block 0, words 32 .. 63 those of query
                 // block 1; squared L2: two - |y|^2 | thresholds 0, then thresholds 1 in the upper half of the second)
-                if constexpr (L2) {
+                if constexpr (SOLO) {  // (squared L2 only: the rows' |y|^2, in both halves of the one word row the epilogue reads)
+                    rj_glds4(a.bn + row0 + (lane & 31), side + ((is_blk % NB_RING) * 2) * 64);
+                } else if constexpr (L2) {
 #pragma unroll
                     for (int qb = 0; qb < 2; ++qb) {
                         const int q = qidx_of(qb) < a.nq ? qidx_of(qb) : 0;
@@ -357,7 +364,9 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
         count = 0;
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
-            if (best[qb] > pub[qb]) {  // a full list's k-th key is published to the other workgroups (fire and forget)
+            if constexpr (SOLO) {  // (best = 0: no list of this lane's query filled up in this drain)
+                if (best[qb]) tauf[qb] = fmaxf(tauf[qb], lvs_tau(best[qb]));
+            } else if (best[qb] > pub[qb]) {  // a full list's k-th key is published to the other workgroups (fire and forget)
                 tauf[qb] = fmaxf(tauf[qb], lvs_tau(best[qb]));
                 pub[qb] = best[qb];
                 if (lane < 32 && !(DBG & 512)) atomicMax(&a.gtau[qidx_of(qb)], best[qb]);
@@ -367,7 +376,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
         if (DBG & 32) d_drain += __builtin_amdgcn_s_memtime() - t_d0;
     };
     // what the other workgroups have found meanwhile (a lower bound of the k-th best over ALL rows), as it rode in with the block
-    auto take_shared = [&](int qb, uint32_t g) {
+    [[maybe_unused]] auto take_shared = [&](int qb, uint32_t g) {
         if (g > pub[qb]) {
             pub[qb] = g;
             tauf[qb] = fmaxf(tauf[qb], lvs_tau(g));
@@ -418,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
     // possible has already happened inside the block's last MFMA steps (see `unit`): the side words are in registers (gsh) and the
     // thresholds the other workgroups published are taken in.  Left for here: the wait states behind the last MFMA, the lanes'
     // maxima, "does any lane hold a candidate?" - and, rarely, the visit.
-    unsigned gsh[2] = {0u, 0u};
+    [[maybe_unused]] unsigned gsh[2] = {0u, 0u};
     auto epilogue = [&](int blk) {
         const long long row0 = (b0 + blk) * 32;
         const unsigned long long t_e0 = (DBG & 32) ? __builtin_amdgcn_s_memtime() : 0;
@@ -494,10 +503,10 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
 
     // One unit of block `blk`.  In the block's LAST unit the epilogue's memory part rides along: step UK - 7 reads the block's side
     // words (ONE more LDS read in flight: the counted waits of the next three steps allow for it), steps UK - 3 / UK - 2 take the
-    // thresholds in.
+    // thresholds in.  SOLO has no such unit: every unit keeps the plain lgkmcnt(AD - 1) schedule.
     auto unit = [&](auto khc, int blk) {
         constexpr int kh = decltype(khc)::value;
-        constexpr bool F = kh == U - 1 && !(DBG & 2) && !(DBG & 256) && !RANGE;
+        constexpr bool F = kh == U - 1 && !(DBG & 2) && !(DBG & 256) && !RANGE && !SOLO;
         constexpr int JS = UK - 7;  // the step that reads the side words
         const unsigned o_next = o_base + (slot + 1 == RING ? (unsigned)(-(RING - 1) * G::UB) : (unsigned)G::UB);
         static_for<UK>([&](auto jc) {
@@ -575,7 +584,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
         const int q = qbase + ((ql >> 5) * 4 + wave) * 32 + (ql & 31);
         if (q < a.nq) a.out[((long long)range * a.nq + q) * k + j] = mylists[ql * KCAP + j];
     }
-    if (lane < 32) {
+    if (!SOLO && lane < 32) {
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             const uint32_t lo = (uint32_t)(mylists[(qb * 32 + lane) * KCAP + k - 1] >> 32);
@@ -584,14 +593,19 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
     }
 }
 
-template <int NJ, int KCAP, bool L2, int DBG = 0, bool RANGE = false>
+template <int NJ, int KCAP, bool L2, int DBG = 0, bool RANGE = false, bool SOLO = false>
 hipError_t rj_launch_k(const LvsRqArgs& a, int grid, hipStream_t stream) {
     using G = RjGeom<NJ>;
-    const size_t lds = (size_t)G::lds_bytes(G::ring(KCAP), KCAP);
-    return lvs_launch_lds<lvs_rj_kernel<NJ, KCAP, L2, DBG, RANGE>>(dim3(grid), dim3(256), lds, stream, a);
+    const size_t lds = (size_t)G::lds_bytes(G::ring(KCAP), KCAP);  // (SOLO keeps the side-word region: RING is the same without it)
+    return lvs_launch_lds<lvs_rj_kernel<NJ, KCAP, L2, DBG, RANGE, SOLO>>(dim3(grid), dim3(256), lds, stream, a);
 }
+template <int NJ, int KCAP, bool L2>
+hipError_t rj_launch_form(const LvsRqArgs& a, int grid, hipStream_t stream, bool solo) {
+    return solo ? rj_launch_k<NJ, KCAP, L2, 0, false, true>(a, grid, stream) : rj_launch_k<NJ, KCAP, L2>(a, grid, stream);
+}
+// solo: the launch has one corpus range (the shared form is correct there too: the tuning ablations below keep it)
 template <int NJ>
-hipError_t rj_launch_nj(const LvsRqArgs& a, int grid, hipStream_t stream) {
+hipError_t rj_launch_nj(const LvsRqArgs& a, int grid, hipStream_t stream, bool solo) {
     const bool l2 = a.metric == LVS_METRIC_L2;
 #ifdef LVS_TUNING
     if (NJ == 48 && !l2 && a.k <= 10) {  // timing ablations (LVS_RQ_DEBUG; WRONG results): 1 no staging loads, 2 no epilogue, 4 + filter only, 16 no barrier
@@ -612,8 +626,8 @@ hipError_t rj_launch_nj(const LvsRqArgs& a, int grid, hipStream_t stream) {
         }
     }
 #endif
-    if (a.k <= 10) return l2 ? rj_launch_k<NJ, 10, true>(a, grid, stream) : rj_launch_k<NJ, 10, false>(a, grid, stream);
-    return l2 ? rj_launch_k<NJ, LVS_RQ_KMAX, true>(a, grid, stream) : rj_launch_k<NJ, LVS_RQ_KMAX, false>(a, grid, stream);
+    if (a.k <= 10) return l2 ? rj_launch_form<NJ, 10, true>(a, grid, stream, solo) : rj_launch_form<NJ, 10, false>(a, grid, stream, solo);
+    return l2 ? rj_launch_form<NJ, LVS_RQ_KMAX, true>(a, grid, stream, solo) : rj_launch_form<NJ, LVS_RQ_KMAX, false>(a, grid, stream, solo);
 }
 
 }  // namespace
@@ -644,21 +658,33 @@ static hipError_t rj_launch_any(LvsRqArgs& a, int dpad, hipStream_t stream, bool
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream) { return rj_launch_any(a, dpad, stream, false); }
 // The threshold join on the same launch geometry (whole 32-row blocks; inner product; a.pair_* / a.threshold / a.q_row0 set)
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream) { return rj_launch_any(a, dpad, stream, true); }
-static hipError_t rj_launch_any(LvsRqArgs& a, int dpad, hipStream_t stream, bool range_mode) {
+// groups / blocks_per_wg / nparts of a launch over a.nq queries and a.nb rows; false: not a launch of this kernel
+static bool rj_geometry(LvsRqArgs& a) {
     const int64_t nblocks = a.nb / 32;
     a.groups = (a.nq + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
     if (a.groups < 1) a.groups = 1;
-    if (a.groups > 32 && a.groups % 32 != 0) return hipErrorInvalidValue;
+    if (a.groups > 32 && a.groups % 32 != 0) return false;
     int64_t ranges = lvs_rq_ranges_for(a.groups);
-    if (ranges < 1 || nblocks < 1) return hipErrorInvalidValue;
-    a.drain_every = (int)lvs_tune("LVS_RJ_EVERY", RJ_DRAIN_EVERY);
-    if (a.drain_every < 1 || (a.drain_every & (a.drain_every - 1))) a.drain_every = RJ_DRAIN_EVERY;
+    if (ranges < 1 || nblocks < 1) return false;
     if (ranges > (nblocks + 3) / 4) ranges = (nblocks + 3) / 4;
     if (ranges < 1) ranges = 1;
     a.blocks_per_wg = (int)((nblocks + ranges - 1) / ranges);
     ranges = (nblocks + a.blocks_per_wg - 1) / a.blocks_per_wg;
     a.nparts = (int)ranges;
-    const int grid = lvs_rq_grid(a.groups, (int)ranges);
+    return true;
+}
+int lvs_rj_parts(int64_t nq, int64_t nb) {
+    LvsRqArgs a;
+    a.nq = (int)nq;
+    a.nb = nb;
+    return rj_geometry(a) ? a.nparts : 0;
+}
+static hipError_t rj_launch_any(LvsRqArgs& a, int dpad, hipStream_t stream, bool range_mode) {
+    if (!rj_geometry(a)) return hipErrorInvalidValue;
+    a.drain_every = (int)lvs_tune("LVS_RJ_EVERY", RJ_DRAIN_EVERY);
+    if (a.drain_every < 1 || (a.drain_every & (a.drain_every - 1))) a.drain_every = RJ_DRAIN_EVERY;
+    const int grid = lvs_rq_grid(a.groups, a.nparts);
+    const bool solo = !range_mode && a.nparts == 1 && lvs_tune("LVS_RJ_SOLO", LVS_RJ_SOLO_DEFAULT) != 0;
     if (range_mode) {
         if (a.metric != LVS_METRIC_IP) return hipErrorInvalidValue;
         switch (dpad / 16) {
@@ -670,10 +696,10 @@ static hipError_t rj_launch_any(LvsRqArgs& a, int dpad, hipStream_t stream, bool
         }
     }
     switch (dpad / 16) {
-        case 48: return rj_launch_nj<48>(a, grid, stream);
-        case 32: return rj_launch_nj<32>(a, grid, stream);
-        case 24: return rj_launch_nj<24>(a, grid, stream);
-        case 16: return rj_launch_nj<16>(a, grid, stream);
+        case 48: return rj_launch_nj<48>(a, grid, stream, solo);
+        case 32: return rj_launch_nj<32>(a, grid, stream, solo);
+        case 24: return rj_launch_nj<24>(a, grid, stream, solo);
+        case 16: return rj_launch_nj<16>(a, grid, stream, solo);
         default: return hipErrorInvalidValue;
     }
 }

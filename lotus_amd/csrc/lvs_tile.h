@@ -218,7 +218,19 @@ struct LvsStreamArgs {
 #define LVS_RQ_GROUPQ 256   // queries of one workgroup (eight waves x 32)
 #define LVS_RQ_MAXQ 4096    // most queries of a call lvs_rq_fits takes as ONE launch of up to 16 groups (also the seed pass' chunk)
 #define LVS_RQ_CHUNK_MAX 65536  // most queries per launch of a chunked call: 256 groups x 1 range
-#define LVS_RQ_CHUNK_DEFAULT 32768  // 128 groups x 2 ranges: fastest of 4 096 .. 65 536 at 100 k x 1 M (profiles/r10j_join_variants.log)
+// Largest chunk of a chunked top-k call (rq_chunk_len cuts greedily: 65 536 / 32 768 / 16 384 / 8 192 <= this and <= what is
+// left).  The earlier "32 768 is the fastest of 4 096 .. 65 536" (profiles/r10j_join_variants.log, r12d_knobs.log `d_64k`) compared
+// it with a 65 536 whose remainder went out in four 8 192-query launches - the slow ones of that same log: it measured the
+// remainder rule, not the geometry.  65 536 = 256 groups x 1 range: lvs_rj_kernel runs its form without threshold sharing and
+// writes the result itself (no merge).  Measured, plain bench (100 k x 1 M, 20 steps), parent and three builds alternated three
+// times on one box (profiles/rj_solo_bench_ab.jsonl): ms per step, median (spread over the alternations) - parent 120.79 (0.11);
+// greedy plan at a maximum of 32 768: 120.82 (0.14); maximum 65 536 with the shared form and the merge: 120.21 (0.05); maximum
+// 65 536, unshared form, no merge: 118.80 (0.06).  Gap to the parent 1.99 ms = 1.65 % = 18 x the larger spread; kernel ms per step
+// 119.10 -> 117.15.  (Estimated before measuring: about 2 ms, 1.5 to 2 %.)
+#ifndef LVS_RQ_CHUNK_DEFAULT  // (an A/B build may set another one on the command line)
+#define LVS_RQ_CHUNK_DEFAULT 65536
+#endif
+#define LVS_RANGE_CHUNK 32768  // rows per chunk of the threshold join (lvs_range_join): its epilogue shares nothing and its j > i skipping favours short chunks
 #define LVS_RQ_KMAX 16      // most list slots per query
 #define LVS_RQ_JOIN_DEFAULT 1  // calls beyond LVS_RQ_MAXQ queries in chunks through lvs_rq_kernel / lvs_rj_kernel (1) or through the list kernel (0)
 #define LVS_RQ_SEED_ROWS 65536  // sample rows (the first of the shard) whose scores seed the thresholds: a workgroup sees ~4 000
@@ -284,7 +296,12 @@ bool lvs_rq_shape_ok(int dpad, int k);
 hipError_t lvs_rq_launch(LvsRqArgs& a, int dpad, hipStream_t stream);
 // ---- lvs_rj.hip: the same launches with ONE wave per SIMD and 64 queries per wave (B fragments in named accumulation registers)
 #define LVS_RJ_DEFAULT 1    // launches lvs_rj_fits accepts go through lvs_rj_kernel (1) or lvs_rq_kernel (0)
+#ifndef LVS_RJ_SOLO_DEFAULT  // (an A/B build may set another one on the command line)
+#define LVS_RJ_SOLO_DEFAULT 1  // a top-k launch with ONE corpus range: the kernel's form without threshold sharing, lists written straight
+                               // to the caller's [nq][k] (1), or the shared form and a one-part merge (0)
+#endif
 bool lvs_rj_fits(int64_t nq, int64_t nb, int dpad, int k, bool has_row_ids);
+int lvs_rj_parts(int64_t nq, int64_t nb);  // corpus ranges (= lists per query) of a launch lvs_rj_fits accepts; 0: no such launch
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // whole 32-row blocks only: the caller adds the tail
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // the same geometry, RANGE epilogue (inner product)
 

@@ -4,7 +4,7 @@ usage: python tools/pmc_summary.py <gpurun_out dir> <tag>    ->  profiles/<tag>_
 HBM traffic follows /opt/skills/guides/MI355X_MICROARCH.md (section HBM): FETCH_SIZE / WRITE_SIZE are reported in KiB by
 rocprofv3; on gfx950 FETCH_SIZE counts 64 B per 128-B request for wide (16 B/lane) streaming reads, so read bytes =
 2 * FETCH_SIZE * 1024.  WRITE_SIZE is uncalibrated (taken as is); it is 5 orders of magnitude below the reads here."""
-import collections, csv, glob, json, os, sys
+import collections, csv, glob, json, os, re, sys
 
 src, tag = sys.argv[1], sys.argv[2]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +14,13 @@ out_dir = os.path.join(root, "profiles")
 os.makedirs(out_dir, exist_ok=True)
 KERNEL = "lvs_tile_kernel"
 DOMINANT = None
+
+
+def family(name):
+    """A kernel name without its last bool template argument: the launches of one step of a chunked join run lvs_rj_kernel's
+    shared form (two or more corpus ranges) and its SOLO form (one range) - one kernel for the per-launch averages."""
+    return re.sub(r", (true|false)>\(", ">(", name, count=1)
+
 
 stats = glob.glob(os.path.join(src, "prof_*", "*kernel_stats.csv"))
 summary = {}
@@ -33,17 +40,20 @@ if stats:
     # the list kernel lvs_tile_kernel<0, 4> before) - SEED-mode sample passes are other instantiations / far shorter
     cand = [r for r in rows if any(kn in r["Name"] for kn in ("lvs_rj_kernel", "lvs_rq_kernel", "lvs_tile_kernel"))]
     if cand:
-        r = max(cand, key=lambda r: float(r["TotalDurationNs"]))
-        DOMINANT = r["Name"]
-        summary["kernel"] = r["Name"]
-        summary["rocprof_kernel_avg_ms"] = float(r["AverageNs"]) / 1e6
-        summary["rocprof_kernel_calls"] = int(r["Calls"])
-        summary["rocprof_kernel_total_ms"] = float(r["TotalDurationNs"]) / 1e6
+        fams = collections.defaultdict(list)
+        for r in cand:
+            fams[family(r["Name"])].append(r)
+        DOMINANT, rs = max(fams.items(), key=lambda kv: sum(float(r["TotalDurationNs"]) for r in kv[1]))
+        total, calls = sum(float(r["TotalDurationNs"]) for r in rs), sum(int(r["Calls"]) for r in rs)
+        summary["kernel"] = " + ".join(sorted(r["Name"] for r in rs))
+        summary["rocprof_kernel_avg_ms"] = total / calls / 1e6
+        summary["rocprof_kernel_calls"] = calls
+        summary["rocprof_kernel_total_ms"] = total / 1e6
 
 counters = collections.defaultdict(list)
 for p in glob.glob(os.path.join(src, "pmc_*", "b_counter_collection.csv")):
     for r in csv.DictReader(open(p)):
-        if (r["Kernel_Name"] == DOMINANT) if DOMINANT else (KERNEL in r["Kernel_Name"] and "<0, 4>" in r["Kernel_Name"]):
+        if (family(r["Kernel_Name"]) == DOMINANT) if DOMINANT else (KERNEL in r["Kernel_Name"] and "<0, 4>" in r["Kernel_Name"]):
             counters[r["Counter_Name"]].append(float(r["Counter_Value"]))
             summary.setdefault("vgpr", int(r["VGPR_Count"]))
             summary.setdefault("sgpr", int(r["SGPR_Count"]))
