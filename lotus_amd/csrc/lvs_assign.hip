@@ -425,12 +425,13 @@ struct AssignPlan {
 };
 bool assign_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, AssignPlan& p) {
     if (nq < 0 || nb <= 0 || d <= 0) return false;
-    if ((xb_pack != LVS_PACK_F16 && xb_pack != LVS_PACK_SPLIT) || (xq_pack != LVS_PACK_F16 && xq_pack != LVS_PACK_SPLIT)) return false;
+    LvsLayout l;
+    if (lvs_layout(d, xb_pack, xq_pack, false, l) != LVS_OK) return false;
     if (nb > LVS_NEAREST3_MAX_ROWS) return false;
-    p.dpad = (int)lvs_round_up(d, LVS_BK);
-    p.nkd = p.dpad / LVS_BK;
-    p.ldb = xb_pack == LVS_PACK_SPLIT ? 2 * p.dpad : p.dpad;
-    p.ldq = xq_pack == LVS_PACK_SPLIT ? 2 * p.dpad : p.dpad;
+    p.dpad = l.dpad;
+    p.nkd = l.nkd;
+    p.ldb = l.ldb;
+    p.ldq = l.ldq;
     p.nct = (int)lvs_ceil_div(nb, LVS_BC);
     p.nqt = (int)lvs_ceil_div(nq > 0 ? nq : 1, AQ);
     // ~4096 items (16 rounds of 256 workgroups), an item at most 16 query tiles long
@@ -549,14 +550,14 @@ extern "C" int32_t lvs_resolve_pairs(const void* xb, int32_t xb_pack, const void
                                      const uint64_t* keys2, void* stream) {
     LVS_REQUIRE(d > 0 && capacity >= 0, "bad shape");
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
-    LVS_REQUIRE((xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT) && (xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT),
-                "bad pack mode %d/%d", xb_pack, xq_pack);
+    LvsLayout l;
+    LVS_REQUIRE(lvs_layout(d, xb_pack, xq_pack, false, l) == LVS_OK, "bad pack mode %d/%d", xb_pack, xq_pack);
     if (capacity == 0) return LVS_OK;
     LVS_REQUIRE(xb && xq && pair_idx && pair_count && keys && keys2, "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LVS_DEVICE_GUARD(stream);
-    const int dpad = (int)lvs_round_up(d, LVS_BK);
-    const long long ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad, ldq = xq_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
+    const int dpad = l.dpad;
+    const long long ldb = l.ldb, ldq = l.ldq;
     const dim3 grid((unsigned)lvs_ceil_div(capacity, 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define LVS_RESOLVE(QS, BS)                                                                                                  \

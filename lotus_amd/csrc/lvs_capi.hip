@@ -146,11 +146,8 @@ extern "C" int32_t lvs_timing_read_calls(double* out_total_ms, int64_t* out_laun
 // packing
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int32_t lvs_packed_ld(int32_t d, int32_t pack_mode) {
-    if (d <= 0) return LVS_EINVAL;
-    int64_t dpad = lvs_round_up(d, LVS_BK);
-    if (pack_mode == LVS_PACK_F16) return (int32_t)dpad;
-    if (pack_mode == LVS_PACK_SPLIT) return (int32_t)(2 * dpad);
-    return LVS_EINVAL;
+    LvsLayout l;
+    return lvs_layout(d, pack_mode, pack_mode, false, l) == LVS_OK ? l.ldb : LVS_EINVAL;
 }
 
 namespace {
@@ -585,11 +582,12 @@ extern "C" int32_t lvs_pack_rows_checked(const void* src, int32_t src_dtype, int
     LVS_REQUIRE(scale_exp >= -100 && scale_exp <= 100, "scale_exp %d out of range", scale_exp);
     const float pw = ldexpf(1.0f, scale_exp);
     LVS_REQUIRE(n >= 0 && d > 0, "bad shape n=%lld d=%d", (long long)n, d);
-    LVS_REQUIRE(pack_mode == LVS_PACK_F16 || pack_mode == LVS_PACK_SPLIT, "bad pack_mode %d", pack_mode);
+    LvsLayout l;
+    LVS_REQUIRE(lvs_layout(d, pack_mode, pack_mode, false, l) == LVS_OK, "bad pack_mode %d", pack_mode);
     LVS_REQUIRE(src_dtype == LVS_DTYPE_F32 || src_dtype == LVS_DTYPE_F16, "bad src_dtype %d", src_dtype);
     if (n == 0) return LVS_OK;
     LVS_REQUIRE(src && dst, "NULL buffer");
-    const int dpad = (int)lvs_round_up(d, LVS_BK);
+    const int dpad = l.dpad;
     LVS_DEVICE_GUARD(stream);
     dim3 block(256), grid((unsigned)lvs_ceil_div(n, 4));
     hipStream_t st = (hipStream_t)stream;
@@ -664,36 +662,10 @@ extern "C" int32_t lvs_gather_f32(const float* src, const int64_t* ids, int64_t 
 // search
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
-// bytes reserved for the small-batch kernel's candidate lists [ranges][nq][k]
-static inline int64_t lvs_stream_parts_bytes(int64_t nq, int k) {
-    return lvs_round_up((int64_t)((lvs_tune_set("LVS_STREAM_WGS") ? LVS_STREAM_MAXWG : 256) + 8) * (nq > 0 ? nq : 1) *
-                            (k > 0 ? k : 1) * 8, 256);
-}
-
-// ... and for the register-resident-queries kernel beyond 256 queries: `groups` query groups x at most 256 / groups corpus
-// ranges = at most 65 536 lists (+ slack), and as many sample scores
-static inline int64_t lvs_rq_parts_bytes(int64_t nq, int k) {
-    if (nq <= LVS_STREAM_MAXQ) return lvs_stream_parts_bytes(nq, k);
-    return lvs_round_up((int64_t)(65536 + 8 * nq) * (k > 0 ? k : 1) * 8, 256);
-}
-static inline int64_t lvs_rq_seed_bytes(int64_t nq) {
-    if (nq <= LVS_STREAM_MAXQ) return lvs_round_up((int64_t)(nq > 0 ? nq : 1) * (LVS_STREAM_MAXWG + 8) * 4, 256);
-    return lvs_round_up((int64_t)(65536 + 8 * nq) * 4, 256);
-}
-
-struct Plan {
-    int dpad, nkd, nk, ldb, ldq, nseg;
-    int seg_q[3], seg_c[3];
-    int ntiles, nqt, nslab, tiles_per_slab;
-    int kpass, npass;
-    int gq, lead_slabs;
-    int v2;  // 1: 256 x 256 geometry (k <= LVS2_KCAP, TOP1 / SCORES / RANGE); 0: 256 x 128 geometry (k > LVS2_KCAP)
-    int64_t off_gtau, off_partial, off_pass, off_seed, total;
-};
-
+// (layout, tile geometry, route and workspace of a call: lvs_plan.h)
 // The plan-derived fields of a tile-kernel launch over rows xb[0, nb) and queries xq[0, nq); every other field is zero, for
 // the caller to set those of its mode (outputs, k, thresholds, pairs).
-void tile_args(LvsTileArgs& a, const Plan& p, const void* xb, const void* xq, const float* bn, const float* qn, int64_t nb,
+void tile_args(LvsTileArgs& a, const LvsLayout& l, const LvsTileGeom& g, const void* xb, const void* xq, const float* bn, const float* qn, int64_t nb,
                int64_t nq, int32_t metric, int64_t id_offset) {
     memset(&a, 0, sizeof(a));
     a.xb = xb;
@@ -702,23 +674,23 @@ void tile_args(LvsTileArgs& a, const Plan& p, const void* xb, const void* xq, co
     a.qn = qn;
     a.nb = nb;
     a.nq = nq;
-    a.ldb = p.ldb;
-    a.ldq = p.ldq;
-    a.nseg = p.nseg;
+    a.ldb = l.ldb;
+    a.ldq = l.ldq;
+    a.nseg = l.nseg;
     for (int i = 0; i < 3; ++i) {
-        a.seg_q[i] = p.seg_q[i];
-        a.seg_c[i] = p.seg_c[i];
+        a.seg_q[i] = l.seg_q[i];
+        a.seg_c[i] = l.seg_c[i];
     }
-    a.nkd = p.nkd;
-    a.nk = p.nk;
+    a.nkd = l.nkd;
+    a.nk = l.nk;
     a.metric = metric;
-    a.ntiles = p.ntiles;
-    a.tiles_per_slab = p.tiles_per_slab;
-    a.nslab = p.nslab;
-    a.nqt = p.nqt;
-    a.bq = p.v2 ? LVS2_BQ : LVS3_BQ;
-    a.gq = p.gq;
-    a.lead_slabs = p.lead_slabs;
+    a.ntiles = g.ntiles;
+    a.tiles_per_slab = g.tiles_per_slab;
+    a.nslab = g.nslab;
+    a.nqt = g.nqt;
+    a.bq = g.v2 ? LVS2_BQ : LVS3_BQ;
+    a.gq = g.gq;
+    a.lead_slabs = g.lead_slabs;
     a.id_offset = id_offset;
 }
 
@@ -732,193 +704,6 @@ void seed_tile_geometry(LvsTileArgs& a, int tiles) {
     a.gq = 1;
     a.lead_slabs = 0;
     a.k = 1;
-}
-
-// Seeded thresholds of a list launch.  A launch cuts the corpus into slabs that run concurrently, and a slab whose queries
-// have no threshold yet pays a cold start of ~k (1 + ln(slab rows / k)) lock-protected insertions per query: with few query
-// tiles EVERY slab starts cold (256 queries x 1 M rows: 0.36 ms of a 1.08 ms launch), with many it is the leading slab of
-// every query tile (100 k x 125 k: 1.3 ms of 21.2).  So LVS_MODE_SEED first scores a sample (the first rows of the shard,
-// one tile per workgroup, no lists), one wave per query takes the k-th largest of the per-tile maxima as the starting
-// threshold, and the list launch only inserts rows that reach it.  Exact for the same reason as the small-batch kernel's
-// seeding: every value is a real row's score, computed by the same instructions in the same order as the list mode
-// computes it, and at least k rows reach the threshold.  Sample size: a sixteenth of the corpus for up to 64 query tiles
-// (the sample pass is negligible there and a tight threshold saves the most); beyond, the pass costs MFMA time in
-// proportion to the queries, and the smallest useful sample - max(k, 8) tiles: the threshold is the k-th largest of one
-// maximum per tile - already removes the first tiles' insertions, which is most of a cold start (100 k x 1 M, same box:
-// 10 / 61 tiles 138.5 / 139.5 ms against 140.0 unseeded; 100 k x 125 k 21.2 -> 20.4 ms, 25 k x 500 k 20.9 -> 20.3;
-// tools/seed_big_sweep.py), so it is nb / 512 rows there; never more than a sixteenth of the corpus or 64 tiles.
-// Returns the sample tiles or 0: no seeding.
-#define LVS_TILE_SEED_MAXTILES 64
-#define LVS_TILE_SEED_MAXQT 4096  // 2^20 queries: 256 B of seed workspace per query at most
-int tile_seed_tiles(int64_t nq, int64_t nb, int k) {
-    if (lvs_tune("LVS_TILE_SEED", 1) == 0 || k < 1 || k > LVS_KPASS) return 0;
-    const int64_t nqt = lvs_ceil_div(nq, LVS2_BQ);
-    long long maxqt = lvs_tune("LVS_TILE_SEED_MAXQT", LVS_TILE_SEED_MAXQT);
-    if (maxqt > LVS_TILE_SEED_MAXQT) maxqt = LVS_TILE_SEED_MAXQT;  // the workspace holds seeds up to here
-    if (nqt > maxqt) return 0;
-    const int64_t kt = k > 8 ? k : 8;
-    if (nb < 16 * (int64_t)LVS_BC * kt) return 0;
-    int64_t tiles = nb / LVS_BC / (nqt <= 64 ? lvs_tune("LVS_TILE_SEED_DIV", 16) : lvs_tune("LVS_TILE_SEED_DIV_BIG", 512));
-    if (tiles < kt) tiles = kt;
-    if (tiles > LVS_TILE_SEED_MAXTILES) tiles = LVS_TILE_SEED_MAXTILES;
-    return (int)tiles;
-}
-
-// hi_only: plan over the fp16 "hi" parts only - one K segment whatever the pack modes (lvs_flat_search_keys_hi)
-int make_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, bool hi_only, int32_t k, Plan& p,
-              bool force_v2 = false, int64_t min_slabs = 0, int64_t max_slabs_cap = 0, bool allow_l2 = true) {
-    if (nq < 0 || nb < 0 || d <= 0 || k < 0) return LVS_EINVAL;
-    if (xb_pack != LVS_PACK_F16 && xb_pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    if (xq_pack != LVS_PACK_F16 && xq_pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    p.dpad = (int)lvs_round_up(d, LVS_BK);
-    p.nkd = p.dpad / LVS_BK;
-    p.ldb = xb_pack == LVS_PACK_SPLIT ? 2 * p.dpad : p.dpad;
-    p.ldq = xq_pack == LVS_PACK_SPLIT ? 2 * p.dpad : p.dpad;
-    // x = hi + lo on either side; keep hi*hi plus the first-order cross terms (lo*lo ~ 2^-22 relative is dropped)
-    p.nseg = 0;
-    auto seg = [&](int qo, int co) {
-        p.seg_q[p.nseg] = qo;
-        p.seg_c[p.nseg] = co;
-        ++p.nseg;
-    };
-    p.seg_q[0] = p.seg_q[1] = p.seg_q[2] = p.seg_c[0] = p.seg_c[1] = p.seg_c[2] = 0;
-    seg(0, 0);
-    if (xb_pack == LVS_PACK_SPLIT && !hi_only) seg(0, p.dpad);
-    if (xq_pack == LVS_PACK_SPLIT && !hi_only) seg(p.dpad, 0);
-    p.nk = p.nseg * p.nkd;
-    p.ntiles = (int)lvs_ceil_div(nb > 0 ? nb : 1, LVS_BC);
-    // geometry: 256 queries per tile with 15 list slots (k <= 15 and every non-top-k mode), else 128 queries / 56 slots
-    p.v2 = force_v2 || k <= LVS2_KCAP;
-    // a single, at most half-full query tile: the 128-query geometry does half the (padding) MFMA work
-    if (!force_v2 && k > 1 && nq <= LVS3_BQ && lvs_tune("LVS_SMALLQ", 1) != 0) p.v2 = 0;
-    p.nqt = (int)lvs_ceil_div(nq > 0 ? nq : 1, p.v2 ? LVS2_BQ : LVS3_BQ);
-    // XCD group = gq query tiles x (32 / gq) slabs resident on one XCD at a time.  Wide groups (one corpus stream per
-    // XCD) are fastest (profiles/r01_tuning.md) but must be full: groups are dealt round-robin to the 8 XCDs, so a
-    // half-empty group idles half an XCD.  Take the widest gq that wastes < 15 % of its query-tile slots.
-    p.gq = 1;
-    const int gq_max = 32;
-    for (int g = gq_max; g >= 1; g >>= 1) {
-        const double fill = (double)p.nqt / (double)(lvs_ceil_div(p.nqt, g) * g);
-        if (fill >= 0.85) {
-            p.gq = g;
-            break;
-        }
-    }
-    // enough (query tile, slab) items to load-balance 256 CUs, slabs kept >= 32 tiles, a multiple of gs slabs
-    int64_t want = lvs_ceil_div(4096, p.nqt);
-    // Long corpus streams: 8 query tiles x 4 slabs per XCD share BOTH operands through the 4 MB L2 (hit rate 37 % -> 70 %,
-    // half the fabric traffic, +3 % clock).  Measured against the 32 x 1 groups (profiles/r02_tuning.md): 100 k x 1 M
-    // +9 % on the main loop, 100 k x 500 k 78.1 -> 72.6 ms, 100 k x 250 k 41.5 -> 38.5 ms, no difference at 100 k x 125 k
-    // (12 slabs of 40 tiles) - so it is used whenever >= 8 narrow slabs of >= 40 tiles exist.
-    int64_t slabs_l2 = 0;
-    if (allow_l2 && p.v2 && p.gq > 8 && p.nqt >= 64 && min_slabs == 0) {
-        const int64_t l2_min_slabs = lvs_tune("LVS_L2_MIN_SLABS", 8);
-        const int64_t n8 = lvs_round_up(want > l2_min_slabs ? want : l2_min_slabs, 4);
-        const int64_t min_tiles = lvs_tune("LVS_L2_MIN_TILES", 40);
-        if (p.ntiles / n8 >= min_tiles) {
-            p.gq = 8;
-            slabs_l2 = n8;
-        }
-    }
-    if (lvs_tune_set("LVS_GQ")) {  // -DLVS_TUNING builds only
-        const int v = (int)lvs_tune("LVS_GQ", 0);
-        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32) {
-            p.gq = v;
-            slabs_l2 = 0;
-        }
-    }
-    const int gs = 32 / p.gq;
-    // few query tiles: allow slabs down to 8 tiles so that every CU gets work (cold starts are cheap)
-    int64_t max_slabs = lvs_ceil_div(p.ntiles, p.nqt >= 8 ? 32 : (p.nqt >= 2 ? 16 : 8));
-    int64_t s = want < 1 ? 1 : want;
-    if (s > max_slabs) s = max_slabs;
-    s = lvs_round_up(s, gs);
-    if (s > p.ntiles) s = p.ntiles;
-    if (s < 1) s = 1;
-    p.lead_slabs = 0;
-    if (slabs_l2 > 0) {  // one leading slab per query tile in wide groups + slabs_l2 slabs in the narrow groups
-        p.lead_slabs = lvs_tune("LVS_LEAD", 1) != 0;
-        s = slabs_l2 + p.lead_slabs;
-    }
-    if (min_slabs > 0 && s < min_slabs) {  // the caller needs at least this many per-slab candidate lists
-        s = lvs_round_up(min_slabs, gs);
-        if (s > p.ntiles) s = p.ntiles;
-    }
-    if (max_slabs_cap > 0 && s > max_slabs_cap) s = max_slabs_cap;  // ... and at most this many
-    // Tail effect.  A launch is nqt * s (query tile, slab) items of equal length; an XCD (32 CUs, one workgroup each) runs
-    // 32 of ITS items at a time, so the launch lasts max over the XCDs of ceil(items of that XCD / 32) item-times
-    // (lvs_tile_xcd_rounds follows item_of_block's deal exactly, incl. the last groups spread over all XCDs).  Measured
-    // with the slab count swept (profiles/r02_tuning.md): 100 k x 1 M at 21 slabs 142.8-147.6 ms, 17 140.5-142.4,
-    // 13 139.2-139.6.  So among the slab counts near the heuristic's choice (same group shape, slabs not shorter than the
-    // heuristic allows) take the one with the smallest estimated time = rounds x (item length + its fixed cost).
-    // (r3: from one full round of items on - launches of a few query tiles run seeded, so an item's fixed cost is the same
-    // two tiles there, and e.g. 256 queries x 1 M rows go from 489 slabs x 8 tiles in two rounds to 245 x 16 in one)
-    if (min_slabs == 0 && max_slabs_cap == 0 && (int64_t)p.nqt * s >= lvs_tune("LVS_TAIL_MIN_ITEMS", 256) &&
-        lvs_tune("LVS_TAIL", 1) != 0) {
-        const int64_t lead = p.lead_slabs;
-        const int64_t hi_lim = slabs_l2 > 0 ? lead + p.ntiles / lvs_tune("LVS_L2_MIN_TILES", 40) : max_slabs;
-        double best_cost = 1e30;
-        int64_t best = s;
-        for (int64_t c = lead + gs; c <= s + s / 4 && c <= hi_lim && c <= p.ntiles; c += gs) {
-            if (10 * c < 3 * s) continue;  // stay within [0.3 s, 1.25 s]
-            const int64_t tps = lvs_ceil_div(p.ntiles, c), ns = lvs_ceil_div(p.ntiles, tps);
-            const int rounds = lvs_tile_xcd_rounds(p.nqt, (int)ns, p.gq, (int)lead);
-            // an item also pays a list cold start and its candidate write-out: about two tiles' worth.  (Round 4 swept a larger
-            // fixed cost - 6, 12, 20 tiles, i.e. fewer and longer slabs - over ten shapes: slower everywhere, by up to 19 % at
-            // 100 k x 125 k with 3 x 163 instead of 9 x 55 tiles; fine items balance the XCDs better than the round count
-            // says.  profiles/r05d_plan_sweep.log)
-            const double cost = (double)rounds * (double)(tps + 2);
-            const int64_t dist = c > s ? c - s : s - c, bdist = best > s ? best - s : s - best;
-            if (cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && dist < bdist)) {
-                best_cost = cost;
-                best = c;
-            }
-        }
-        s = best;
-    }
-    if (lvs_tune_set("LVS_NSLAB")) {  // -DLVS_TUNING builds only
-        const int64_t v = lvs_tune("LVS_NSLAB", 0);
-        if (v >= 1 && v <= p.ntiles) s = v;
-    }
-    p.tiles_per_slab = (int)lvs_ceil_div(p.ntiles, s);
-    p.nslab = (int)lvs_ceil_div(p.ntiles, p.tiles_per_slab);
-    // With around a hundred query tiles the item count pushes the 8 x 4 plan to 45-49 slabs of 40-90 tiles, and there the wide
-    // groups win (same box, profiles/r05d_plan_sweep.log: 20 k x 1 M 31.1 -> 28.5 ms, 25 k x 1 M 36.7 -> 35.6, 25 k x 500 k 19.4 ->
-    // 18.6); with 196 / 391 query tiles the 8 x 4 groups stay ahead even on 55-109-tile slabs (100 k x 125 k 20.0 vs 20.5 ms,
-    // 100 k x 250 k 37.4 vs 38.6), and from 118 query tiles on the slabs are long anyway.
-    if (slabs_l2 > 0 && p.nqt <= lvs_tune("LVS_L2_SHORT_NQT", 128) && p.tiles_per_slab < lvs_tune("LVS_L2_MIN_FINAL", 120) &&
-        !lvs_tune_set("LVS_GQ") && !lvs_tune_set("LVS_NSLAB"))
-        return make_plan(nq, nb, d, xb_pack, xq_pack, hi_only, k, p, force_v2, min_slabs, max_slabs_cap, false);
-#ifdef LVS_TUNING
-    if (lvs_tune("LVS_PLAN_PRINT", 0) != 0)
-        fprintf(stderr, "lvs plan: nq %lld nb %lld k %d -> nqt %d ntiles %d gq %d lead %d slabs %d x %d tiles, items %lld, xcd rounds %d\n",
-                (long long)nq, (long long)nb, (int)k, p.nqt, p.ntiles, p.gq, p.lead_slabs, p.nslab, p.tiles_per_slab,
-                (long long)p.nqt * p.nslab, lvs_tile_xcd_rounds(p.nqt, p.nslab, p.gq, p.lead_slabs));
-#endif
-    p.kpass = k < LVS_KPASS ? (k > 0 ? k : 1) : LVS_KPASS;  // k <= 15 -> one pass on the 256-query geometry
-    p.npass = k > 0 ? (int)lvs_ceil_div(k, p.kpass) : 0;
-    int64_t off = 256;  // the first 256 bytes hold status words (the large-k overflow flag) in every layout
-    p.off_gtau = off;
-    off += lvs_round_up(nq * 4, 256);
-    p.off_partial = off;
-    off += lvs_round_up((int64_t)p.nslab * nq * p.kpass * 8, 256);
-    p.off_pass = off;  // [nq][kpass] merged keys of one pass (multi-pass only)
-    off += p.npass > 1 ? lvs_round_up(nq * p.kpass * 8, 256) : 0;
-    // the small-batch kernel: one k-list per (corpus range, query) written from off_partial onwards, then the per-range best
-    // scores of the sample that seeds its thresholds
-    if (nq <= LVS_STREAM_MAXQ && k <= LVS_KPASS)
-        off += lvs_stream_parts_bytes(nq, k) + lvs_round_up((int64_t)(nq > 0 ? nq : 1) * (LVS_STREAM_MAXWG + 8) * 4, 256);
-    else if (k <= LVS_RQ_KMAX) {  // lvs_rq_kernel in query groups, beyond LVS_RQ_MAXQ queries one chunk of that many at a time
-        int64_t cmax = lvs_tune("LVS_RQ_CHUNK", LVS_RQ_CHUNK_DEFAULT);
-        if (cmax < LVS_RQ_MAXQ) cmax = LVS_RQ_MAXQ;
-        if (cmax > LVS_RQ_CHUNK_MAX) cmax = LVS_RQ_CHUNK_MAX;
-        const int64_t cq = nq <= cmax ? nq : cmax;
-        off += lvs_rq_parts_bytes(cq, k) + lvs_rq_seed_bytes(cq);
-    }
-    p.off_seed = off;  // [sample tiles][nq] per-tile best scores of a seeded list launch (tile_seed_tiles)
-    if (p.npass == 1) off += lvs_round_up((int64_t)(nq > 0 ? nq : 1) * tile_seed_tiles(nq, nb, k) * 4, 256);
-    p.total = off;
-    return LVS_OK;
 }
 
 // One workgroup per query: n candidate keys src[q * stride_q + (i / inner) * stride_outer + (i % inner)], i < n, are
@@ -969,13 +754,6 @@ __global__ __launch_bounds__(256) void select_keys_kernel(const u64* __restrict_
     if (topk_out)
         for (int j = threadIdx.x; j < k; j += 256) topk_out[q * out_ld + j] = j < P2 ? sk[j] : 0;
 }
-
-int pow2_ceil(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-constexpr int LVS_SELECT_MAX = 4096;  // most candidates per query select_keys_kernel sorts (32 KB of LDS)
 
 hipError_t launch_select(const u64* src, long long stride_q, int inner, long long stride_outer, int n_max,
                          const uint32_t* counts, int k, u64* kth_out, u64* topk_out, long long out_ld, uint32_t* overflow,
@@ -1034,53 +812,6 @@ hipError_t launch_merge_long(const u64* parts, int p0, int np, const u64* acc, i
     hipLaunchKernelGGL(merge_long_kernel, dim3((unsigned)nq), dim3(256), (size_t)P2 * 8, st, parts, p0, np, acc,
                        (long long)nq, k, P2, out);
     return hipGetLastError();
-}
-
-// ---- large k in two phases (k > LVS_KPASS) ----------------------------------------------------------------------
-// Phase A is a 15-per-slab top-k pass with at least 3k/15 slabs that do NOT share thresholds, so every slab's list is
-// its own exact top 15.  The lists hold 15 * nslab DISTINCT rows,
-// so the k-th largest of all their keys is a valid lower bound T of the query's true k-th best key - and a tight one
-// unless one slab holds more than 15 of the true top k.  Phase B (LVS_MODE_COLLECT) streams the corpus once more and
-// drops every key >= T into the query's bucket (>= k keys by construction); phase C sorts the bucket and keeps k.
-// Exact; two corpus passes whatever k is.  If a bucket overflows (heavily tied or slab-clustered data) the caller falls
-// back to ceil(k / LVS_KPASS) selection passes.
-struct TwoPhasePlan {
-    Plan a;             // phase A geometry: 15-slot lists (256 x 256) for moderate k, 56-slot lists (256 x 128) beyond
-    Plan b;             // phase B (collect) geometry: always 256 x 256
-    int slots;          // list slots per (query, slab) in phase A
-    int capacity;       // bucket slots per query
-    int64_t off_thr, off_cnt, off_bucket, total;
-};
-
-bool make_two_phase_plan(int64_t nq, int64_t nb, int32_t d, int32_t xb_pack, int32_t xq_pack, bool hi_only, int32_t k,
-                         TwoPhasePlan& tp) {
-    if (k <= LVS_KPASS || nq <= 0 || nb <= 0) return false;
-    if (lvs_tune("LVS_TWO_PHASE", 1) == 0) return false;
-    // 15-slot lists on the fast geometry beat 56-slot lists on the 128-query geometry at every k tried (100 .. 1000:
-    // 329 vs 402 ms, 545 vs 607 ms at 100 k x 1 M), although they need four times the slabs
-    tp.slots = LVS2_KCAP;
-    if (lvs_tune("LVS_TWO_PHASE_SLOTS", LVS2_KCAP) == LVS3_KCAP) tp.slots = LVS3_KCAP;
-    const int64_t cap_slabs = LVS_SELECT_MAX / tp.slots;        // the selection kernel sorts at most 4096 keys per query
-    int64_t want_slabs = lvs_ceil_div(2ll * k, tp.slots);       // ~2k candidates: a tight bound at a moderate slab count
-    if (want_slabs > cap_slabs) want_slabs = cap_slabs;
-    if (make_plan(nq, nb, d, xb_pack, xq_pack, hi_only, tp.slots, tp.a, tp.slots == LVS2_KCAP, want_slabs, cap_slabs) != LVS_OK)
-        return false;
-    if ((int64_t)tp.a.nslab * tp.slots > LVS_SELECT_MAX) return false;
-    if ((int64_t)tp.a.nslab * tp.slots < (int64_t)k + k / 4) return false;  // corpus too small for a useful bound
-    if (make_plan(nq, nb, d, xb_pack, xq_pack, hi_only, LVS2_KCAP, tp.b, true) != LVS_OK) return false;
-    tp.capacity = pow2_ceil(2 * k < 512 ? 512 : 2 * k);
-    if (tp.capacity > LVS_SELECT_MAX) tp.capacity = LVS_SELECT_MAX;
-    if (tp.capacity < k) return false;
-    int64_t off = tp.a.off_pass;  // gtau and the per-slab lists use the phase-A plan's layout
-    tp.off_thr = off;
-    off += lvs_round_up(nq * 8, 256);
-    tp.off_cnt = off;
-    off += lvs_round_up(nq * 4, 256);
-    tp.off_bucket = off;
-    off += lvs_round_up(nq * (int64_t)tp.capacity * 8, 256);
-    tp.total = off;
-    if (tp.total > (24ll << 30)) return false;  // lists + buckets beyond 24 GB: not worth it, use the selection passes
-    return true;
 }
 
 // Seed of the small-batch kernel's shared thresholds: gtau[q] = order key of the k-th largest of the nparts values
@@ -1160,28 +891,6 @@ hipError_t launch_merge(bool wide, const u64* parts, int nparts, int64_t nq, int
     return hipGetLastError();
 }
 
-// Chunked calls of lvs_rq_kernel / lvs_rj_kernel: a chunk is 4 096 queries (16 groups x 16 corpus ranges) or 8 192 x 2^i
-// (32 / 64 / 128 / 256 groups x 8 / 4 / 2 / 1 ranges: a multiple of 32 groups - lvs_rq_item).  rq_chunk_size: the largest such
-// size up to `want`, the call's maximum.  A call is cut greedily (rq_chunk_len): every chunk is the largest of 65 536, 32 768,
-// 16 384, 8 192 that is <= the queries left and <= the maximum, then one of 4 096 while more than 4 096 are left, then the rest -
-// 100 000 = 65 536 + 32 768 + 1 696, 50 000 = 32 768 + 16 384 + 848.  (Before this rule whatever was left below the maximum went out
-// in 8 192s - the slowest of these geometries: 100 000 at a maximum of 65 536 ran 65 536 + 4 x 8 192 + 1 696, which is what the
-// "65 536" lines of profiles/r10j_join_variants.log and r12d_knobs.log measured.)
-int64_t rq_chunk_size(int64_t want) {
-    int64_t c = LVS_RQ_MAXQ;
-    while (2 * c <= want && 2 * c <= LVS_RQ_CHUNK_MAX) c *= 2;
-    return c;
-}
-int64_t rq_chunk_len(int64_t left, int64_t chunk_max) {
-    for (int64_t c = chunk_max; c >= 8192; c /= 2)
-        if (left >= c) return c;
-    return left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left;
-}
-// the threshold join's cut (lvs_range_join), unchanged: chunks of LVS_RANGE_CHUNK rows, what is left in 8 192s, 4 096, the rest
-int64_t range_chunk_len(int64_t left) {
-    return left >= LVS_RANGE_CHUNK ? LVS_RANGE_CHUNK : (left >= 8192 ? 8192 : (left > LVS_RQ_MAXQ ? LVS_RQ_MAXQ : left));
-}
-
 // What a flat search does beyond its operands (the lvs_flat_search_keys variants)
 struct SearchOpts {
     bool hi_only = false;  // lvs_flat_search_keys_hi: planned over the fp16 "hi" parts only (one K segment whatever the pack modes)
@@ -1207,16 +916,15 @@ struct SearchCall {
     u64* out_keys;  // [nq][k]
     hipStream_t st;
     SearchOpts o;
-    Plan p;
-    char* ws;  // laid out by p
+    LvsFlatPlan p;
+    char* ws;  // laid out by p.w
     int64_t ws_bytes;
-    uint32_t* gtau;  // ws + p.off_gtau
-    u64* partial;    // ws + p.off_partial
+    uint32_t* gtau;  // ws + p.w.off_gtau
 };
 
-// a tile launch of the search over its whole corpus and all its queries, on plan pl
-void search_tile_args(LvsTileArgs& a, const SearchCall& sc, const Plan& pl, uint32_t* gtau, u64* out) {
-    tile_args(a, pl, sc.xb, sc.xq, sc.bn, sc.qn, sc.nb, sc.nq, sc.metric, sc.id_offset);
+// a tile launch of the search over its whole corpus and all its queries, on geometry g
+void search_tile_args(LvsTileArgs& a, const SearchCall& sc, const LvsTileGeom& g, uint32_t* gtau, u64* out) {
+    tile_args(a, sc.p.l, g, sc.xb, sc.xq, sc.bn, sc.qn, sc.nb, sc.nq, sc.metric, sc.id_offset);
     a.row_ids = sc.row_ids;
     a.gtau = gtau;
     a.out = out;
@@ -1233,11 +941,11 @@ int32_t search_two_phase(const SearchCall& sc, const uint32_t** pred) {
     const int k = sc.k;
     hipStream_t st = sc.st;
     TwoPhasePlan tp;
-    if (!make_two_phase_plan(nq, sc.nb, sc.d, sc.xb_pack, sc.xq_pack, sc.o.hi_only, k, tp) || tp.total > sc.ws_bytes)
+    if (!make_two_phase_plan(nq, sc.nb, k, tp) || tp.total > sc.ws_bytes)
         return LVS_OK;
     char* ws = sc.ws;
-    uint32_t* gtau2 = (uint32_t*)(ws + tp.a.off_gtau);
-    u64* lists = (u64*)(ws + tp.a.off_partial);    // [nslab][nq][slots]
+    uint32_t* gtau2 = (uint32_t*)(ws + tp.off_gtau);
+    u64* lists = (u64*)(ws + tp.off_lists);        // [nslab][nq][slots]
     u64* thr = (u64*)(ws + tp.off_thr);            // [nq]
     uint32_t* cnt = (uint32_t*)(ws + tp.off_cnt);  // [nq]
     uint32_t* flag = (uint32_t*)ws;                // status word 0: some bucket overflowed
@@ -1292,12 +1000,13 @@ int32_t search_two_phase(const SearchCall& sc, const uint32_t** pred) {
 // lvs_rj_kernel with ONE corpus range and no nb % 32 tail rows writes [1][cn][k] = the chunk's [cn][k] of out_keys itself; a
 // one-part merge_keys_kernel is a plain copy of a sorted, zero-padded list) ----
 int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
-    const Plan& p = sc.p;
+    const LvsLayout& p = sc.p.l;
     const int64_t nq = sc.nq, nb = sc.nb;
     const int k = sc.k;
     hipStream_t st = sc.st;
     uint32_t* gtau = sc.gtau;
-    u64* partial = sc.partial;
+    u64* partial = (u64*)(sc.ws + sc.p.w.off_parts);
+    float* seeds = (float*)(sc.ws + sc.p.w.off_seeds);  // [ranges][<= 4 096]
     const bool rq_ext_seeds = sc.o.ext_seeds && sc.o.ext_rows >= k;
     if (rq_join && rq_ext_seeds)  // the k-th largest of the caller's sample scores, for every query of the call at once
         LVS_HIP_CHECK(launch_seed_kth(sc.o.ext_seeds, (int)sc.o.ext_rows, nq, k, gtau, st));
@@ -1320,22 +1029,11 @@ int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
         ra.nq = (int)cn;
         ra.k = k;
         ra.metric = sc.metric;
-        // thresholds seeded from a sample of the rows scanned by this kernel's own SEED mode (bit-identical scores; see
-        // search_stream for why a caller's pooled sample scores are not used)
-        int64_t sample = nb / 8 / 1024 * 1024;
-        // (eight groups or more: a workgroup sees 30 000+ rows and fills its own lists - a quarter of the sample costs the main
-        // pass 1 % and saves 3 % of the call; profiles/r09b_rq_groups_sample_probe.log)
-        // (chunks of 16 384 queries or more see the corpus in <= 4 long ranges whose lists fill at once: half of that sample again
-        // costs the launches nothing and the sample pass half - 100 k x 1 M: call 126.0-127.8 -> 125.4-126.2 ms, same box,
-        // profiles/r12d_knobs.log)
-        const int64_t sample_cap = lvs_tune("LVS_RQ_SAMPLE", cn >= 16384 ? LVS_RQ_SEED_ROWS / 8
-                                                             : (cn > 7 * LVS_RQ_GROUPQ ? LVS_RQ_SEED_ROWS / 4 : LVS_RQ_SEED_ROWS));
-        if (sample > sample_cap) sample = sample_cap;
+        const int64_t sample = lvs_rq_sample_rows(nb, cn);  // thresholds seeded from the kernel's own SEED mode over these rows
         if (rq_join && rq_ext_seeds) {
             // seeded above
-        } else if (sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0) {
+        } else if (sample > 0) {
             // (the k-th largest of one maximum per corpus range needs >= k ranges: the sample pass keeps launches of <= 16 groups)
-            float* seeds = (float*)((char*)partial + lvs_rq_parts_bytes(cn, k));  // [ranges][<= 4 096]
             for (int64_t s0 = 0; s0 < cn; s0 += LVS_RQ_MAXQ) {
                 const int64_t sn = cn - s0 < LVS_RQ_MAXQ ? cn - s0 : LVS_RQ_MAXQ;
                 LvsRqArgs rs = ra;
@@ -1351,10 +1049,9 @@ int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
         } else {
             LVS_HIP_CHECK(hipMemsetAsync(gtau + c0, 0, (size_t)cn * 4, st));
         }
-        // (r6) one wave per SIMD, 64 queries per wave (lvs_rj.hip) for the launches it takes: whole 32-row blocks there, the
-        // corpus' last nb % 32 rows through lvs_rq_kernel as one more list per query
-        if (lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_rj_fits(cn, nb, p.dpad, k, sc.row_ids != nullptr)) {
-            if (nb % 32 == 0 && lvs_rj_parts(cn, nb) == 1 && lvs_tune("LVS_RJ_SOLO", LVS_RJ_SOLO_DEFAULT) != 0) {
+        const int kernel = lvs_rq_chunk_kernel(cn, nb, p.dpad, k, sc.row_ids != nullptr);
+        if (kernel != LVS_CHUNK_RQ) {
+            if (kernel == LVS_CHUNK_RJ_SOLO) {
                 ra.out = sc.out_keys + c0 * k;
                 ScopedKernelTimer timer(st, LVS_KERNEL_RJ, c0 > 0);
                 LVS_HIP_CHECK(lvs_rj_launch(ra, p.dpad, st));
@@ -1384,20 +1081,14 @@ int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
     return LVS_OK;
 }
 
-// the small-batch kernel's shape for a call (lvs_stream_plan)
-struct StreamShape {
-    int nbfrag;  // B fragments per query block: query K segments x dpad / 16
-    int kcap, nqb, groups;
-};
-
 // ---- lvs_stream_kernel: stream the corpus once, queries resident in LDS ----
-int32_t search_stream(const SearchCall& sc, const StreamShape& sh) {
-    const Plan& p = sc.p;
+int32_t search_stream(const SearchCall& sc, const LvsStreamShape& sh) {
+    const LvsLayout& p = sc.p.l;
     const int64_t nq = sc.nq, nb = sc.nb;
     const int k = sc.k;
     hipStream_t st = sc.st;
     uint32_t* gtau = sc.gtau;
-    u64* partial = sc.partial;
+    u64* partial = (u64*)(sc.ws + sc.p.w.off_parts);
     const int jper = p.dpad / 16;
     LvsStreamArgs sa;
     memset(&sa, 0, sizeof(sa));
@@ -1427,24 +1118,9 @@ int32_t search_stream(const SearchCall& sc, const StreamShape& sh) {
         sa.seg_c[i] = p.seg_c[i];
         sa.seg_b[i] = p.seg_q[i] == 0 ? 0 : jper;
     }
-    // Every workgroup scans its own contiguous range, all at the same time: without help each of them starts with
-    // empty lists and pays its own cold start (~k (1 + ln(range / k)) insertions per query and workgroup - with
-    // dozens of queries that, not HBM, set the time in round 2).  So with several queries the thresholds are
-    // SEEDED: the same kernel first scans a sample (the first nb / 8 rows, at most 32 768) in SEED mode - no lists,
-    // every workgroup just keeps the best score per query over its 4 row blocks - and one wave per query takes the
-    // k-th largest of those per-range maxima as the starting threshold (~15 + 5 us; round 3's first version scored the
-    // sample into a matrix with the tile kernel and radix-selected it: 130-180 us).  A workgroup of the main scan then
-    // only inserts rows that beat it (~k * nb / sample per query over the WHOLE launch).  Exact: every value is a
-    // real row's score and the k-th largest of a subset never exceeds the k-th largest of all rows; the sample
-    // rows themselves are scanned again with the rest.
-    int64_t sample = nb / 8 / 1024 * 1024;
-    if (sample > LVS_STREAM_SEED_ROWS) sample = LVS_STREAM_SEED_ROWS;
-    // A caller's pooled sample scores (ext_seeds) are NOT used here: they come from the tile kernel's SEED mode, whose
-    // accumulation order differs from this kernel's, and "the k-th largest of a subset is a lower bound" is only exact
-    // when the threshold and the scan see bit-identical scores - one ulp the wrong way could reject a true top-k row on
-    // its own shard.  This path seeds itself, with its own arithmetic.
-    if (nq >= lvs_tune("LVS_STREAM_SEED_MINQ", 2) && sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0) {
-        float* seeds = (float*)((char*)partial + lvs_stream_parts_bytes(nq, k));  // [ranges][nq]
+    const int64_t sample = lvs_stream_sample_rows(nq, nb);  // seeded thresholds: the kernel's own SEED mode over these rows
+    if (sample > 0) {
+        float* seeds = (float*)(sc.ws + sc.p.w.off_seeds);  // [ranges][nq]
         LvsStreamArgs ss = sa;
         ss.nb = sample;
         ss.seed_out = seeds;
@@ -1464,13 +1140,14 @@ int32_t search_stream(const SearchCall& sc, const StreamShape& sh) {
 // ---- the list kernel (lvs_tile.hip): ceil(k / LVS_KPASS) passes of per-slab lists and their merge; pred (nullable): every
 // launch is a no-op unless *pred != 0 (the fallback of the two-phase search) ----
 int32_t search_list_passes(const SearchCall& sc, const uint32_t* pred) {
-    const Plan& p = sc.p;
+    const LvsTileGeom& p = sc.p.g;
+    const LvsWorkspace& w = sc.p.w;
     const int64_t nq = sc.nq;
     const int k = sc.k;
     hipStream_t st = sc.st;
     uint32_t* gtau = sc.gtau;
-    u64* partial = sc.partial;
-    u64* passbuf = (u64*)(sc.ws + p.off_pass);
+    u64* partial = (u64*)(sc.ws + w.off_partial);
+    u64* passbuf = (u64*)(sc.ws + w.off_pass);
     LvsTileArgs a;
     search_tile_args(a, sc, p, gtau, partial);
     a.pred = pred;
@@ -1488,24 +1165,24 @@ int32_t search_list_passes(const SearchCall& sc, const uint32_t* pred) {
     // (best score, lowest row among equals).
     bool use_top1 = k == 1 && !sc.row_ids && p.tiles_per_slab <= 64;
     if (lvs_tune_set("LVS_TOP1")) use_top1 = k == 1 && !sc.row_ids && lvs_tune("LVS_TOP1", 0) != 0;  // -DLVS_TUNING only
-    for (int pass = 0; pass < p.npass; ++pass) {
-        const int col0 = pass * p.kpass;
-        const int kp = (k - col0) < p.kpass ? (k - col0) : p.kpass;
+    for (int pass = 0; pass < w.npass; ++pass) {
+        const int col0 = pass * w.kpass;
+        const int kp = (k - col0) < w.kpass ? (k - col0) : w.kpass;
         a.k = kp;
         // pass > 0: only keys strictly below the last key of the previous pass take part
         a.ub = pass == 0 ? nullptr : sc.out_keys + (col0 - 1);
         a.ub_stride = k;
-        const bool banded = sc.o.kc > 0 && sc.o.kc < kp && p.npass == 1 && !pred && !use_top1 && sc.qn;
+        const bool banded = sc.o.kc > 0 && sc.o.kc < kp && w.npass == 1 && !pred && !use_top1 && sc.qn;
         a.kc = banded ? sc.o.kc : 0;
         a.bscale = banded ? sc.o.bscale : 0.f;
         a.bslack = banded ? sc.o.bslack : 0.f;
-        const bool seedable = pass == 0 && p.npass == 1 && !pred && !use_top1;
+        const bool seedable = pass == 0 && w.npass == 1 && !pred && !use_top1;
         const int seed_tiles = seedable ? tile_seed_tiles(nq, sc.nb, kp) : 0;
         if (seedable && sc.o.ext_seeds && sc.o.ext_rows >= kp) {  // the caller's pooled sample scores (every shard's sample)
             LVS_HIP_CHECK(launch_seed_kth(sc.o.ext_seeds, (int)sc.o.ext_rows, nq, kp, gtau, st, a.kc, sc.qn, a.bscale,
                                           a.bslack));  // writes every gtau[q]
         } else if (seed_tiles > 0) {  // thresholds seeded from a sample instead of cold starts (tile_seed_tiles)
-            float* seeds = (float*)(sc.ws + p.off_seed);
+            float* seeds = (float*)(sc.ws + w.off_tile_seeds);
             LvsTileArgs sd = a;
             seed_tile_geometry(sd, seed_tiles);
             sd.kc = 0;
@@ -1522,10 +1199,10 @@ int32_t search_list_passes(const SearchCall& sc, const uint32_t* pred) {
             ScopedKernelTimer timer(st);
             LVS_HIP_CHECK(lvs_tile_launch(use_top1 ? LVS_MODE_TOP1 : LVS_MODE_TOPK, a, st));
         }
-        if (p.npass == 1 && kp == 1) {
+        if (w.npass == 1 && kp == 1) {
             hipLaunchKernelGGL(merge_top1_kernel, dim3((unsigned)lvs_ceil_div(nq, 256)), dim3(256), 0, st, partial, p.nslab,
                                (long long)nq, sc.out_keys, (long long)k);
-        } else if (p.npass == 1) {
+        } else if (w.npass == 1) {
             // few queries, many slabs: one workgroup of 16 waves per query (one wave per query walks hundreds of partial
             // lists as a chain of dependent loads: 150 us of a 0.5 ms call at 256 queries x 489 slabs)
             const bool wide = !pred && p.nslab >= 16 && nq <= 4096;
@@ -1557,11 +1234,7 @@ int32_t search_list_passes(const SearchCall& sc, const uint32_t* pred) {
 
 extern "C" int64_t lvs_flat_search_workspace_bytes(int64_t nq, int64_t nb, int32_t d, int32_t k, int32_t xb_pack,
                                                    int32_t xq_pack) {
-    Plan p;
-    if (make_plan(nq, nb, d, xb_pack, xq_pack, false, k, p) != LVS_OK) return LVS_EINVAL;
-    TwoPhasePlan tp;
-    if (make_two_phase_plan(nq, nb, d, xb_pack, xq_pack, false, k, tp) && tp.total > p.total) return tp.total;
-    return p.total;
+    return lvs_flat_workspace_bytes(nq, nb, d, k, xb_pack, xq_pack);
 }
 
 static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
@@ -1569,8 +1242,8 @@ static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, con
                                 const float* xq_norms_sq, int64_t id_offset, const uint32_t* row_ids,
                                 uint64_t* out_keys, void* workspace, int64_t workspace_bytes, void* stream,
                                 const SearchOpts& o) {
-    Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, o.hi_only, k, p) == LVS_OK,
+    LvsFlatPlan p;
+    LVS_REQUIRE(lvs_flat_plan(nq, nb, d, xb_pack, xq_pack, o.hi_only, k, p) == LVS_OK,
                 "bad shape nq=%lld nb=%lld d=%d k=%d pack=%d/%d", (long long)nq, (long long)nb, d, k, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(k <= LVS_MAX_K, "k=%d exceeds LVS_MAX_K", k);
@@ -1585,40 +1258,26 @@ static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, con
     }
     LVS_REQUIRE(xb && xq, "NULL rows");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
-    if (workspace_bytes < p.total || !workspace) {
-        lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)p.total, (long long)workspace_bytes);
+    if (workspace_bytes < p.w.total || !workspace) {
+        lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)p.w.total, (long long)workspace_bytes);
         return LVS_ENOMEM;
     }
     char* ws = (char*)workspace;
     const SearchCall sc = {xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, id_offset, d, metric, k, xb_pack, xq_pack, row_ids,
-                           (u64*)out_keys, st, o, p, ws, workspace_bytes, (uint32_t*)(ws + p.off_gtau), (u64*)(ws + p.off_partial)};
+                           (u64*)out_keys, st, o, p, ws, workspace_bytes, (uint32_t*)(ws + p.w.off_gtau)};
 
     const uint32_t* pred = nullptr;
     const int32_t rc = search_two_phase(sc, &pred);
     if (rc != LVS_OK) return rc;
 
-    // ---- routing: one path serves the (rest of the) call ----
-    // 97 .. 256 queries (and up to 4 096 in groups of 256), one K segment of fp16 k-slices: the queries live in REGISTERS
-    // (lvs_rq.hip), the corpus streams through LDS once - between the HBM-bound batches below and the joins the list kernel is
-    // built for.  (r6) Beyond 4 096 queries the same launch repeats per CHUNK of queries (search_rq_chunks).
-    const bool rq_ok = lvs_tune("LVS_RQ", 1) != 0 && p.nseg == 1 && p.npass == 1 && !pred && o.kc == 0;
-    // (a corpus SHARD qualifies from 32 768 rows on: its thresholds may come from the caller - the pooled sample scores of all
-    // shards, scored by the list kernel's SEED mode in the same arithmetic - or from its own first rows)
-    const bool rq_join = rq_ok && nq > LVS_RQ_MAXQ && lvs_tune("LVS_RQ_JOIN", LVS_RQ_JOIN_DEFAULT) != 0 &&
-                         lvs_rq_shape_ok(p.dpad, k) && nb >= lvs_tune("LVS_RQ_JOIN_MINROWS", LVS_RQ_JOIN_MINROWS);
-    if (rq_join || (rq_ok && lvs_rq_fits(nq, nb, p.dpad, k))) return search_rq_chunks(sc, rq_join);
-    // HBM-bound regime (the literal sem_search: one query per call; small batches up to 256 queries): the small-batch kernel
-    StreamShape sh = {0, 0, 0, 0};
-    sh.nbfrag = ((xq_pack == LVS_PACK_SPLIT && !o.hi_only) ? 2 : 1) * (p.dpad / 16);
-    const bool stream_fits = lvs_stream_plan(nq, k, sh.nbfrag, &sh.kcap, &sh.nqb, &sh.groups) > 0;
-    const bool stream_want = lvs_tune("LVS_STREAM", 1) != 0 && nq <= lvs_tune("LVS_STREAM_MAXQ_RT", LVS_STREAM_MAXQ);
-    // several sibling workgroups per corpus range (beyond 96 fp16 queries) leave the HBM-bound regime - the siblings'
-    // re-reads are bound by the fabric behind the L2 (0.45 / 0.70 ms at 128 / 256 queries x 1 M rows) - while the seeded
-    // list kernel runs such batches near its MFMA rate: the stream kernel keeps the single-group batches
-    const bool stream_beyond = sh.groups > lvs_tune("LVS_STREAM_MAXG", 1) && p.npass == 1 && tile_seed_tiles(nq, nb, k) > 0;
-    if (stream_want && stream_fits && nb >= 4096 && !stream_beyond) return search_stream(sc, sh);
-    // everything else, and the predicated fallback of the two-phase search: the list kernel
-    return search_list_passes(sc, pred);
+    // one path serves the (rest of the) call; the list kernel is also the predicated fallback of the two-phase search
+    const LvsRoute route = lvs_flat_route(nq, nb, p.l, k, p.w.npass, o.kc, pred != nullptr);
+    switch (route.kind) {
+        case LVS_ROUTE_RQ: return search_rq_chunks(sc, false);
+        case LVS_ROUTE_RQ_JOIN: return search_rq_chunks(sc, true);
+        case LVS_ROUTE_STREAM: return search_stream(sc, route.stream);
+        default: return search_list_passes(sc, pred);
+    }
 }
 
 extern "C" int32_t lvs_flat_search_keys(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
@@ -1659,8 +1318,8 @@ extern "C" int32_t lvs_flat_search_seed_tiles(int64_t nq, int64_t nb, int32_t k)
 extern "C" int32_t lvs_flat_search_seed_scores(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack,
                                                int64_t nq, int32_t d, int32_t metric, const float* xb_norms_sq,
                                                const float* xq_norms_sq, int32_t tiles, float* out_scores, void* stream) {
-    Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
+    LvsTilePlan p;
+    LVS_REQUIRE(lvs_plain_tile_plan(nq, nb, d, xb_pack, xq_pack, p) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
                 (long long)nq, (long long)nb, d, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(tiles >= 0, "bad tile count %d", tiles);
@@ -1679,7 +1338,7 @@ extern "C" int32_t lvs_flat_search_seed_scores(const void* xb, int32_t xb_pack, 
     LVS_REQUIRE(xb && xq, "NULL rows");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LvsTileArgs a;
-    tile_args(a, p, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, 0);
+    tile_args(a, p.l, p.g, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, 0);
     seed_tile_geometry(a, have);
     a.seed_out = out_scores;
     LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_SEED, a, st));
@@ -1687,17 +1346,17 @@ extern "C" int32_t lvs_flat_search_seed_scores(const void* xb, int32_t xb_pack, 
 }
 
 extern "C" int64_t lvs_nearest_hi_workspace_bytes(int64_t nq, int64_t nb, int32_t d) {
-    Plan p;
-    if (make_plan(nq, nb, d, LVS_PACK_F16, LVS_PACK_F16, false, 1, p, true) != LVS_OK) return LVS_EINVAL;
-    return 256 + lvs_round_up((int64_t)p.nslab * nq * 8, 256) + lvs_round_up((int64_t)p.nslab * nq * 4, 256);
+    LvsTilePlan p;
+    if (lvs_plain_tile_plan(nq, nb, d, LVS_PACK_F16, LVS_PACK_F16, p) != LVS_OK) return LVS_EINVAL;
+    return 256 + lvs_round_up((int64_t)p.g.nslab * nq * 8, 256) + lvs_round_up((int64_t)p.g.nslab * nq * 4, 256);
 }
 
 extern "C" int32_t lvs_nearest_hi(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack, int64_t nq,
                                   int32_t d, int32_t metric, const float* xb_norms_sq, const float* xq_norms_sq,
                                   int64_t id_offset, uint64_t* out_keys, float* out_second, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
-    Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
+    LvsTilePlan p;
+    LVS_REQUIRE(lvs_plain_tile_plan(nq, nb, d, xb_pack, xq_pack, p) == LVS_OK, "bad shape nq=%lld nb=%lld d=%d pack=%d/%d",
                 (long long)nq, (long long)nb, d, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(id_offset >= 0 && id_offset + nb < 0xFFFFFFFFll, "ids must stay below 2^32-1");
@@ -1714,22 +1373,22 @@ extern "C" int32_t lvs_nearest_hi(const void* xb, int32_t xb_pack, int64_t nb, c
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace + 256;
     u64* pk = (u64*)ws;
-    float* ps = (float*)(ws + lvs_round_up((int64_t)p.nslab * nq * 8, 256));
+    float* ps = (float*)(ws + lvs_round_up((int64_t)p.g.nslab * nq * 8, 256));
     LvsTileArgs a;
-    tile_args(a, p, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, id_offset);
+    tile_args(a, p.l, p.g, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, id_offset);
     // SPLIT rows keep their leading dimension; only the fp16 "hi" half (columns [0, dpad)) is read
     a.nseg = 1;
-    a.nk = p.nkd;
+    a.nk = p.l.nkd;
     a.bq = LVS2_BQ;
     a.k = 1;
-    a.out = p.nslab == 1 ? (u64*)out_keys : pk;
-    a.out_second = p.nslab == 1 ? out_second : ps;
+    a.out = p.g.nslab == 1 ? (u64*)out_keys : pk;
+    a.out_second = p.g.nslab == 1 ? out_second : ps;
     {
         ScopedKernelTimer timer(st);
         LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOP2, a, st));
     }
-    if (p.nslab > 1) {
-        hipLaunchKernelGGL(merge_top2_kernel, dim3((unsigned)lvs_ceil_div(nq, 256)), dim3(256), 0, st, pk, ps, p.nslab,
+    if (p.g.nslab > 1) {
+        hipLaunchKernelGGL(merge_top2_kernel, dim3((unsigned)lvs_ceil_div(nq, 256)), dim3(256), 0, st, pk, ps, p.g.nslab,
                            (long long)nq, (u64*)out_keys, out_second);
         LVS_HIP_CHECK(hipGetLastError());
     }
@@ -1742,19 +1401,17 @@ extern "C" int32_t lvs_rescore_keys(const void* xb, int32_t xb_pack, const void*
     LVS_REQUIRE(nq >= 0 && d > 0 && k >= 0, "bad shape");
     if (k == 0) return LVS_OK;
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
-    LVS_REQUIRE((xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT) && (xq_pack == LVS_PACK_F16 || xq_pack == LVS_PACK_SPLIT),
-                "bad pack mode %d/%d", xb_pack, xq_pack);
+    LvsLayout l;
+    LVS_REQUIRE(lvs_layout(d, xb_pack, xq_pack, false, l) == LVS_OK, "bad pack mode %d/%d", xb_pack, xq_pack);
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(xb && xq && keys, "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LVS_DEVICE_GUARD(stream);
-    const int dpad = (int)lvs_round_up(d, LVS_BK);
-    const long long ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad, ldq = xq_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
     const dim3 grid((unsigned)lvs_ceil_div(nq * k, 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define LVS_RESCORE(QS, BS)                                                                                              \
-    hipLaunchKernelGGL((rescore_keys_kernel<QS, BS>), grid, block, 0, st, (const _Float16*)xb, ldb, (const _Float16*)xq, ldq, \
-                       dpad, metric, xb_norms_sq, xq_norms_sq, (long long)id_offset, (long long)nq, (int)k, (u64*)keys)
+    hipLaunchKernelGGL((rescore_keys_kernel<QS, BS>), grid, block, 0, st, (const _Float16*)xb, (long long)l.ldb, (const _Float16*)xq, \
+                       (long long)l.ldq, l.dpad, metric, xb_norms_sq, xq_norms_sq, (long long)id_offset, (long long)nq, (int)k, (u64*)keys)
     if (xq_pack == LVS_PACK_SPLIT && xb_pack == LVS_PACK_SPLIT) LVS_RESCORE(1, 1);
     else if (xq_pack == LVS_PACK_SPLIT) LVS_RESCORE(1, 0);
     else if (xb_pack == LVS_PACK_SPLIT) LVS_RESCORE(0, 1);
@@ -1904,16 +1561,16 @@ extern "C" int32_t lvs_keys_to_result(const uint64_t* keys, int64_t nq, int32_t 
 extern "C" int32_t lvs_scores(const void* xb, int32_t xb_pack, int64_t nb, const void* xq, int32_t xq_pack, int64_t nq,
                               int32_t d, int32_t metric, const float* xb_norms_sq, const float* xq_norms_sq,
                               int32_t score_exp, float* out, int64_t ld_out, void* stream) {
-    Plan p;
+    LvsTilePlan p;
     LVS_REQUIRE(score_exp >= -120 && score_exp <= 120, "score_exp %d out of range", score_exp);
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape");
+    LVS_REQUIRE(lvs_plain_tile_plan(nq, nb, d, xb_pack, xq_pack, p) == LVS_OK, "bad shape");
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     if (nq == 0 || nb == 0) return LVS_OK;
     LVS_REQUIRE(xb && xq && out && ld_out >= nb, "bad buffers");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
     LVS_DEVICE_GUARD(stream);
     LvsTileArgs a;
-    tile_args(a, p, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, 0);
+    tile_args(a, p.l, p.g, xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, metric, 0);
     a.scores = out;
     a.ld_scores = ld_out;
     a.out_scale = ldexpf(1.0f, -score_exp);
@@ -1927,9 +1584,9 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
                                   float threshold, int32_t score_exp, int64_t q_row0, int64_t id_offset,
                                   int32_t qt_stride, int32_t qt_phase, int64_t capacity, int64_t* out_q, int64_t* out_j,
                                   float* out_s, uint64_t* out_count, void* stream) {
-    Plan p;
+    LvsTilePlan p;
     LVS_REQUIRE(score_exp >= -120 && score_exp <= 120, "score_exp %d out of range", score_exp);
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p, true) == LVS_OK, "bad shape");
+    LVS_REQUIRE(lvs_plain_tile_plan(nq, nb, d, xb_pack, xq_pack, p) == LVS_OK, "bad shape");
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(capacity >= 0 && out_count, "bad output buffers");
     LVS_REQUIRE(qt_stride >= 1 && qt_phase >= 0 && qt_phase < qt_stride, "bad tile dealing %d/%d", qt_phase, qt_stride);
@@ -1943,10 +1600,8 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
     // one launch of the list kernel over queries [c0, c0 + cn) x rows [r0, r0 + rn), query tiles dealt stride / phase
     auto tile_launch = [&](int64_t c0, int64_t cn, int64_t r0, int64_t rn, int32_t stride, int32_t phase,
                            bool continuation) -> int32_t {
-        Plan pl;
-        LVS_REQUIRE(make_plan(cn, rn, d, xb_pack, xq_pack, false, 1, pl, true) == LVS_OK, "bad shape");
         LvsTileArgs a;
-        tile_args(a, pl, (const char*)xb + r0 * pl.ldb * 2, (const char*)xq + c0 * pl.ldq * 2,
+        tile_args(a, p.l, lvs_tile_geometry(lvs_tile_request_plain(cn, rn)), (const char*)xb + r0 * p.l.ldb * 2, (const char*)xq + c0 * p.l.ldq * 2,
                   xb_norms_sq ? xb_norms_sq + r0 : nullptr, xq_norms_sq ? xq_norms_sq + c0 : nullptr, rn, cn, metric,
                   id_offset + r0);
         a.k = 1;
@@ -1971,7 +1626,7 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
     // kernel.  Same pairs (keys are scores of the same MFMA sequence), one shared counter.
     const bool rj_range = lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_tune("LVS_RJ_RANGE", 1) != 0 && xb_pack == LVS_PACK_F16 &&
                           xq_pack == LVS_PACK_F16 && metric == LVS_METRIC_IP && qt_stride == 1 && nq >= 2048 &&
-                          lvs_rq_shape_ok(p.dpad, 1);
+                          lvs_rq_shape_ok(p.l.dpad, 1);
     if (!rj_range) return tile_launch(0, nq, 0, nb, qt_stride, qt_phase, false);
     bool first = true;
     for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
@@ -1990,11 +1645,11 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
         if (take) {
             LvsRqArgs ra;
             memset(&ra, 0, sizeof(ra));
-            ra.xb = (const char*)xb + r0 * p.ldb * 2;
-            ra.xq = (const _Float16*)xq + c0 * p.ldq;
+            ra.xb = (const char*)xb + r0 * p.l.ldb * 2;
+            ra.xq = (const _Float16*)xq + c0 * p.l.ldq;
             ra.nb = rn;
-            ra.ldb = p.ldb;
-            ra.ldq = p.ldq;
+            ra.ldb = p.l.ldb;
+            ra.ldq = p.l.ldq;
             ra.id_offset = id_offset + r0;
             ra.nq = (int)cn;
             ra.k = 1;
@@ -2010,7 +1665,7 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
             ra.out_scale = out_scale;
             {
                 ScopedKernelTimer timer(st, LVS_KERNEL_RJ, !first);
-                LVS_HIP_CHECK(lvs_rj_range_launch(ra, p.dpad, st));
+                LVS_HIP_CHECK(lvs_rj_range_launch(ra, p.l.dpad, st));
             }
             first = false;
             if (r_full < nb) {  // the corpus' last nb % 32 rows
@@ -2050,9 +1705,8 @@ struct TimingPause {
 // does the list scan's LDS image (the tile's query fragments + its lists) fit a workgroup for queries of dimension d packed
 // with xq_pack?  hi|lo queries: d <= 1088 (k <= 16: 1216); fp16 queries: d <= 2240 (2432).  Larger shapes are not served
 bool ivf_fits(int32_t d, int32_t k, int32_t xq_pack) {
-    const int jper = (int)(lvs_round_up(d, LVS_BK) / 16);
-    const int nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper;
-    return lvs_ivf_lds_bytes(nbfrag, lvs_ivf_kcap(k)) <= 160 * 1024;
+    LvsLayout l;
+    return lvs_layout(d, xq_pack, xq_pack, false, l) == LVS_OK && lvs_ivf_lds_bytes(l.nbfrag, lvs_ivf_kcap(k)) <= 160 * 1024;
 }
 // does the SQ8 scan's LDS image (the tile's w fragments, hi|lo whatever the query's pack mode, + its lists) fit?
 bool ivf_sq8_fits(int32_t d, int32_t k) {
@@ -2185,7 +1839,7 @@ int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, S
     char* w = (char*)s.workspace;
     uint64_t* coarse = (uint64_t*)(w + L.off_coarse);
     u64* parts = (u64*)(w + L.off_parts);
-    const size_t qrow_bytes = (size_t)lvs_round_up(s.d, LVS_BK) * (s.xq_pack == LVS_PACK_SPLIT ? 2 : 1) * 2;
+    const size_t qrow_bytes = (size_t)lvs_packed_ld(s.d, s.xq_pack) * 2;
     for (int64_t q0 = 0; q0 < s.nq; q0 += L.chunk) {
         const int64_t cn = s.nq - q0 < L.chunk ? s.nq - q0 : L.chunk;
         const void* xq_c = (const char*)s.xq + (size_t)q0 * qrow_bytes;
@@ -2221,7 +1875,7 @@ int32_t ivf_group_pairs(const IvfLayout& L, char* w, const uint64_t* coarse, int
 }
 
 // the gathered-row scans' shared arguments (lvs_ivf_scan_kernel, lvs_ivf_range_kernel) that do not change from chunk to chunk
-void ivf_gather_args(LvsIvfGatherArgs& g, const Plan& p, int32_t xq_pack, const void* xb, const float* xb_norms_sq,
+void ivf_gather_args(LvsIvfGatherArgs& g, const LvsLayout& p, const void* xb, const float* xb_norms_sq,
                      const int64_t* offsets, const uint32_t* rows, const uint32_t* sel_bits, int32_t nlist, int32_t nprobe,
                      int32_t metric) {
     g.xb = xb;
@@ -2236,7 +1890,7 @@ void ivf_gather_args(LvsIvfGatherArgs& g, const Plan& p, int32_t xq_pack, const 
     g.metric = metric;
     g.jper = p.dpad / 16;
     g.nseg = p.nseg;
-    g.nbfrag = (xq_pack == LVS_PACK_SPLIT ? 2 : 1) * g.jper;
+    g.nbfrag = p.nbfrag;
     for (int i = 0; i < 3; ++i) {
         g.seg_c[i] = p.seg_c[i];
         g.seg_b[i] = p.seg_q[i] == 0 ? 0 : g.jper;
@@ -2261,9 +1915,10 @@ int32_t ivf_check_encode(int64_t n, int32_t d, int32_t nlist, int32_t M, int32_t
     LVS_REQUIRE(nlist >= 1, "nlist=%d must be >= 1", nlist);
     LVS_REQUIRE(M >= 1 && d % M == 0, "M=%d must be >= 1 and divide d=%d", M, d);
     LVS_REQUIRE(ksub >= 1 && ksub <= LVS_PQ_KSUB, "ksub=%d must be in [1, %d]", ksub, LVS_PQ_KSUB);
-    LVS_REQUIRE(xb_pack == LVS_PACK_F16 || xb_pack == LVS_PACK_SPLIT, "bad xb_pack");
-    dpad = (int)lvs_round_up(d, LVS_BK);
-    ldb = xb_pack == LVS_PACK_SPLIT ? 2 * dpad : dpad;
+    LvsLayout l;
+    LVS_REQUIRE(lvs_layout(d, xb_pack, xb_pack, false, l) == LVS_OK, "bad xb_pack");
+    dpad = l.dpad;
+    ldb = l.ldb;
     return LVS_OK;
 }
 
@@ -2328,15 +1983,15 @@ extern "C" int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int6
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(xb && offsets && rows && centroids && xq && out_keys && workspace, "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
-    Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, k, p) == LVS_OK, "bad plan");
+    LvsLayout p;
+    LVS_REQUIRE(lvs_layout(d, xb_pack, xq_pack, false, p) == LVS_OK, "bad plan");
     if (!ivf_fits(d, k, xq_pack)) {
         lvs_set_error("d=%d with k=%d does not fit the list scan's LDS (see lvs_ivf_search_workspace_bytes)", d, k);
         return LVS_EUNSUPPORTED;
     }
     LvsIvfArgs a;
     memset(&a, 0, sizeof(a));
-    ivf_gather_args(a.g, p, xq_pack, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
+    ivf_gather_args(a.g, p, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
     a.k = k;
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
@@ -2370,8 +2025,8 @@ namespace {
 // does lvs_ivf_range_kernel's LDS image (the tile's query fragments + the slot table, no lists) fit?  hi|lo queries: d <= 1216;
 // fp16 queries: d <= 2496
 bool ivf_range_fits(int32_t d, int32_t xq_pack) {
-    const int jper = (int)(lvs_round_up(d, LVS_BK) / 16);
-    return lvs_ivf_range_lds_bytes((xq_pack == LVS_PACK_SPLIT ? 2 : 1) * jper) <= 160 * 1024;
+    LvsLayout l;
+    return lvs_layout(d, xq_pack, xq_pack, false, l) == LVS_OK && lvs_ivf_range_lds_bytes(l.nbfrag) <= 160 * 1024;
 }
 }  // namespace
 
@@ -2399,15 +2054,15 @@ extern "C" int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(xb && offsets && rows && centroids && xq && workspace && (capacity == 0 || (out_q && out_j && out_s)), "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
-    Plan p;
-    LVS_REQUIRE(make_plan(nq, nb, d, xb_pack, xq_pack, false, 1, p) == LVS_OK, "bad plan");
+    LvsLayout p;
+    LVS_REQUIRE(lvs_layout(d, xb_pack, xq_pack, false, p) == LVS_OK, "bad plan");
     if (!ivf_range_fits(d, xq_pack)) {
         lvs_set_error("d=%d does not fit the threshold scan's LDS (see lvs_ivf_range_workspace_bytes)", d);
         return LVS_EUNSUPPORTED;
     }
     LvsIvfRangeArgs a;
     memset(&a, 0, sizeof(a));
-    ivf_gather_args(a.g, p, xq_pack, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
+    ivf_gather_args(a.g, p, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
     a.out_q = (long long*)out_q;
     a.out_j = (long long*)out_j;
     a.out_s = out_s;
@@ -2483,9 +2138,11 @@ extern "C" int32_t lvs_ivf_sq8_search_keys_sel(const uint8_t* codes, const float
     a.metric = metric;
     a.d = d;
     a.ldc = lvs_ivf_sq8_ldc(d);
+    LvsLayout l;
+    lvs_layout(d, xq_pack, xq_pack, false, l);  // (d and xq_pack passed ivf_check_search)
     a.qsplit = xq_pack == LVS_PACK_SPLIT;
-    a.qdpad = (int)lvs_round_up(d, LVS_BK);
-    a.ldq = a.qsplit ? 2 * a.qdpad : a.qdpad;
+    a.qdpad = l.dpad;
+    a.ldq = l.ldq;
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
@@ -2570,9 +2227,11 @@ extern "C" int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float*
     a.d = d;
     a.M = M;
     a.ldc = lvs_ivf_pq_ldc(M);
+    LvsLayout l;
+    lvs_layout(d, xq_pack, xq_pack, false, l);  // (d and xq_pack passed ivf_check_search)
     a.qsplit = xq_pack == LVS_PACK_SPLIT;
-    a.qdpad = (int)lvs_round_up(d, LVS_BK);
-    a.ldq = a.qsplit ? 2 * a.qdpad : a.qdpad;
+    a.qdpad = l.dpad;
+    a.ldq = l.ldq;
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
@@ -2633,11 +2292,13 @@ extern "C" int32_t lvs_refine_keys(const void* xb, int32_t xb_pack, int64_t nb, 
     a.out = (u64*)out_keys;
     a.nb = nb;
     a.nq = nq;
-    a.dpad = (int)lvs_round_up(d, LVS_BK);
+    LvsLayout l;
+    lvs_layout(d, xb_pack, xq_pack, false, l);  // (checked above)
+    a.dpad = l.dpad;
     a.bsplit = xb_pack == LVS_PACK_SPLIT;
     a.qsplit = xq_pack == LVS_PACK_SPLIT;
-    a.ldb = a.bsplit ? 2 * a.dpad : a.dpad;
-    a.ldq = a.qsplit ? 2 * a.dpad : a.dpad;
+    a.ldb = l.ldb;
+    a.ldq = l.ldq;
     a.kc = kc;
     a.k = k;
     a.metric = metric;

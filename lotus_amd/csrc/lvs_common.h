@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/lotus_hip.h"
+#include "lvs_plan.h"  // host planner: geometry constants, lvs_round_up / lvs_ceil_div, lvs_tune
 
 typedef unsigned long long u64;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -175,25 +176,6 @@ void lvs_set_error(const char* fmt, ...);
             return LVS_EINVAL;      \
         }                           \
     } while (0)
-
-static inline int64_t lvs_round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-static inline int64_t lvs_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// ---- tuning / debug knobs ----------------------------------------------------------------------------------
-// The shipped library reads NO environment variable: every knob below is a compile-time constant unless the library is
-// built with -DLVS_TUNING (`make tuning` -> liblotus_hip_tuning.so, reported by lvs_build_flags()).  Some knobs skip
-// work and produce wrong results on purpose (timing ablations); they exist in the tuning build only.
-#ifdef LVS_TUNING
-#include <stdlib.h>
-static inline long long lvs_tune(const char* name, long long dflt) {
-    const char* e = getenv(name);
-    return e ? atoll(e) : dflt;
-}
-static inline bool lvs_tune_set(const char* name) { return getenv(name) != nullptr; }
-#else
-#define lvs_tune(name, dflt) ((long long)(dflt))
-#define lvs_tune_set(name) (false)
-#endif
 
 // Entry points launch on `stream`; make that stream's device current for the duration of the call (the caller may
 // drive several GPUs from one process) and restore the previous one afterwards.

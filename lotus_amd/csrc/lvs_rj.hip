@@ -643,44 +643,18 @@ extern "C" int32_t lvs_rj_debug_read(unsigned long long* out16) {
 }
 #endif
 
-// Does the one-wave-per-SIMD form take this launch?  Everything lvs_rq_kernel's grouped launch takes (lvs_rq_fits) with row ids
-// that are positions (no id table: a candidate's key is built where it is found) and at least one whole 32-row block per range.
-bool lvs_rj_fits(int64_t nq, int64_t nb, int dpad, int k, bool has_row_ids) {
-    if (has_row_ids || !(dpad == 256 || dpad == 384 || dpad == 512 || dpad == 768) || nq <= 128 || k < 1 || k > LVS_RQ_KMAX) return false;
-    if (nq <= LVS_RQ_MAXQ) return lvs_rq_fits(nq, nb, dpad, k) || (nq > 2048 && nb >= LVS_RQ_JOIN_MINROWS);  // (the last chunk of a call)
-    const int64_t groups = (nq + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;  // a chunk of a larger call: 32 x 2^i groups
-    return nq <= LVS_RQ_CHUNK_MAX && groups % 32 == 0 && nb >= LVS_RQ_JOIN_MINROWS;
-}
-
 static hipError_t rj_launch_any(LvsRqArgs& a, int dpad, hipStream_t stream, bool range_mode);
 // a.nb rows are searched in whole 32-row blocks: the caller runs the last a.nb % 32 rows through lvs_rq_launch (one more list per
 // query).  On return a.nparts = candidate lists per query in a.out ([nparts][nq][k]).
 hipError_t lvs_rj_launch(LvsRqArgs& a, int dpad, hipStream_t stream) { return rj_launch_any(a, dpad, stream, false); }
 // The threshold join on the same launch geometry (whole 32-row blocks; inner product; a.pair_* / a.threshold / a.q_row0 set)
 hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream) { return rj_launch_any(a, dpad, stream, true); }
-// groups / blocks_per_wg / nparts of a launch over a.nq queries and a.nb rows; false: not a launch of this kernel
-static bool rj_geometry(LvsRqArgs& a) {
-    const int64_t nblocks = a.nb / 32;
-    a.groups = (a.nq + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
-    if (a.groups < 1) a.groups = 1;
-    if (a.groups > 32 && a.groups % 32 != 0) return false;
-    int64_t ranges = lvs_rq_ranges_for(a.groups);
-    if (ranges < 1 || nblocks < 1) return false;
-    if (ranges > (nblocks + 3) / 4) ranges = (nblocks + 3) / 4;
-    if (ranges < 1) ranges = 1;
-    a.blocks_per_wg = (int)((nblocks + ranges - 1) / ranges);
-    ranges = (nblocks + a.blocks_per_wg - 1) / a.blocks_per_wg;
-    a.nparts = (int)ranges;
-    return true;
-}
-int lvs_rj_parts(int64_t nq, int64_t nb) {
-    LvsRqArgs a;
-    a.nq = (int)nq;
-    a.nb = nb;
-    return rj_geometry(a) ? a.nparts : 0;
-}
 static hipError_t rj_launch_any(LvsRqArgs& a, int dpad, hipStream_t stream, bool range_mode) {
-    if (!rj_geometry(a)) return hipErrorInvalidValue;
+    LvsGroupedGeom g;
+    if (!lvs_grouped_geometry(a.nq, a.nb / 32, g)) return hipErrorInvalidValue;
+    a.groups = g.groups;
+    a.blocks_per_wg = g.blocks_per_wg;
+    a.nparts = g.nparts;
     a.drain_every = (int)lvs_tune("LVS_RJ_EVERY", RJ_DRAIN_EVERY);
     if (a.drain_every < 1 || (a.drain_every & (a.drain_every - 1))) a.drain_every = RJ_DRAIN_EVERY;
     const int grid = lvs_rq_grid(a.groups, a.nparts);

@@ -464,40 +464,14 @@ hipError_t rq_launch_shape(const LvsRqArgs& a, int grid, hipStream_t stream) {
 
 }  // namespace
 
-// Corpus ranges a launch of `groups` query groups uses at most: every range has one workgroup per group, all on one XCD
-// (32 CUs), a workgroup fills a CU
-static int rq_max_ranges(int groups) { return lvs_rq_ranges_for(groups); }
-
-// Does the register-resident-queries kernel take this call?  fp16 k-slices of one K segment (d padded to 256, 384, 512 or
-// 768 halfs), k <= 16, a corpus long enough to give every CU a few blocks, and 97 .. 256 queries - or up to LVS_RQ_MAXQ in
-// groups of 256 when the groups' workgroups fill (nearly) every CU (>= 224 of 256): 2 .. 8, 10, 14, 15 or 16 groups.
-bool lvs_rq_shape_ok(int dpad, int k) {  // operand shapes the register-resident kernels are built for
-    const int nj = dpad / 16;
-    return dpad % 16 == 0 && k >= 1 && k <= RQ_KMAX && (nj == 16 || nj == 24 || nj == 32 || nj == 48);
-}
-bool lvs_rq_fits(int64_t nq, int64_t nb, int dpad, int k) {
-    const int nj = dpad / 16;
-    if (!(nq > 96 && nq <= LVS_RQ_MAXQ && k >= 1 && k <= RQ_KMAX && nb >= 32768 && (nj == 16 || nj == 24 || nj == 32 || nj == 48))) return false;
-    const int groups = (int)((nq + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ);
-    if (groups == 1) return true;
-    return groups <= lvs_tune("LVS_RQ_MAXG", LVS_RQ_MAXQ / LVS_RQ_GROUPQ) && groups * rq_max_ranges(groups) >= 224 &&
-           nb >= (int64_t)32768 * groups;
-}
-
 // On return a.nparts = candidate lists per query in a.out ([nparts][nq][k]) (SEED: rows of a.seed_out [nparts][nq]).
 hipError_t lvs_rq_launch(LvsRqArgs& a, int dpad, hipStream_t stream) {
-    const int64_t nblocks = (a.nb + 31) / 32;
-    a.groups = (a.nq + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
-    if (a.groups < 1) a.groups = 1;
-    int64_t ranges = rq_max_ranges(a.groups);
-    if (ranges < 1) return hipErrorInvalidValue;
-    if (ranges > (nblocks + 3) / 4) ranges = (nblocks + 3) / 4;
-    if (ranges < 1) ranges = 1;
-    a.blocks_per_wg = (int)((nblocks + ranges - 1) / ranges);
-    ranges = (nblocks + a.blocks_per_wg - 1) / a.blocks_per_wg;
-    a.nparts = (int)ranges;
-    if (a.groups > 32 && a.groups % 32 != 0) return hipErrorInvalidValue;  // (chunks of a larger call: 32 x 2^i groups)
-    const int grid = lvs_rq_grid(a.groups, (int)ranges);
+    LvsGroupedGeom g;
+    if (!lvs_grouped_geometry(a.nq, (a.nb + 31) / 32, g)) return hipErrorInvalidValue;
+    a.groups = g.groups;
+    a.blocks_per_wg = g.blocks_per_wg;
+    a.nparts = g.nparts;
+    const int grid = lvs_rq_grid(a.groups, a.nparts);
     const bool seed = a.seed_out != nullptr;
     switch (dpad / 16) {
         case 48: return seed ? rq_launch_shape<48, 24, true>(a, grid, stream) : rq_launch_shape<48, 24, false>(a, grid, stream);

@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int SQ = 32;          // queries per query block (MFMA N)
+constexpr int SQ = LVS_STREAM_BLOCKQ;          // queries per query block (MFMA N)
 // UNROLL = A-fragment loads in flight per wave (1 KB each) = fragments per inner-loop iteration: a template parameter so
 // that the branch-free fast path exists for every row length whose fragment count per K segment is a multiple of 8:
 //   16 (d = 256, 512, 768, 1024, ...), 24 (d = 384 - BASELINE configs[0]'s dimension -, 1152), 8 (d = 128, 640, ...)
@@ -337,52 +337,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void lvs_stream_ker
 }
 
 // host side -----------------------------------------------------------------------------------------------------
-// corpus ranges of a launch: one per CU when every workgroup has its own range, 256 / G with G sibling groups
-int lvs_stream_ranges(int64_t nb, int groups) {
-    const int64_t nblocks = (nb + 31) / 32;
-    int64_t r = 256 / (groups > 0 ? groups : 1) / (groups > 1 ? 8 : 1) * (groups > 1 ? 8 : 1);  // siblings: multiples of 8
-    if (groups <= 1 && lvs_tune("LVS_STREAM_WGS", 0) > 0) r = lvs_tune("LVS_STREAM_WGS", 0);  // -DLVS_TUNING builds only
-    if (r > LVS_STREAM_MAXWG) r = LVS_STREAM_MAXWG;
-    if (groups > 1) {
-        // siblings are consecutive slots of one XCD: ranges come in multiples of 8 (one per XCD and slot group)
-        int64_t cap = (nblocks + 3) / 4;
-        cap = cap / 8 * 8;
-        if (r > cap) r = cap;
-        if (r < 8) r = 8;
-    } else {
-        if (r > (nblocks + 3) / 4) r = (nblocks + 3) / 4;
-        if (r < 1) r = 1;
-    }
-    return (int)r;
-}
-
-size_t lvs_stream_lds_bytes(int nbfrag, int nqb, int kcap) {
-    return (size_t)nqb * nbfrag * 1024 + (size_t)nqb * SQ * kcap * 8 + (size_t)nqb * SQ * 4;
-}
-
-// How a call is laid out: *out_nqb = 32-query blocks per workgroup (1, 2 or 3), *out_groups = sibling workgroups per corpus
-// range (1 .. 4), *out_kcap = list slots per query.  Fewest groups first: every group is one more pass of the corpus
-// through the fabric (measured, 1 M x 768: 64 queries in one group 0.26 ms, 128 in two 0.38 ms, 256 in four 0.70 ms - the
-// siblings drift apart by more than an L2's worth of stream, so the memory-side cache, not the L2, serves the re-reads);
-// then the fewest blocks per workgroup (more list slots, less LDS).  Returns 0 when the call does not fit the streaming
-// kernel (too many queries / k for the LDS left beside the query fragments).
-int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* out_nqb, int* out_groups) {
-    if (nq < 1 || nq > LVS_STREAM_MAXQ || k < 1 || k > LVS_KPASS) return 0;
-    const int blocks = (int)((nq + SQ - 1) / SQ);
-    for (int groups = 1; groups <= 4; ++groups) {
-        const int nqb = (blocks + groups - 1) / groups;
-        if (nqb > 3) continue;
-        // one block keeps the full 64 slots (any k <= 56 costs the same insertion step); more blocks trade slots for queries
-        const int kcap = nqb == 1 ? 64 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
-        if (lvs_stream_lds_bytes(nbfrag, nqb, kcap) > 160 * 1024) continue;  // a workgroup may use the whole 160 KiB
-        if (out_kcap) *out_kcap = kcap;
-        if (out_nqb) *out_nqb = nqb;
-        if (out_groups) *out_groups = groups;
-        return nqb;
-    }
-    return 0;
-}
-
 template <int U, int NQB, int WAVES, bool SEED>
 static hipError_t stream_launch_one(const LvsStreamArgs& a, int grid, size_t lds, hipStream_t stream) {
     return lvs_launch_lds<lvs_stream_kernel<U, NQB, WAVES, SEED>>(dim3(grid), dim3(WAVES * 64), lds, stream, a);
@@ -410,20 +364,12 @@ static hipError_t stream_launch_mode(const LvsStreamArgs& a, int grid, size_t ld
 // a.nqb / a.groups / a.kcap come from lvs_stream_plan.  On return a.nparts = candidate lists per query in a.out
 // ([nparts][nq][k]).
 hipError_t lvs_stream_launch(LvsStreamArgs& a, hipStream_t stream) {
-    const int64_t nblocks = (a.nb + 31) / 32;
     if (a.groups < 1 || a.groups > 4) return hipErrorInvalidValue;
     if (a.nqb < 1 || a.nqb > 3 || a.kcap < a.k || a.kcap > 64) return hipErrorInvalidValue;
     if ((long long)a.nqb * SQ * a.groups < a.nq) return hipErrorInvalidValue;
-    int ranges = lvs_stream_ranges(a.nb, a.groups);
-    a.blocks_per_wg = (int)((nblocks + ranges - 1) / ranges);
+    lvs_stream_geometry(a.nb, a.groups, &a.blocks_per_wg, &a.nparts);
     a.debug = (int)lvs_tune("LVS_STREAM_DEBUG", 0);
-    if (a.groups > 1) {
-        ranges = (int)((((nblocks + a.blocks_per_wg - 1) / a.blocks_per_wg) + 7) / 8 * 8);  // empty ranges write empty lists
-    } else {
-        ranges = (int)((nblocks + a.blocks_per_wg - 1) / a.blocks_per_wg);
-    }
-    a.nparts = ranges;
-    const int grid = ranges * a.groups;
+    const int grid = a.nparts * a.groups;
     const size_t lds = lvs_stream_lds_bytes(a.nbfrag, a.nqb, a.kcap);
     if (a.seed_out) return stream_launch_mode<true>(a, grid, lds, stream);
     return stream_launch_mode<false>(a, grid, lds, stream);

@@ -1,0 +1,34 @@
+"""tests/native/plan_check.cpp - the flat search's host planner (lotus_amd/csrc/lvs_plan.h) as a program - built once per
+session with the host C++ compiler (no HIP, no GPU)."""
+import atexit
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@functools.lru_cache(maxsize=None)
+def exe():
+    tmp = tempfile.mkdtemp(prefix="plan_check_")
+    atexit.register(shutil.rmtree, tmp, True)
+    out = os.path.join(tmp, "plan_check")
+    subprocess.run([os.environ.get("CXX", "c++"), "-O2", "-std=c++17", "-Wall", "-Werror",
+                    os.path.join(ROOT, "tests", "native", "plan_check.cpp"), "-o", out], check=True)
+    return out
+
+
+def run(*args, stdin=None):
+    return subprocess.run([exe(), *args], input=stdin, capture_output=True, text=True)
+
+
+def ask(questions):
+    """--query mode: one question per line ("rq_fits nq nb dpad k", "grouped nq blocks", "chunks nq maximum", ...) -> the
+    answers, each a list of ints (None for "none")."""
+    out = run("--query", stdin="".join(q + "\n" for q in questions))
+    assert out.returncode == 0 and "?" not in out.stdout, out.stdout[-500:]
+    answers = [None if ln.strip() == "none" else [int(v) for v in ln.split()] for ln in out.stdout.splitlines()]
+    assert len(answers) == len(questions)
+    return answers

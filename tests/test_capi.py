@@ -253,6 +253,22 @@ def test_block_to_item_deal_covers_every_item_once(tmp_path):
     assert out.startswith("ok "), out
 
 
+def test_planner_invariants_hold_over_the_grid():
+    """The flat search's host planner (lotus_amd/csrc/lvs_plan.h) compiled alone by the host compiler (tests/native/plan_check.cpp):
+    over 147 840 shapes the slabs cut the tiles, the offsets are aligned and ascending, lvs_flat_search_workspace_bytes is the
+    largest layout, and the region the routed path writes holds what its launch geometry says it writes, chunk by chunk."""
+    import plan_native
+
+    out = plan_native.run()
+    assert out.returncode == 0 and out.stdout.startswith("ok 147840 shapes"), out.stdout[-1000:]
+    # the library answers with the same function
+    lib = _capi.load()
+    have = {ln.split("|")[0]: int(ln.rsplit(" ", 1)[1]) for ln in plan_native.run("--dump").stdout.splitlines()}
+    for (nq, nb, d, k, bp, qp) in [(100_000, 1_000_000, 768, 10, 0, 0), (100_000, 1_000_000, 768, 2048, 0, 0), (256, 1_000_000, 1536, 10, 1, 1),
+                                   (1, 10_000_000, 8, 2048, 0, 0), (0, 0, 8, 1, 0, 0), (65236, 10_000_000, 768, 10, 0, 1)]:
+        assert lib.lvs_flat_search_workspace_bytes(nq, nb, d, k, bp, qp) == have[f"nq={nq} nb={nb} d={d} k={k} pack={bp}/{qp} hi=0 "]
+
+
 def test_permutation_prefix_equals_the_full_permutation():
     """lvs_rand_perm_prefix_host (O(m)) against lvs_rand_perm_host and the oracle's restatement of faiss rand_perm."""
     import numpy as np

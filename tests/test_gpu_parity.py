@@ -677,7 +677,7 @@ def test_one_pass_certificate_refuses_rows_that_differ_below_fp16_resolution(hip
                                      (20_000, 330_000, 768)])   # 79 query tiles on short slabs: wide groups instead of 8 x 4
 def test_planner_shapes_sampled_parity(hip_backend, nq, nb, d):
     """Launch shapes that take the planner's 8 x 4 L2 groups with a leading slab, a remainder of groups dealt across all
-    XCDs, remainder query tiles and the wide-group fallback (lvs_tile.h, make_plan): the whole launch runs on the GPU,
+    XCDs, remainder query tiles and the wide-group fallback (lvs_plan.h, lvs_tile_geometry): the whole launch runs on the GPU,
     EIGHT queries of EVERY 256-query tile are checked against the oracle - one in each 32-query block of the tile (= one per
     (wave column, accumulator block) of the workgroup), at a lane position that walks with the tile number, so all 256
     positions of a tile are hit across the launch (a query's list depends on every (tile, slab) item of its tile)."""

@@ -35,7 +35,7 @@ _CACHE = {}
 
 
 def _range_rows(nb, nq):
-    """Rows per corpus range of one launch: lvs_rq_ranges_for's rule and rj_launch_any's rounding (lvs_tile.h, lvs_rj.hip)."""
+    """Rows per corpus range of one launch: lvs_rq_ranges_for's rule and lvs_grouped_geometry's rounding (lvs_plan.h)."""
     groups = max(1, -(-nq // 256))
     ranges = 256 if groups <= 1 else (8 * (32 // groups) if groups <= 32 else 256 // groups)
     nblocks = nb // 32

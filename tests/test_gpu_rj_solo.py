@@ -33,8 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _default_max():
-    """LVS_RQ_CHUNK_DEFAULT as the library was built (lvs_tile.h)."""
-    text = open(os.path.join(ROOT, "lotus_amd", "csrc", "lvs_tile.h")).read()
+    """LVS_RQ_CHUNK_DEFAULT as the library was built (lvs_plan.h)."""
+    text = open(os.path.join(ROOT, "lotus_amd", "csrc", "lvs_plan.h")).read()
     return int(re.search(r"^#define LVS_RQ_CHUNK_DEFAULT (\d+)", text, re.M).group(1))
 
 

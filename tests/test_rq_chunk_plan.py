@@ -1,11 +1,16 @@
 """CPU model of the greedy chunk plan of a chunked ``lvs_rq_kernel`` / ``lvs_rj_kernel`` call (``rq_chunk_size`` /
-``rq_chunk_len`` in lotus_amd/csrc/lvs_capi.hip): every chunk is the largest of 65 536, 32 768, 16 384, 8 192 that is <= the
+``rq_chunk_len`` in lotus_amd/csrc/lvs_plan.h): every chunk is the largest of 65 536, 32 768, 16 384, 8 192 that is <= the
 queries left and <= the configured maximum, then one of 4 096 while more than 4 096 are left, then the rest.
 
 ``chunks()`` in ``test_rq_groups_model.py`` describes the rule BEFORE this one (the maximum while that many are left, then
 8 192s, one 4 096, the rest) and stays there as a record; the threshold join (``lvs_range_join``) still cuts its rows that
-way."""
+way.
+
+The model keeps its assertions; `test_the_model_is_the_compiled_rule` compares it with the compiled ``rq_chunk_size`` /
+``rq_chunk_len`` (lotus_amd/csrc/lvs_plan.h through tests/native/plan_check.cpp) on every parameter used here."""
 import pytest
+
+import plan_native
 
 GROUPQ, MAXQ, CHUNK_MAX = 256, 4096, 65536
 
@@ -64,3 +69,11 @@ def test_the_literal_plans():
     assert plan(25_000, 65536) == [16384, 8192, 424]
     # a maximum that is not a launchable size is rounded down to one
     assert plan(100_000, 40_000) == plan(100_000, 32768)
+
+
+def test_the_model_is_the_compiled_rule():
+    wants = [4096, 8191, 8192, 32768, 40_000, 65535, 65536, 100_000, 1 << 20]
+    assert plan_native.ask([f"chunk_size {w}" for w in wants]) == [[chunk_size(w)] for w in wants]
+    cases = [(nq, m) for m in (32768, 65536) for nq in (4097, 9000, 20_000, 33_000, 40_000, 50_000, 65_536, 100_000, 1_000_000)]
+    cases += [(25_000, 65536), (100_000, 40_000), (1, 65536), (4096, 65536), (8192, 4096)]
+    assert plan_native.ask([f"chunks {nq} {m}" for nq, m in cases]) == [plan(nq, m) for nq, m in cases]

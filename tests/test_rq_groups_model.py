@@ -1,11 +1,17 @@
-"""CPU model of the launch arithmetic of the grouped ``lvs_rq_kernel`` (lotus_amd/csrc/lvs_rq.hip: ``rq_max_ranges``,
-``lvs_rq_fits``, ``lvs_rq_launch`` and the kernel's blockIdx -> (corpus range, query group) map), for the calls the literal
-``sem_search`` loop and small joins make with 257 .. 4 096 queries (lotus/sem_ops/sem_search.py:120-138,
-sem_sim_join.py:132-134).  The GPU parity rows of ``test_seeded_list_kernel`` run the code itself; this pins the rules the
-comments state: one workgroup per (range, group), the siblings of a range on ONE XCD, never more workgroups than CUs."""
+"""CPU model of the launch arithmetic of the grouped ``lvs_rq_kernel`` (``lvs_rq_ranges_for``, ``lvs_rq_fits`` and
+``lvs_grouped_geometry`` in lotus_amd/csrc/lvs_plan.h, as ``lvs_rq_launch`` uses them, and the kernel's blockIdx -> (corpus
+range, query group) map), for the calls the literal ``sem_search`` loop and small joins make with 257 .. 4 096 queries
+(lotus/sem_ops/sem_search.py:120-138, sem_sim_join.py:132-134).  The GPU parity rows of ``test_seeded_list_kernel`` run the
+code itself; this pins the rules the comments state: one workgroup per (range, group), the siblings of a range on ONE XCD,
+never more workgroups than CUs.
+
+`test_the_models_are_the_compiled_rules` compares every model below with the compiled
+code (tests/native/plan_check.cpp) on the parameters the tests use."""
 import itertools
 
 import pytest
+
+import plan_native
 
 GROUPQ, MAXQ, CUS, XCDS = 256, 4096, 256, 8
 
@@ -79,7 +85,7 @@ def test_every_range_and_group_has_exactly_one_workgroup_and_siblings_share_an_x
     assert (groups - 1) * GROUPQ < nq <= groups * GROUPQ
 
 
-# ---- round 6: chunked calls (lvs_rq_item / lvs_rq_ranges_for / lvs_rq_grid in lvs_tile.h; the chunk policy of lvs_capi.hip) -----
+# ---- round 6: chunked calls (lvs_rq_item / lvs_rq_ranges_for / lvs_rq_grid and the chunk policy in lvs_plan.h) -----
 def ranges_for(groups):
     return 256 if groups <= 1 else (8 * (32 // groups) if groups <= 32 else 256 // groups)
 
@@ -139,3 +145,26 @@ def test_chunk_policy_covers_the_queries_with_launchable_group_counts(nq):
         assert groups <= 32 or groups % 32 == 0  # what lvs_rq_launch / lvs_rj_launch accept
     assert cs == sorted(cs, reverse=True)
     assert chunks(100_000) == [32768, 32768, 32768, 1696]
+
+
+LAUNCHES = [(300, 70_001), (512, 66_000), (700, 100_000), (1300, 200_000), (2560, 1_000_000), (4000, 530_000), (4096, 1_000_000),
+            (3500, 500_000), (3840, 600_001), (257, 32768 * 2), (200, 40_000), (128, 33_000)]
+
+
+def test_the_models_are_the_compiled_rules():
+    ask = plan_native.ask
+    shapes = [(g * GROUPQ, 32768 * 16) for g in range(1, 17)] + LAUNCHES
+    shapes += [(96, 10 ** 6), (97, 10 ** 6), (4096, 10 ** 6), (4097, 10 ** 6), (512, 60_000), (512, 65_536)]
+    assert ask([f"rq_fits {nq} {nb} 768 10" for nq, nb in shapes]) == [[int(fits(nq, nb))] for nq, nb in shapes]
+    # lvs_rq_launch: the corpus in rounded-up 32-row blocks
+    assert ask([f"grouped {nq} {-(-nb // 32)}" for nq, nb in LAUNCHES]) == [list(launch(nq, nb)) for nq, nb in LAUNCHES]
+    groups = list(range(1, 33)) + [64, 128, 256]
+    assert ask([f"ranges_for {g}" for g in groups]) == [[ranges_for(g)] for g in groups]
+    assert all(ranges_for(g) == max_ranges(g) for g in range(1, 33))
+    for g in (1, 2, 7, 16, 32, 64, 128, 256):
+        grid = ranges_for(g) if g == 1 else (CUS if g > 32 else 8 * g * -(-ranges_for(g) // 8))
+        got = ask([f"item {b} {g} {ranges_for(g)}" for b in range(grid)])
+        assert got == [None if item(b, g, ranges_for(g)) is None else list(item(b, g, ranges_for(g))) for b in range(grid)]
+    # chunks() at its default records the threshold join's cut (range_chunk_len)
+    nqs = [1, 4096, 4097, 5000, 9000, 10_000, 20_000, 33_000, 40_000, 65_536, 100_000, 1_000_000]
+    assert ask([f"range_chunks {nq}" for nq in nqs]) == [chunks(nq) for nq in nqs]
