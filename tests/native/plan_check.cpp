@@ -2,7 +2,8 @@
 //   plan_check           walks the grid below and fails on the first violated invariant of geometry, layout, route and chunks
 //   plan_check --dump    one line per grid shape with every field of layout, geometry, two-phase plan, route, chunk list and
 //                        workspace offsets (tests/test_plan_pins.py pins some; the whole dump is what a refactor diffs)
-//   plan_check --query   answers questions read from stdin, one per line, for the Python models of tests/test_rq_*.py
+//   plan_check --query   answers questions read from stdin, one per line, for the Python models of tests/test_rq_*.py and
+//                        the route table of tests/test_widths_host.py
 // Built with a plain host compiler by tests/plan_native.py (run from tests/test_capi.py).
 #include "../../lotus_amd/csrc/lvs_plan.h"
 
@@ -180,10 +181,10 @@ static bool plan_shape(int64_t nq, int64_t nb, int d, int k, int bp, int qp, boo
 
 static int query_mode() {
     char cmd[32];
-    long long a[4];
+    long long a[6];
     char line[256];
     while (fgets(line, sizeof(line), stdin)) {
-        const int n = sscanf(line, "%31s %lld %lld %lld %lld", cmd, &a[0], &a[1], &a[2], &a[3]);
+        const int n = sscanf(line, "%31s %lld %lld %lld %lld %lld %lld", cmd, &a[0], &a[1], &a[2], &a[3], &a[4], &a[5]);
         if (n < 2) continue;
         const std::string c = cmd;
         if (c == "rq_fits" && n == 5) {
@@ -207,6 +208,16 @@ static int query_mode() {
                 left -= cn;
             }
             printf("\n");
+        } else if (c == "route" && n == 7) {  // nq nb d k xb_pack xq_pack -> kind nbfrag kcap nqb groups sample_rows jper nseg
+            LvsFlatPlan p;
+            TwoPhasePlan tp;
+            if (lvs_flat_plan(a[0], a[1], (int)a[2], (int)a[4], (int)a[5], false, (int)a[3], p) != LVS_OK) {
+                printf("none\n");
+                continue;
+            }
+            const LvsRoute r = lvs_flat_route(a[0], a[1], p.l, (int)a[3], p.w.npass, 0, make_two_phase_plan(a[0], a[1], (int)a[3], tp));
+            printf("%d %d %d %d %d %lld %d %d\n", r.kind, r.stream.nbfrag, r.stream.kcap, r.stream.nqb, r.stream.groups,
+                   (long long)(r.kind == LVS_ROUTE_STREAM ? lvs_stream_sample_rows(a[0], a[1]) : 0), p.l.dpad / 16, p.l.nseg);
         } else {
             printf("?\n");
         }

@@ -27,6 +27,8 @@ _OPERANDS = {}
 def _operands(be, d, mode):
     """Packed unit Gaussian rows and queries of one (d, pack mode), made once, with their stored values in float64."""
     if (d, mode) not in _OPERANDS:
+        while len(_OPERANDS) >= 6:  # (the wide ones hold 77 MB of float64 each)
+            _OPERANDS.pop(next(iter(_OPERANDS)))
         xb, xq = synth.corpus(NB, d, seed=d), synth.corpus(NQ, d, seed=d + 1)
         if mode == F16:
             xb, xq = xb.astype(np.float16), xq.astype(np.float16)
@@ -77,7 +79,10 @@ def _check(xb_s, xq_s, rows, k, metric, D, I, bar=BAR, tie_gap=TIE_GAP, what="")
 
 
 # ---- the kernel alone ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("d", [64, 100, 192, 768, 1536])  # fewer lanes than a wave, a padded width, a pass and a half, passes
+# fewer lanes than a wave, a padded width, a pass and a half, passes; then the instantiations with 4 passes of 512 halfs, with 5 (on
+# the six-pass kernel), with 6 (hi|lo queries: its own launch bounds) and the one that reads the query again per group of rows (dpad
+# > 3 072).  The reference's near-tie share at the four wide ones, computed on the CPU, is at most 4.4 % (cap 15 %).
+@pytest.mark.parametrize("d", [64, 100, 192, 768, 1536, 2048, 2500, 3072, 3200])
 @pytest.mark.parametrize("metric", [IP, L2])
 @pytest.mark.parametrize("mode", [F16, SPLIT])
 def test_planted_candidates_come_back_in_exact_order(hip_backend, mode, metric, d):
@@ -90,6 +95,24 @@ def test_planted_candidates_come_back_in_exact_order(hip_backend, mode, metric, 
         for k in sorted({1, kc // 2 + 1, kc}):
             D, I, _ = _refine(be, pb, pq, keys, k, metric)
             _check(xb_s, xq_s, rows, k, metric, D, I, what=f"mode={mode} metric={metric} d={d} kc={kc}")
+
+
+@pytest.mark.parametrize("d", [192, 3072])
+@pytest.mark.parametrize("metric", [IP, L2])
+@pytest.mark.parametrize("qmode,bmode", [(F16, SPLIT), (SPLIT, F16)])
+def test_mixed_operands_come_back_in_exact_order(hip_backend, qmode, bmode, metric, d):
+    """fp16 queries against hi|lo rows and hi|lo queries against fp16 rows: the kernel's instantiations with different query and
+    row pack modes, at one pass and a half and at six."""
+    be = hip_backend
+    pb, _, xb_s, _ = _operands(be, d, bmode)
+    _, pq, _, xq_s = _operands(be, d, qmode)
+    rng = np.random.default_rng(1000 * d + 100 * qmode + 10 * bmode + metric)
+    for kc in (7, 64):
+        rows = _draw(rng, NQ, kc, NB)
+        keys = _keys_of(rng, rows)
+        for k in sorted({1, kc // 2 + 1, kc}):
+            D, I, _ = _refine(be, pb, pq, keys, k, metric)
+            _check(xb_s, xq_s, rows, k, metric, D, I, what=f"queries mode={qmode} rows mode={bmode} metric={metric} d={d} kc={kc}")
 
 
 @pytest.mark.parametrize("metric", [IP, L2])

@@ -234,7 +234,7 @@ def test_pack_rows_values_and_norms(hip_backend):
     assert np.abs(nrm - 1).max() < 2e-3
 
 
-@pytest.mark.parametrize("d", [96, 200, 768, 1000])
+@pytest.mark.parametrize("d", [96, 200, 768, 1000, 3072, 4100])  # (4 100: the element-wise kernel, wide)
 @pytest.mark.parametrize("src_dtype", [np.float32, np.float16])
 def test_pack_rows_vector_path_equals_scalar_semantics(hip_backend, d, src_dtype):
     """d % 8 == 0 takes the 16-byte-per-lane kernel: same stored values as the element-wise definition, also for a
