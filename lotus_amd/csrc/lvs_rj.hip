@@ -14,8 +14,10 @@
 // So, unlike lvs_rq_kernel:
 //   * the fragment pipeline runs ACROSS the unit barriers (a barrier certifies the unit after the one about to be computed);
 //   * a block's first MFMAs take the constant 0 as C (no accumulator clears);
-//   * the staging cursor is advanced incrementally in scalar registers, and the kernel only sees WHOLE 32-row blocks - no
-//     clamping arithmetic per load; the caller searches the corpus' last nb % 32 rows with lvs_rq_kernel (same arithmetic);
+//   * the staging cursor lives in scalar registers and is advanced without a branch or a vector instruction: it leads the unit
+//     being computed by RING - 1 units, so which k-half it is on is known when the code is generated, and "stop at the range's
+//     end" is a compare + select of the byte step (see `issue_piece`); the kernel only sees WHOLE 32-row blocks - no clamping
+//     arithmetic per load; the caller searches the corpus' last nb % 32 rows with lvs_rq_kernel (same arithmetic);
 //   * candidates are not inserted where they are found: a lane whose score reaches its query's threshold APPENDS the key to a
 //     per-wave buffer in LDS (one ballot + one write), and the buffer is drained - sorted insertions, thresholds, publication -
 //     once it holds enough of them.  A wave-wide slow path per candidate (~1 500 cycles with nobody to hide it) becomes ~100
@@ -238,48 +240,68 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
 #pragma unroll
     for (int i = 0; i < LPW; ++i) soff[i] = src_off(wave * LPW + i, lane);
     soff[LPW] = src_off(UK, lane);
-    // the staging cursor (wave-uniform: scalar registers): the unit issued next
+    // the staging cursor (wave-uniform, scalar registers only): the unit issued next.  It leads the unit being computed by
+    // exactly RING - 1 units, so its k-half `ikh` is a compile-time constant at every call site ((kh + RING - 1) % U in `unit`,
+    // n % U in the prologue): which of the two byte steps the source takes - UK * 32 to the same rows' next k-half, is_step_blk to
+    // the next block's first - is decided when the code is generated, and whether it is taken at all (not past the range's end) is
+    // one scalar compare + select.  No branch, no vector instruction; the LDS side keeps a byte address that wraps by compare +
+    // select.  What stays a branch: the quarter-used last piece (one wave in turn) and the once-per-block side-word DMA.
     const char* is_src = xb + b0 * 32 * ldb2;
-    int is_n = 0, is_kh = 0, is_blk = 0, is_slot = 0;
-    auto issue_piece = [&](auto pc) {
+    const long long is_step_blk = 32 * ldb2 - (long long)(U - 1) * UK * 32;
+    const unsigned is_dst0 = (unsigned)(unsigned long long)ring + (unsigned)(wave * (LPW * 1024));  // this wave's share of slot 0
+    const unsigned is_dst_end = is_dst0 + (unsigned)(RING * G::UB);
+    const unsigned is_dst_last = (unsigned)((UK - wave * LPW) * 1024);  // from this wave's share to the slot's last (quarter-used) KiB
+    unsigned is_dst = is_dst0;
+    int is_n = 0;
+    [[maybe_unused]] const float* is_bn = L2 ? a.bn + b0 * 32 : nullptr;  // |y|^2 of the issued unit's block (squared L2)
+    [[maybe_unused]] unsigned is_side = 0;  // float offset of that block's side words: (block % NB_RING) * 128
+    auto issue_piece = [&](auto pc, auto ikhc) {
         constexpr int i = decltype(pc)::value;
-        const unsigned dst = (unsigned)(unsigned long long)ring + (unsigned)(is_slot * G::UB);
+        constexpr int ikh = decltype(ikhc)::value;  // the k-half of unit is_n (is_n % U)
         if constexpr (i < LPW) {
-            rj_glds16(is_src, soff[i], dst + (unsigned)((wave * LPW + i) * 1024));
+            rj_glds16(is_src, soff[i], is_dst + (unsigned)(i * 1024));
         } else {
-            if ((is_n & 3) == wave) rj_glds16(is_src, soff[LPW], dst + (unsigned)(UK * 1024));
-            if (!RANGE && (!SOLO || L2) && is_kh == 0 && is_n < total_units) {
+            if ((is_n & 3) == wave) rj_glds16(is_src, soff[LPW], is_dst + is_dst_last);
+            constexpr bool side_unit = !RANGE && (!SOLO || L2) && ikh == 0;  // a block's first unit, in a form that has side words
+            if (side_unit && is_n < total_units) {
                 // the block's side words, one 4-byte DMA per query block: lanes 0 .. 31 -> |y|^2 of its rows (any valid word under
                 // inner product), lanes 32 .. 63 -> the shared thresholds of this wave's queries as the other workgroups left them
-                const long long row0 = (b0 + is_blk) * 32;
                 // (inner product: ONE 4-byte DMA - words 0 .. 31 the thresholds of query block 0, words 32 .. 63 those of query
                 // block 1; squared L2: two - |y|^2 | thresholds 0, then thresholds 1 in the upper half of the second)
                 if constexpr (SOLO) {  // (squared L2 only: the rows' |y|^2, in both halves of the one word row the epilogue reads)
-                    rj_glds4(a.bn + row0 + (lane & 31), side + ((is_blk % NB_RING) * 2) * 64);
+                    rj_glds4(is_bn + (lane & 31), side + is_side);
                 } else if constexpr (L2) {
 #pragma unroll
                     for (int qb = 0; qb < 2; ++qb) {
                         const int q = qidx_of(qb) < a.nq ? qidx_of(qb) : 0;
-                        const void* p = lane < 32 ? (const void*)(a.bn + row0 + (lane & 31)) : (const void*)(a.gtau + q);
-                        rj_glds4(p, side + ((is_blk % NB_RING) * 2 + qb) * 64);
+                        const void* p = lane < 32 ? (const void*)(is_bn + (lane & 31)) : (const void*)(a.gtau + q);
+                        rj_glds4(p, side + is_side + qb * 64);
                     }
                 } else {
                     const int qi = qidx_of(lane >> 5);
-                    rj_glds4(a.gtau + (qi < a.nq ? qi : 0), side + ((is_blk % NB_RING) * 2) * 64);
+                    rj_glds4(a.gtau + (qi < a.nq ? qi : 0), side + is_side);
                 }
             }
-            // advance the cursor; past the range's end the last unit is loaded again (into a free slot, never read)
+            // advance the cursor; past the range's end the last unit is loaded again (into a free slot, never read): once `more`
+            // is false it stays false, so the compile-time phase moves nothing from then on
+            const bool more = is_n + 1 < total_units;
+            if constexpr (ikh == U - 1) {
+                is_src += more ? is_step_blk : 0ll;
+                if constexpr (!RANGE && (!SOLO || L2)) {
+                    if constexpr (L2) is_bn += more ? 32 : 0;
+                    const unsigned nside = is_side + 128 == (unsigned)(NB_RING * 128) ? 0u : is_side + 128;
+                    is_side = more ? nside : is_side;
+                }
+            } else {
+                is_src += more ? (long long)(UK * 32) : 0ll;
+            }
             ++is_n;
-            if (is_n < total_units) {
-                if (++is_kh == U) {
-                    is_kh = 0;
-                    ++is_blk;
-                    is_src += 32 * ldb2 - (long long)(U - 1) * UK * 32;
-                } else {
-                    is_src += UK * 32;
-                }
-            }
-            is_slot = is_slot + 1 == RING ? 0 : is_slot + 1;
+            is_dst = is_dst + (unsigned)G::UB == is_dst_end ? is_dst0 : is_dst + (unsigned)G::UB;
+            // (the new cursor is due HERE, in the shadow of this step's MFMAs: left alone, the compiler sinks the advance of a
+            // block's last unit behind the epilogue, where nothing hides it)
+            asm volatile("" : "+s"(is_src), "+s"(is_dst), "+s"(is_n));
+            if constexpr (!RANGE && (!SOLO || L2) && ikh == U - 1) asm volatile("" : "+s"(is_side));
+            if constexpr (L2 && ikh == U - 1) asm volatile("" : "+s"(is_bn));
         }
     };
     // ---- fragment reads: lane (r = l & 31, h = l >> 5) reads bytes [(2 jj + h) * 16, + 16) of padded row r: lane base + jj * 32
@@ -522,7 +544,7 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
                     asm volatile("ds_read2_b32 %0, %1 offset0:0 offset1:32" : "=v"(*(unsigned long long*)gsh) : "v"(side_lds + (unsigned)((blk % NB_RING) * 512)) : "memory");
             }
             constexpr int piece = rj_piece_at(jj, UK, LPW);
-            if constexpr (piece >= 0 && !(DBG & 1)) issue_piece(std::integral_constant<int, piece>{});
+            if constexpr (piece >= 0 && !(DBG & 1)) issue_piece(std::integral_constant<int, piece>{}, std::integral_constant<int, (kh + RING - 1) % U>{});
             __builtin_amdgcn_sched_barrier(0);
             constexpr int extra = (F && jj >= JS && jj < JS + AD - 1) ? 1 : 0;
             if constexpr (F && jj == JS + AD - 1) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(*(unsigned long long*)gsh) : "n"(AD - 1) : "memory");
@@ -542,7 +564,9 @@ __global__ __launch_bounds__(256, 1) void lvs_rj_kernel(const LvsRqArgs a) {
     };
 
     // ---- prologue: RING - 1 units in flight, unit 0 certified by a barrier of its own, its first fragments read
-    for (int n = 0; n < RING - 1; ++n) static_for<LPW + 1>([&](auto pc) { issue_piece(pc); });
+    static_for<RING - 1>([&](auto nc) {
+        static_for<LPW + 1>([&](auto pc) { issue_piece(pc, std::integral_constant<int, decltype(nc)::value % U>{}); });
+    });
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RING - 2) * LPW) : "memory");
     __builtin_amdgcn_s_barrier();
     static_for<AD - 1>([&](auto jc) {
