@@ -12,6 +12,13 @@
  *     the library allocates nothing, keeps no pointer after a call returns and never synchronises: work is only
  *     enqueued on `stream` (a hipStream_t passed as void*, NULL = default stream).  The stream's device is made
  *     current for the duration of a call, so one process may drive several GPUs.
+ *   - scratch: an entry point with a `workspace` argument checks `workspace_bytes` against its `lvs_*_workspace_bytes(...)`
+ *     for the same shape and returns LVS_ENOMEM, before anything is launched or written, if it is given less.  The
+ *     declared size suffices: a call touches nothing outside the `workspace_bytes` it is given, and reads nothing of what
+ *     the buffer held before the call.  The workspace base must be aligned to 256 bytes (any hipMalloc'd pointer is): every
+ *     layout places its regions at multiples of 256 bytes from the base and reads them back as 64-bit keys, 64-bit atomics
+ *     and 16-byte vectors; a base that is not is refused with LVS_EINVAL.  Output buffers need only the alignment of their
+ *     element type.
  *   - the library reads no environment variable.  (A separate tuning build, `make -C lotus_amd/csrc tuning`, compiles
  *     the LVS_* tuning/ablation knobs in; lvs_build_flags() tells the two apart.)
  *   - "rows" matrices are the library's device layout produced by lvs_pack_rows(): fp16, row-major, leading

@@ -174,7 +174,7 @@ class _Loop:
         fracs = [1.0 / int(parts)] * int(parts) if isinstance(parts, int) else [float(f) for f in parts]
         if hasattr(be, "kmeans_accumulate_keys_into") and dev.type == "cuda" and len(fracs) > 1 and min(fracs) * train.n >= 65536:
             self.side = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
-            self.side_ws = torch.empty(int(be.lib.lvs_kmeans_accumulate_workspace_bytes(train.n, k)) + 256, dtype=torch.uint8, device=dev)
+            self.side_ws = torch.empty(int(be.lib.lvs_kmeans_accumulate_workspace_bytes(train.n, k)), dtype=torch.uint8, device=dev)
             self.cuts = range_cuts(train.n, fracs)
             self.pipelined = PIPELINE_CERTIFICATES and hasattr(be, "nearest_begin")
             return self.ranges, True

@@ -482,6 +482,7 @@ extern "C" int32_t lvs_nearest3(const void* xb, int32_t xb_pack, int64_t nb, con
         lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)p.total, (long long)workspace_bytes);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

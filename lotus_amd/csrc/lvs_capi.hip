@@ -1258,10 +1258,15 @@ static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, con
     }
     LVS_REQUIRE(xb && xq, "NULL rows");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && xq_norms_sq), "L2 needs both norm vectors");
-    if (workspace_bytes < p.w.total || !workspace) {
-        lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)p.w.total, (long long)workspace_bytes);
+    // the declared size: the larger of the call's own layout and its two-phase plan's (lvs_flat_search_workspace_bytes).  A call
+    // short of it is refused even where the selection passes' layout would fit: it must not quietly run ceil(k / 56) passes
+    TwoPhasePlan tp;
+    const int64_t need = make_two_phase_plan(nq, nb, k, tp) && tp.total > p.w.total ? tp.total : p.w.total;
+    if (workspace_bytes < need || !workspace) {
+        lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)workspace_bytes);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     char* ws = (char*)workspace;
     const SearchCall sc = {xb, xq, xb_norms_sq, xq_norms_sq, nb, nq, id_offset, d, metric, k, xb_pack, xq_pack, row_ids,
                            (u64*)out_keys, st, o, p, ws, workspace_bytes, (uint32_t*)(ws + p.w.off_gtau)};
@@ -1369,6 +1374,7 @@ extern "C" int32_t lvs_nearest_hi(const void* xb, int32_t xb_pack, int64_t nb, c
         lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)need, (long long)workspace_bytes);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace + 256;
@@ -1723,14 +1729,21 @@ struct IvfLayout {
     int64_t off_coarse, off_extra, off_sort, off_tiles, off_items, off_parts, flat_bytes, sort_bytes, max_items, total;
 };
 
-// scratch of a chunk of `c` queries: [flat search scratch | coarse keys [c][nprobe] | the mode's own region, extra_per_q
-// bytes per query (PQ: tables [c][M][256] fp32) | tiled modes (Flat, SQ8): bucket sort | tile offsets | work items
-// | parts [<= nprobe][c][k]]
-bool ivf_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
+// scratch of a call in chunks of `c` queries and a shorter last chunk of `tail` (0: none): [flat search scratch | coarse keys
+// [c][nprobe] | the mode's own region, extra_per_q bytes per query (PQ: tables [c][M][256] fp32) | tiled modes (Flat, SQ8):
+// bucket sort | tile offsets | work items | parts [<= nprobe][c][k]].  The flat search's declared size is not monotone in its
+// query count (fewer queries can take a path with more lists per query, or gain a two-phase plan), so the coarse step's region
+// holds the larger of the two chunk lengths' sizes; every other region grows with the chunk.
+bool ivf_layout(int64_t c, int64_t tail, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
                 int64_t extra_per_q, bool tiled, IvfLayout& L) {
     L.chunk = c;
     L.flat_bytes = lvs_flat_search_workspace_bytes(c, nlist, d, nprobe, c_pack, xq_pack);
     if (L.flat_bytes < 0) return false;
+    if (tail > 0) {
+        const int64_t tail_bytes = lvs_flat_search_workspace_bytes(tail, nlist, d, nprobe, c_pack, xq_pack);
+        if (tail_bytes < 0) return false;
+        if (tail_bytes > L.flat_bytes) L.flat_bytes = tail_bytes;
+    }
     const int64_t npairs = c * nprobe;
     int64_t off = lvs_round_up(L.flat_bytes, 256);
     L.off_coarse = off;
@@ -1755,13 +1768,14 @@ bool ivf_layout(int64_t c, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, 
     return true;
 }
 
-// the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits
+// the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits.  The
+// chunks a call runs have two lengths at most: c, and nq % c for the last one
 bool ivf_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
               int64_t extra_per_q, bool tiled, IvfLayout& L) {
     int64_t c = nq < IVF_CHUNK_MAX ? nq : IVF_CHUNK_MAX;
     if (c < 1) c = 1;
     for (;;) {
-        if (!ivf_layout(c, nlist, nprobe, d, k, c_pack, xq_pack, extra_per_q, tiled, L)) return false;
+        if (!ivf_layout(c, nq % c, nlist, nprobe, d, k, c_pack, xq_pack, extra_per_q, tiled, L)) return false;
         if (L.total <= IVF_WS_BUDGET || c == 1) return c * nprobe < 0xFFFFFFFFll;
         c = (c + 1) / 2;
     }
@@ -1834,6 +1848,7 @@ int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, S
         lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(s.workspace);
     LVS_DEVICE_GUARD(s.stream);
     hipStream_t st = (hipStream_t)s.stream;
     char* w = (char*)s.workspace;

@@ -177,6 +177,12 @@ void lvs_set_error(const char* fmt, ...);
         }                           \
     } while (0)
 
+// Every workspace layout places its regions at multiples of 256 bytes from the base and reads them back as 64-bit keys, 64-bit
+// atomics and 16-byte vectors: the base itself must sit on a multiple of 256 (include/lotus_hip.h; any hipMalloc'd pointer does).
+#define LVS_WS_ALIGN 256
+#define LVS_REQUIRE_WS_ALIGNED(ws) \
+    LVS_REQUIRE(((uintptr_t)(ws) & (LVS_WS_ALIGN - 1)) == 0, "the workspace must be aligned to %d bytes", LVS_WS_ALIGN)
+
 // Entry points launch on `stream`; make that stream's device current for the duration of the call (the caller may
 // drive several GPUs from one process) and restore the previous one afterwards.
 struct LvsDeviceGuard {

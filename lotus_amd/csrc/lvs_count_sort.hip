@@ -271,6 +271,7 @@ int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_
         lvs_set_error("workspace too small: need %lld bytes", (long long)p.total);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(ws);
     LVS_DEVICE_GUARD(stream);  // after the checks: a caller that holds no guard yet (k-means) reports these errors first
     if (keys) return bucket_rows<u64>((const u64*)keys, n, k, id_offset, p, (char*)ws, stream, rows_out, offs_out);
     return bucket_rows<long long>((const long long*)assign, n, k, id_offset, p, (char*)ws, stream, rows_out, offs_out);

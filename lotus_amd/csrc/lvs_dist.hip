@@ -115,6 +115,7 @@ extern "C" int32_t lvs_search_sharded(lvs_all_gather_fn all_gather, void* all_ga
         lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)p.total, (long long)workspace_bytes);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     // Everything that can fail on ONE rank only is checked before the first exchange: a rank that returned early would leave
     // its peers waiting inside the all-gather.  (An error from the all-gather itself, or from a launch, still leaves the
     // communicator in an undefined collective state - include/lotus_hip.h.)

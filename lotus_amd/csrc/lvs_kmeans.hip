@@ -577,7 +577,12 @@ extern "C" int32_t lvs_kmeans_objective(const float* centroids, const float* sum
                                         int64_t workspace_bytes, void* stream) {
     LVS_REQUIRE(k > 0 && d > 0, "bad shape k=%d d=%d", k, d);
     LVS_REQUIRE(centroids && sums && counts && out_obj && workspace, "NULL buffer");
-    LVS_REQUIRE(workspace_bytes >= lvs_kmeans_objective_workspace_bytes(k), "workspace too small");
+    if (workspace_bytes < lvs_kmeans_objective_workspace_bytes(k)) {  // LVS_ENOMEM as in every other entry, not LVS_REQUIRE's LVS_EINVAL
+        lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)lvs_kmeans_objective_workspace_bytes(k),
+                      (long long)workspace_bytes);
+        return LVS_ENOMEM;
+    }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)workspace;

@@ -109,6 +109,7 @@ extern "C" int32_t lvs_kmeans_iteration(lvs_all_reduce_fn all_reduce, void* all_
         lvs_set_error("workspace too small: need %lld bytes, got %lld", (long long)p.total, (long long)workspace_bytes);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -149,8 +150,11 @@ extern "C" int32_t lvs_kmeans_iteration(lvs_all_reduce_fn all_reduce, void* all_
                                    keys2 + r0, stream);
             if (rc != LVS_OK) return rc;
         }
-        for (int64_t o0 = 0; o0 < n_open; o0 += p.cap_open) {  // three or more centroids inside the bound: the exact search
-            const int64_t mo = n_open - o0 < p.cap_open ? n_open - o0 : p.cap_open;
+        for (int64_t o0 = 0, mo; o0 < n_open; o0 += mo) {  // three or more centroids inside the bound: the exact search
+            // in batches of cap_open rows.  The flat search's declared size is not monotone in its query count (at 24 576
+            // centroids 108 534 queries need more than 131 072 do): a batch the region was not sized for is halved until it fits
+            mo = n_open - o0 < p.cap_open ? n_open - o0 : p.cap_open;
+            while (mo > 1 && lvs_flat_search_workspace_bytes(mo, k, d, 1, c_pack, x_pack) > p.search_bytes) mo = (mo + 1) / 2;
             void* sub = ws + p.off_sub;
             float* subn = (float*)(ws + p.off_subn);
             uint64_t* subk = (uint64_t*)(ws + p.off_subk);

@@ -156,6 +156,7 @@ extern "C" int32_t lvs_sort_rows_desc(const float* scores, int64_t nq, int64_t n
         lvs_set_error("workspace too small: need %lld bytes", (long long)p.total);
         return LVS_ENOMEM;
     }
+    LVS_REQUIRE_WS_ALIGNED(workspace);
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)workspace;

@@ -3,7 +3,7 @@
 //   plan_check --dump    one line per grid shape with every field of layout, geometry, two-phase plan, route, chunk list and
 //                        workspace offsets (tests/test_plan_pins.py pins some; the whole dump is what a refactor diffs)
 //   plan_check --query   answers questions read from stdin, one per line, for the Python models of tests/test_rq_*.py and
-//                        the route table of tests/test_widths_host.py
+//                        the route tables of tests/test_widths_host.py and tests/extent_cases.py
 // Built with a plain host compiler by tests/plan_native.py (run from tests/test_capi.py).
 #include "../../lotus_amd/csrc/lvs_plan.h"
 
@@ -218,6 +218,15 @@ static int query_mode() {
             const LvsRoute r = lvs_flat_route(a[0], a[1], p.l, (int)a[3], p.w.npass, 0, make_two_phase_plan(a[0], a[1], (int)a[3], tp));
             printf("%d %d %d %d %d %lld %d %d\n", r.kind, r.stream.nbfrag, r.stream.kcap, r.stream.nqb, r.stream.groups,
                    (long long)(r.kind == LVS_ROUTE_STREAM ? lvs_stream_sample_rows(a[0], a[1]) : 0), p.l.dpad / 16, p.l.nseg);
+        } else if (c == "chunk_kernel" && n == 5) {  // cn nb dpad k -> LVS_CHUNK_* of a chunk of cn queries (no row ids)
+            printf("%d\n", lvs_rq_chunk_kernel(a[0], a[1], (int)a[2], (int)a[3], false));
+        } else if (c == "tile_geom" && n == 4) {  // nq nb k -> the list kernel's geometry for a top-k pass: v2 (1: 256 x 256) nslab
+            const LvsTileGeom g = lvs_tile_geometry(lvs_tile_request_topk(a[0], a[1], (int)a[2]));
+            printf("%d %d\n", g.v2, g.nslab);
+        } else if (c == "two_phase" && n == 4) {  // nq nb k -> ran (0 / 1), selection passes, the plan's bytes (0: no plan)
+            TwoPhasePlan tp;
+            const bool ok = make_two_phase_plan(a[0], a[1], (int)a[2], tp);
+            printf("%d %d %lld\n", (int)ok, lvs_workspace(a[0], a[1], (int)a[2], 1).npass, (long long)(ok ? tp.total : 0));
         } else {
             printf("?\n");
         }
