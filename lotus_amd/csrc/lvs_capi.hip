@@ -1626,63 +1626,44 @@ extern "C" int32_t lvs_range_join(const void* xb, int32_t xb_pack, int64_t nb, c
         LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_RANGE, a, st));
         return LVS_OK;
     };
-    // (r6) fp16 rows, inner product, one rank's tiles: the register-resident-queries kernel in RANGE mode (lvs_rj.hip) - chunks of
-    // <= 32 768 queries (LVS_RANGE_CHUNK, its own constant), each against the rows that can still pair with it (a self-join skips
-    // the rows below the chunk's first query: j > i), whole 32-row blocks; the corpus' last nb % 32 rows and chunks left with a short corpus go through the list
-    // kernel.  Same pairs (keys are scores of the same MFMA sequence), one shared counter.
-    const bool rj_range = lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_tune("LVS_RJ_RANGE", 1) != 0 && xb_pack == LVS_PACK_F16 &&
-                          xq_pack == LVS_PACK_F16 && metric == LVS_METRIC_IP && qt_stride == 1 && nq >= 2048 &&
-                          lvs_rq_shape_ok(p.l.dpad, 1);
-    if (!rj_range) return tile_launch(0, nq, 0, nb, qt_stride, qt_phase, false);
+    // one launch of lvs_rj_kernel in RANGE mode over the same rectangle (whole 32-row blocks)
+    auto rj_launch = [&](int64_t c0, int64_t cn, int64_t r0, int64_t rn, bool continuation) -> int32_t {
+        LvsRqArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.xb = (const char*)xb + r0 * p.l.ldb * 2;
+        ra.xq = (const _Float16*)xq + c0 * p.l.ldq;
+        ra.nb = rn;
+        ra.ldb = p.l.ldb;
+        ra.ldq = p.l.ldq;
+        ra.id_offset = id_offset + r0;
+        ra.nq = (int)cn;
+        ra.k = 1;
+        ra.metric = metric;
+        ra.pair_q = (long long*)out_q;
+        ra.pair_j = (long long*)out_j;
+        ra.pair_s = out_s;
+        ra.pair_count = (unsigned long long*)out_count;
+        ra.pair_capacity = capacity;
+        ra.q_row0 = q_row0 >= 0 ? q_row0 + c0 : -1;
+        ra.q_base = c0;
+        ra.threshold = thr;
+        ra.out_scale = out_scale;
+        ScopedKernelTimer timer(st, LVS_KERNEL_RJ, continuation);
+        LVS_HIP_CHECK(lvs_rj_range_launch(ra, p.l.dpad, st));
+        return LVS_OK;
+    };
+    // the plan (lvs_plan.h): one launch of the list kernel, or chunks of queries, each against the rows that can still pair with
+    // it.  Same pairs whichever kernel finds them (keys are scores of the same MFMA sequence), one shared counter.
+    if (!lvs_range_rj_ok(nq, p.l.dpad, xb_pack, xq_pack, metric, qt_stride)) return tile_launch(0, nq, 0, nb, qt_stride, qt_phase, false);
     bool first = true;
     for (int64_t c0 = 0, cn = 0; c0 < nq; c0 += cn) {
         cn = range_chunk_len(nq - c0);
-        // rows that can pair with this chunk's queries: all of them, or (self-join) those above the chunk's first query row
-        int64_t r0 = 0;
-        if (q_row0 >= 0) {
-            r0 = (q_row0 + c0 - id_offset) / 32 * 32;
-            if (r0 < 0) r0 = 0;
-            if (r0 > nb) r0 = nb;
-        }
-        const int64_t r_full = nb / 32 * 32;  // the register-resident kernel sees whole blocks
-        const int64_t rn = r_full - r0;
-        const int64_t groups = (cn + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
-        const bool take = rn >= LVS_RQ_JOIN_MINROWS && cn > 128 && (groups <= 32 || groups % 32 == 0);
-        if (take) {
-            LvsRqArgs ra;
-            memset(&ra, 0, sizeof(ra));
-            ra.xb = (const char*)xb + r0 * p.l.ldb * 2;
-            ra.xq = (const _Float16*)xq + c0 * p.l.ldq;
-            ra.nb = rn;
-            ra.ldb = p.l.ldb;
-            ra.ldq = p.l.ldq;
-            ra.id_offset = id_offset + r0;
-            ra.nq = (int)cn;
-            ra.k = 1;
-            ra.metric = metric;
-            ra.pair_q = (long long*)out_q;
-            ra.pair_j = (long long*)out_j;
-            ra.pair_s = out_s;
-            ra.pair_count = (unsigned long long*)out_count;
-            ra.pair_capacity = capacity;
-            ra.q_row0 = q_row0 >= 0 ? q_row0 + c0 : -1;
-            ra.q_base = c0;
-            ra.threshold = thr;
-            ra.out_scale = out_scale;
-            {
-                ScopedKernelTimer timer(st, LVS_KERNEL_RJ, !first);
-                LVS_HIP_CHECK(lvs_rj_range_launch(ra, p.l.dpad, st));
-            }
-            first = false;
-            if (r_full < nb) {  // the corpus' last nb % 32 rows
-                const int32_t rc = tile_launch(c0, cn, r_full, nb - r_full, 1, 0, true);
-                if (rc != LVS_OK) return rc;
-            }
-        } else if (nb - r0 > 0) {
-            const int32_t rc = tile_launch(c0, cn, r0, nb - r0, 1, 0, !first);
-            if (rc != LVS_OK) return rc;
-            first = false;
-        }
+        const LvsRangeChunk c = lvs_range_chunk_plan(c0, cn, nb, q_row0, id_offset);
+        if (c.rn <= 0) continue;
+        int32_t rc = c.kernel == LVS_RANGE_RJ ? rj_launch(c0, cn, c.r0, c.rn, !first) : tile_launch(c0, cn, c.r0, c.rn, 1, 0, !first);
+        if (rc != LVS_OK) return rc;
+        first = false;
+        if (c.tn > 0 && (rc = tile_launch(c0, cn, c.t0, c.tn, 1, 0, true)) != LVS_OK) return rc;  // the corpus' last nb % 32 rows
     }
     return LVS_OK;
 }
@@ -1707,92 +1688,6 @@ struct TimingPause {
         g_timing.on = was;
     }
 };
-
-// does the list scan's LDS image (the tile's query fragments + its lists) fit a workgroup for queries of dimension d packed
-// with xq_pack?  hi|lo queries: d <= 1088 (k <= 16: 1216); fp16 queries: d <= 2240 (2432).  Larger shapes are not served
-bool ivf_fits(int32_t d, int32_t k, int32_t xq_pack) {
-    LvsLayout l;
-    return lvs_layout(d, xq_pack, xq_pack, false, l) == LVS_OK && lvs_ivf_lds_bytes(l.nbfrag, lvs_ivf_kcap(k)) <= 160 * 1024;
-}
-// does the SQ8 scan's LDS image (the tile's w fragments, hi|lo whatever the query's pack mode, + its lists) fit?
-bool ivf_sq8_fits(int32_t d, int32_t k) {
-    return lvs_ivf_sq8_lds_bytes(lvs_ivf_sq8_ldc(d), lvs_ivf_kcap(k)) <= 160 * 1024;
-}
-// does the PQ scan's LDS image (one query's fp32 table of M x 256 entries + its list) fit?  M <= 159, whatever d and k
-bool ivf_pq_fits(int32_t M, int32_t k) { return lvs_ivf_pq_lds_bytes(M, lvs_ivf_kcap(k)) <= 160 * 1024; }
-
-constexpr int64_t IVF_WS_BUDGET = 512ll << 20;  // scratch of one call; more queries go through in chunks
-constexpr int64_t IVF_CHUNK_MAX = 16384;
-
-struct IvfLayout {
-    int64_t chunk;  // queries per chunk
-    int64_t off_coarse, off_extra, off_sort, off_tiles, off_items, off_parts, flat_bytes, sort_bytes, max_items, total;
-};
-
-// scratch of a call in chunks of `c` queries and a shorter last chunk of `tail` (0: none): [flat search scratch | coarse keys
-// [c][nprobe] | the mode's own region, extra_per_q bytes per query (PQ: tables [c][M][256] fp32) | tiled modes (Flat, SQ8):
-// bucket sort | tile offsets | work items | parts [<= nprobe][c][k]].  The flat search's declared size is not monotone in its
-// query count (fewer queries can take a path with more lists per query, or gain a two-phase plan), so the coarse step's region
-// holds the larger of the two chunk lengths' sizes; every other region grows with the chunk.
-bool ivf_layout(int64_t c, int64_t tail, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
-                int64_t extra_per_q, bool tiled, IvfLayout& L) {
-    L.chunk = c;
-    L.flat_bytes = lvs_flat_search_workspace_bytes(c, nlist, d, nprobe, c_pack, xq_pack);
-    if (L.flat_bytes < 0) return false;
-    if (tail > 0) {
-        const int64_t tail_bytes = lvs_flat_search_workspace_bytes(tail, nlist, d, nprobe, c_pack, xq_pack);
-        if (tail_bytes < 0) return false;
-        if (tail_bytes > L.flat_bytes) L.flat_bytes = tail_bytes;
-    }
-    const int64_t npairs = c * nprobe;
-    int64_t off = lvs_round_up(L.flat_bytes, 256);
-    L.off_coarse = off;
-    off += lvs_round_up(npairs * 8, 256);
-    L.off_extra = off;
-    off += lvs_round_up(c * extra_per_q, 256);
-    L.off_sort = L.off_tiles = L.off_items = off;
-    L.sort_bytes = L.max_items = 0;
-    if (tiled) {
-        L.sort_bytes = lvs_bucket_workspace_bytes(npairs, nlist);
-        if (L.sort_bytes < 0) return false;
-        L.max_items = lvs_ivf_max_items(npairs, nlist);
-        off += lvs_round_up(L.sort_bytes, 256);
-        L.off_tiles = off;
-        off += lvs_round_up((int64_t)(nlist + 1) * 4, 256);
-        L.off_items = off;
-        off += lvs_round_up(L.max_items * 4, 256);
-    }
-    L.off_parts = off;
-    off += lvs_round_up(npairs * k * 8, 256);
-    L.total = off;
-    return true;
-}
-
-// the chunk size depends on the arguments only: the largest power-of-two fraction of min(nq, 16 384) whose scratch fits.  The
-// chunks a call runs have two lengths at most: c, and nq % c for the last one
-bool ivf_plan(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t c_pack, int32_t xq_pack,
-              int64_t extra_per_q, bool tiled, IvfLayout& L) {
-    int64_t c = nq < IVF_CHUNK_MAX ? nq : IVF_CHUNK_MAX;
-    if (c < 1) c = 1;
-    for (;;) {
-        if (!ivf_layout(c, nq % c, nlist, nprobe, d, k, c_pack, xq_pack, extra_per_q, tiled, L)) return false;
-        if (L.total <= IVF_WS_BUDGET || c == 1) return c * nprobe < 0xFFFFFFFFll;
-        c = (c + 1) / 2;
-    }
-}
-
-// what the three *_search_workspace_bytes share.  M: PQ's subspaces (1 otherwise); fits: the mode's LDS check
-int64_t ivf_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k, int32_t pack, bool fits,
-                            int64_t extra_per_q, bool tiled) {
-    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0 || k < 1 || k > LVS_KPASS)
-        return LVS_EINVAL;
-    if (M < 1 || d % M != 0) return LVS_EINVAL;
-    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    if (!fits) return LVS_EUNSUPPORTED;  // the caller searches such shapes exactly
-    IvfLayout L;
-    if (!ivf_plan(nq, nlist, nprobe, d, k, pack, pack, extra_per_q, tiled, L)) return LVS_EINVAL;
-    return L.total;
-}
 
 // the argument checks of the searches through the lists, in the order they are reported.  A mode without rows of its own passes
 // xb_pack = LVS_PACK_F16, a mode without a product quantizer M = ksub = 1: those checks then always hold
@@ -1839,11 +1734,23 @@ struct IvfSearch {
 // ScopedKernelTimer (q0 > 0: a continuation) and may lower nparts, the lists per query that it fills (nprobe on entry).
 // s.k = 0 (the threshold search): the scan appends to the caller's own buffers - no parts region and nothing to merge.
 // A row selector (s.sel_bits) concerns the scan alone: the coarse step, the pair grouping, the tiling and the merge see none.
+// mode: LVS_IVF_*, M: PQ's subspaces (1 otherwise) - the plan (lvs_ivf_plan.h) is the one *_workspace_bytes declared.
 template <class Scan>
-int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, Scan scan) {
-    IvfLayout L;
-    LVS_REQUIRE(ivf_plan(s.nq, s.nlist, s.nprobe, s.d, s.k, s.c_pack, s.xq_pack, extra_per_q, tiled, L),
-                "shape beyond the IVF search");
+int32_t ivf_search_chunks(const IvfSearch& s, int mode, int32_t M, Scan scan) {
+    LvsIvfPlan L;
+    const int planned = lvs_ivf_plan(mode, s.nq, s.nlist, s.nprobe, s.d, M, s.k, s.c_pack, s.xq_pack, L);
+    if (planned == LVS_EUNSUPPORTED) {
+        if (mode == LVS_IVF_FLAT)
+            lvs_set_error("d=%d with k=%d does not fit the list scan's LDS (see lvs_ivf_search_workspace_bytes)", s.d, s.k);
+        else if (mode == LVS_IVF_RANGE)
+            lvs_set_error("d=%d does not fit the threshold scan's LDS (see lvs_ivf_range_workspace_bytes)", s.d);
+        else if (mode == LVS_IVF_SQ8)
+            lvs_set_error("d=%d with k=%d does not fit the SQ8 list scan's LDS (see lvs_ivf_sq8_search_workspace_bytes)", s.d, s.k);
+        else
+            lvs_set_error("M=%d with k=%d does not fit the PQ list scan's LDS (see lvs_ivf_pq_search_workspace_bytes)", M, s.k);
+        return LVS_EUNSUPPORTED;
+    }
+    LVS_REQUIRE(planned == LVS_OK, "shape beyond the IVF search");
     if (s.workspace_bytes < L.total) {
         lvs_set_error("workspace too small: need %lld bytes", (long long)L.total);
         return LVS_ENOMEM;
@@ -1880,7 +1787,7 @@ int32_t ivf_search_chunks(const IvfSearch& s, int64_t extra_per_q, bool tiled, S
 // Flat and SQ8: invert a chunk's (query, probe) pairs - pair numbers q * nprobe + p grouped by list (the bucket sort of
 // lvs_count_sort.hip) -, cut every list's pairs into work items of 32 (the SQ8 scan halves them) and zero the parts (a pair
 // whose probe named no list - never with nprobe <= nlist - keeps empty slots; k = 0: there are none)
-int32_t ivf_group_pairs(const IvfLayout& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t nlist, int32_t k, u64* parts,
+int32_t ivf_group_pairs(const LvsIvfPlan& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t nlist, int32_t k, u64* parts,
                         hipStream_t st, const uint32_t** pairs, const uint32_t** pair_offs) {
     const int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, 0, w + L.off_sort, L.sort_bytes, st, pairs, pair_offs);
     if (rc != LVS_OK) return rc;
@@ -1912,7 +1819,7 @@ void ivf_gather_args(LvsIvfGatherArgs& g, const LvsLayout& p, const void* xb, co
     }
 }
 // ... and those that do: the chunk's queries and its work items (ivf_group_pairs)
-int32_t ivf_gather_chunk(LvsIvfGatherArgs& g, const IvfLayout& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t k,
+int32_t ivf_gather_chunk(LvsIvfGatherArgs& g, const LvsIvfPlan& L, char* w, const uint64_t* coarse, int64_t npairs, int32_t k,
                          u64* parts, hipStream_t st, const void* xq_c, const float* qn_c) {
     const int32_t rc = ivf_group_pairs(L, w, coarse, npairs, g.nlist, k, parts, st, &g.pairs, &g.pair_offs);
     if (rc != LVS_OK) return rc;
@@ -1935,18 +1842,6 @@ int32_t ivf_check_encode(int64_t n, int32_t d, int32_t nlist, int32_t M, int32_t
     dpad = l.dpad;
     ldb = l.ldb;
     return LVS_OK;
-}
-
-// probes per PQ scan workgroup: enough for ~2 048 rows of the average list (the table's staging and the first insertions
-// are paid once per workgroup), but no fewer than ~512 workgroups per chunk while the probes allow it; at most LVS_PQ_MAXRANGE
-int32_t pq_prange(int64_t nb, int32_t nlist, int64_t cn, int32_t nprobe) {
-    const int64_t avg = nb / nlist > 0 ? nb / nlist : 1;
-    int64_t pr = (2048 + avg - 1) / avg;
-    const int64_t by_blocks = cn * nprobe / 512;
-    if (pr > by_blocks) pr = by_blocks;
-    if (pr > LVS_PQ_MAXRANGE) pr = LVS_PQ_MAXRANGE;
-    if (pr > nprobe) pr = nprobe;
-    return pr < 1 ? 1 : (int32_t)pr;
 }
 }  // namespace
 
@@ -1984,7 +1879,7 @@ extern "C" int32_t lvs_ivf_build_lists(const int64_t* assign, int64_t n, int32_t
 
 // ---- IVF-Flat
 extern "C" int64_t lvs_ivf_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k, int32_t pack) {
-    return ivf_workspace_bytes(nq, nlist, nprobe, d, 1, k, pack, ivf_fits(d, k, pack), 0, true);
+    return lvs_ivf_plan_bytes(LVS_IVF_FLAT, nq, nlist, nprobe, d, 1, k, pack);
 }
 
 extern "C" int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq,
@@ -2000,10 +1895,6 @@ extern "C" int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int6
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
     LvsLayout p;
     LVS_REQUIRE(lvs_layout(d, xb_pack, xq_pack, false, p) == LVS_OK, "bad plan");
-    if (!ivf_fits(d, k, xq_pack)) {
-        lvs_set_error("d=%d with k=%d does not fit the list scan's LDS (see lvs_ivf_search_workspace_bytes)", d, k);
-        return LVS_EUNSUPPORTED;
-    }
     LvsIvfArgs a;
     memset(&a, 0, sizeof(a));
     ivf_gather_args(a.g, p, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
@@ -2011,8 +1902,8 @@ extern "C" int32_t lvs_ivf_search_keys_sel(const void* xb, int32_t xb_pack, int6
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
-    return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
-                                             const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
+    return ivf_search_chunks(s, LVS_IVF_FLAT, 1, [&](const LvsIvfPlan& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
+                                                     const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
         const int32_t rc = ivf_gather_chunk(a.g, L, w, coarse, cn * nprobe, k, parts, st, xq_c, qn_c);
         if (rc != LVS_OK) return rc;
@@ -2036,22 +1927,8 @@ extern "C" int32_t lvs_ivf_search_keys(const void* xb, int32_t xb_pack, int64_t 
 }
 
 // ---- threshold search through the lists (faiss IndexIVF::range_search): lvs_ivf_range_kernel over the full-precision rows
-namespace {
-// does lvs_ivf_range_kernel's LDS image (the tile's query fragments + the slot table, no lists) fit?  hi|lo queries: d <= 1216;
-// fp16 queries: d <= 2496
-bool ivf_range_fits(int32_t d, int32_t xq_pack) {
-    LvsLayout l;
-    return lvs_layout(d, xq_pack, xq_pack, false, l) == LVS_OK && lvs_ivf_range_lds_bytes(l.nbfrag) <= 160 * 1024;
-}
-}  // namespace
-
 extern "C" int64_t lvs_ivf_range_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t pack) {
-    if (nq < 0 || nlist < 1 || nprobe < 1 || nprobe > nlist || nprobe > LVS_MAX_K || d <= 0) return LVS_EINVAL;
-    if (pack != LVS_PACK_F16 && pack != LVS_PACK_SPLIT) return LVS_EINVAL;
-    if (!ivf_range_fits(d, pack)) return LVS_EUNSUPPORTED;  // the caller joins such shapes exactly
-    IvfLayout L;  // the tiled searches' scratch without parts (k = 0): the pairs go to the caller's buffers
-    if (!ivf_plan(nq, nlist, nprobe, d, 0, pack, pack, 0, true, L)) return LVS_EINVAL;
-    return L.total;
+    return lvs_ivf_plan_bytes(LVS_IVF_RANGE, nq, nlist, nprobe, d, 1, 0, pack);
 }
 
 // Where the top-k searches scan into parts that the driver merges, every chunk's launch appends to the call's one pair list.
@@ -2071,10 +1948,6 @@ extern "C" int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (xb_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
     LvsLayout p;
     LVS_REQUIRE(lvs_layout(d, xb_pack, xq_pack, false, p) == LVS_OK, "bad plan");
-    if (!ivf_range_fits(d, xq_pack)) {
-        lvs_set_error("d=%d does not fit the threshold scan's LDS (see lvs_ivf_range_workspace_bytes)", d);
-        return LVS_EUNSUPPORTED;
-    }
     LvsIvfRangeArgs a;
     memset(&a, 0, sizeof(a));
     ivf_gather_args(a.g, p, xb, xb_norms_sq, offsets, rows, sel_bits, nlist, nprobe, metric);
@@ -2087,8 +1960,8 @@ extern "C" int32_t lvs_ivf_range_search(const void* xb, int32_t xb_pack, int64_t
     a.out_scale = ldexpf(1.0f, -score_exp);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, 0, nullptr, nullptr, workspace, workspace_bytes, stream, sel_bits};
-    return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
-                                             const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
+    return ivf_search_chunks(s, LVS_IVF_RANGE, 1, [&](const LvsIvfPlan& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
+                                                      const float* qn_c, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
         const int32_t rc = ivf_gather_chunk(a.g, L, w, coarse, cn * nprobe, 0, parts, st, xq_c, qn_c);
         if (rc != LVS_OK) return rc;
@@ -2118,7 +1991,7 @@ extern "C" int32_t lvs_ivf_sq8_encode(const void* xb, int32_t xb_pack, int64_t n
 
 extern "C" int64_t lvs_ivf_sq8_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t k,
                                                       int32_t pack) {
-    return ivf_workspace_bytes(nq, nlist, nprobe, d, 1, k, pack, ivf_sq8_fits(d, k), 0, true);
+    return lvs_ivf_plan_bytes(LVS_IVF_SQ8, nq, nlist, nprobe, d, 1, k, pack);
 }
 
 extern "C" int32_t lvs_ivf_sq8_search_keys_sel(const uint8_t* codes, const float* residual_norms_sq, const float* vmin,
@@ -2134,10 +2007,6 @@ extern "C" int32_t lvs_ivf_sq8_search_keys_sel(const uint8_t* codes, const float
     LVS_REQUIRE(codes && vmin && vdiff && offsets && rows && centroids && centroids_f32 && xq && out_keys && workspace,
                 "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (residual_norms_sq && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
-    if (!ivf_sq8_fits(d, k)) {
-        lvs_set_error("d=%d with k=%d does not fit the SQ8 list scan's LDS (see lvs_ivf_sq8_search_workspace_bytes)", d, k);
-        return LVS_EUNSUPPORTED;
-    }
     LvsIvfSq8Args a;
     memset(&a, 0, sizeof(a));
     a.codes = codes;
@@ -2161,8 +2030,8 @@ extern "C" int32_t lvs_ivf_sq8_search_keys_sel(const uint8_t* codes, const float
     a.kcap = lvs_ivf_kcap(k);
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
-    return ivf_search_chunks(s, 0, true, [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
-                                             const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
+    return ivf_search_chunks(s, LVS_IVF_SQ8, 1, [&](const LvsIvfPlan& L, char* w, int64_t q0, int64_t cn, const void* xq_c,
+                                                    const float*, const uint64_t* coarse, u64* parts, int32_t&) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
         const int32_t rc = ivf_group_pairs(L, w, coarse, cn * nprobe, nlist, k, parts, st, &a.pairs, &a.pair_offs);
         if (rc != LVS_OK) return rc;
@@ -2208,7 +2077,7 @@ extern "C" int32_t lvs_ivf_pq_encode(const void* xb, int32_t xb_pack, int64_t n,
 
 extern "C" int64_t lvs_ivf_pq_search_workspace_bytes(int64_t nq, int32_t nlist, int32_t nprobe, int32_t d, int32_t M, int32_t k,
                                                      int32_t pack) {
-    return ivf_workspace_bytes(nq, nlist, nprobe, d, M, k, pack, ivf_pq_fits(M, k), (int64_t)M * LVS_PQ_KSUB * 4, false);
+    return lvs_ivf_plan_bytes(LVS_IVF_PQ, nq, nlist, nprobe, d, M, k, pack);
 }
 
 extern "C" int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float* beta, const float* codebooks, int32_t M,
@@ -2224,10 +2093,6 @@ extern "C" int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float*
     LVS_REQUIRE(codes && codebooks && offsets && rows && centroids && centroids_f32 && xq && out_keys && workspace,
                 "NULL buffer");
     LVS_REQUIRE(metric != LVS_METRIC_L2 || (beta && c_norms_sq && xq_norms_sq), "squared L2 needs the norms");
-    if (!ivf_pq_fits(M, k)) {
-        lvs_set_error("M=%d with k=%d does not fit the PQ list scan's LDS (see lvs_ivf_pq_search_workspace_bytes)", M, k);
-        return LVS_EUNSUPPORTED;
-    }
     LvsIvfPqArgs a;
     memset(&a, 0, sizeof(a));
     a.codes = codes;
@@ -2251,12 +2116,12 @@ extern "C" int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float*
     const IvfSearch s = {nlist, centroids, c_pack, c_norms_sq, xq, xq_pack, nq, xq_norms_sq, d,
                          metric, nprobe, k, out_keys, out_probe, workspace, workspace_bytes, stream, sel_bits};
     // the queries' tables, then the query-major scan: one part per range of probes
-    return ivf_search_chunks(s, (int64_t)M * LVS_PQ_KSUB * 4, false,
-                             [&](const IvfLayout& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
+    return ivf_search_chunks(s, LVS_IVF_PQ, M,
+                             [&](const LvsIvfPlan& L, char* w, int64_t q0, int64_t cn, const void* xq_c, const float*,
                                  const uint64_t* coarse, u64* parts, int32_t& nparts) -> int32_t {
         hipStream_t st = (hipStream_t)stream;
         float* lut = (float*)(w + L.off_extra);
-        a.prange = pq_prange(nb, nlist, cn, nprobe);
+        a.prange = lvs_ivf_pq_prange(nb, nlist, cn, nprobe);
         nparts = (nprobe + a.prange - 1) / a.prange;
         a.lut = lut;
         a.coarse = (const u64*)coarse;

@@ -75,9 +75,7 @@ __global__ __launch_bounds__(256) void lvs_scan3_kernel(uint32_t* __restrict__ v
 }
 
 // ---- bucket sort -----------------------------------------------------------------------------------------------
-constexpr int BUCKET_CHUNK = 8192;
-constexpr int BUCKET_MAX_BINS = 24576;  // (k + 1) * 4 B of LDS per workgroup; larger k sorts by two digits
-
+// (BucketPlan, BUCKET_CHUNK, BUCKET_MAX_BINS: lvs_ivf_plan.h)
 template <typename KeyT>
 __device__ inline uint32_t lvs_bucket_bin_of(KeyT v, long long id_offset, int k);
 template <>
@@ -172,48 +170,6 @@ int bucket_bits(int nbins) {
     while ((1 << b) < nbins) ++b;
     return b;
 }
-struct BucketPlan {
-    int nchunks, passes, nbins[2], shift[2];
-    uint32_t mask[2];
-    int64_t off_counts, off_seg, off_rows_a, off_rows_b, off_offs, total;
-};
-bool bucket_plan(int64_t n, int32_t k, BucketPlan& p) {
-    if (n < 0 || k <= 0 || n >= 0xFFFFFFFFll) return false;
-    p.nchunks = (int)lvs_ceil_div(n > 0 ? n : 1, BUCKET_CHUNK);
-    if (k + 1 <= BUCKET_MAX_BINS) {
-        p.passes = 1;
-        p.nbins[0] = k + 1;
-        p.shift[0] = 0;
-        p.mask[0] = 0xFFFFFFFFu;
-        p.nbins[1] = 0;
-        p.shift[1] = 0;
-        p.mask[1] = 0;
-    } else {  // two stable passes: low 12 bits, then the rest
-        p.passes = 2;
-        p.nbins[0] = 4096;
-        p.shift[0] = 0;
-        p.mask[0] = 4095u;
-        p.nbins[1] = (k >> 12) + 1;
-        p.shift[1] = 12;
-        p.mask[1] = 0xFFFFFFFFu;
-        if (p.nbins[1] > BUCKET_MAX_BINS) return false;  // k >= 2^26.5: not a k-means anyone runs
-    }
-    const int64_t maxbins = p.nbins[0] > p.nbins[1] ? p.nbins[0] : p.nbins[1];
-    int64_t off = 0;
-    p.off_counts = off;
-    off += lvs_round_up(maxbins * p.nchunks * 4, 256);
-    p.off_seg = off;
-    off += lvs_round_up(lvs_scan_scratch_bytes(maxbins * p.nchunks), 256);
-    p.off_rows_a = off;
-    off += lvs_round_up(n * 4, 256);
-    p.off_rows_b = off;
-    off += p.passes > 1 ? lvs_round_up(n * 4, 256) : 0;
-    p.off_offs = off;
-    off += lvs_round_up((int64_t)(k + 2) * 4, 256);
-    p.total = off;
-    return true;
-}
-
 template <typename KeyT>
 int32_t bucket_rows(const KeyT* assign, int64_t n, int32_t k, int64_t id_offset, const BucketPlan& p, char* w, hipStream_t st,
                     const uint32_t** rows_out, const uint32_t** offs_out) {
@@ -254,12 +210,6 @@ void lvs_scan_excl_launch(uint32_t* v, long long total, uint32_t* seg, hipStream
     hipLaunchKernelGGL(lvs_scan2_kernel, dim3(1), dim3(256), 0, stream, seg, nseg);
     hipLaunchKernelGGL(lvs_scan3_kernel, dim3((unsigned)lvs_ceil_div(total, 256)), dim3(256), 0, stream, v, total,
                        (const uint32_t*)seg, nchunks, offsets, nbuckets);
-}
-
-int64_t lvs_bucket_workspace_bytes(int64_t n, int32_t k) {
-    BucketPlan p;
-    if (!bucket_plan(n, k, p)) return LVS_EINVAL;
-    return p.total;
 }
 
 int32_t lvs_bucket_positions(const uint64_t* keys, const int64_t* assign, int64_t n, int32_t k, int64_t id_offset, void* ws,

@@ -141,12 +141,6 @@ hipError_t ivf_scan_launch_u(const LvsIvfArgs& a, int64_t max_items, hipStream_t
 
 }  // namespace
 
-size_t lvs_ivf_lds_bytes(int nbfrag, int kcap) {
-    return (size_t)nbfrag * 1024 + (size_t)LVS_IVF_TILEQ * kcap * 8 + (size_t)LVS_IVF_TILEQ * 4 * 3;
-}
-
-int lvs_ivf_kcap(int k) { return k <= 16 ? 16 : (k <= 32 ? 32 : 64); }
-
 hipError_t lvs_ivf_tiles_launch(const uint32_t* pair_offs, int nlist, uint32_t* tile_offs, uint32_t* item_list,
                                 hipStream_t stream) {
     hipLaunchKernelGGL(lvs_ivf_tiles_kernel, dim3(1), dim3(1024), 0, stream, pair_offs, nlist, tile_offs, item_list);

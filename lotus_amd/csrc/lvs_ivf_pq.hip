@@ -293,12 +293,6 @@ __global__ __launch_bounds__(256) void lvs_ivf_pq_encode_kernel(const _Float16* 
 
 }  // namespace
 
-size_t lvs_ivf_pq_lds_bytes(int M, int kcap) {
-    return (size_t)M * PQ_KS * 4 + (size_t)kcap * 8 + 16 + (size_t)LVS_PQ_MAXRANGE * 4 * 3 + 4;
-}
-
-int lvs_ivf_pq_ldc(int M) { return (int)lvs_round_up(M, 16); }
-
 hipError_t lvs_ivf_pq_encode_launch(const void* xb, int64_t ldb, int split, int xdpad, int64_t n, int d, int M, int ksub,
                                     const int64_t* offsets, int nlist, const uint32_t* rows, const float* cent,
                                     const float* codebooks, uint8_t* codes, float* beta, hipStream_t stream) {
@@ -321,7 +315,7 @@ hipError_t lvs_ivf_pq_lut_launch(const void* xq, int64_t ldq, int split, int qdp
 
 hipError_t lvs_ivf_pq_scan_launch(const LvsIvfPqArgs& a, hipStream_t stream) {
     if (a.M < 1 || a.ldc != lvs_ivf_pq_ldc(a.M) || a.k < 1 || a.k > a.kcap || a.kcap > 64 || a.prange < 1 ||
-        a.prange > LVS_PQ_MAXRANGE || a.nprobe < 1 || a.nq > 65535 || lvs_ivf_pq_lds_bytes(a.M, a.kcap) > 160 * 1024)
+        a.prange > LVS_PQ_MAXRANGE || a.nprobe < 1 || a.nq > 65535 || lvs_ivf_pq_lds_bytes(a.M, a.kcap) > LVS_LDS_MAX)
         return hipErrorInvalidValue;
     if (a.nq <= 0) return hipSuccess;
     const int nranges = (a.nprobe + a.prange - 1) / a.prange;

@@ -97,13 +97,10 @@ hipError_t ivf_range_launch_u(const LvsIvfRangeArgs& a, int64_t max_items, hipSt
 
 }  // namespace
 
-// the tile's query fragments (1 KB each) + the slot -> query table
-size_t lvs_ivf_range_lds_bytes(int nbfrag) { return (size_t)nbfrag * 1024 + (size_t)LVS_IVF_TILEQ * 4; }
-
 // jper = dpad / 16 is a multiple of 4 (dpad is a multiple of 64): batches of 8 fragments where they divide it, else 4
 hipError_t lvs_ivf_range_launch(const LvsIvfRangeArgs& a, int64_t max_items, hipStream_t stream) {
     if (a.g.jper % 4 != 0 || a.g.nseg < 1 || a.g.nseg > 3 || a.capacity < 0 || !a.out_count ||
-        lvs_ivf_range_lds_bytes(a.g.nbfrag) > 160 * 1024)
+        lvs_ivf_range_lds_bytes(a.g.nbfrag) > LVS_LDS_MAX)
         return hipErrorInvalidValue;
     if (max_items <= 0) return hipSuccess;
     if (a.g.sel) return a.g.jper % 8 == 0 ? ivf_range_launch_u<8, true>(a, max_items, stream) : ivf_range_launch_u<4, true>(a, max_items, stream);

@@ -326,12 +326,6 @@ hipError_t sq8_scan_launch_u(const LvsIvfSq8Args& a, int64_t max_items, hipStrea
 
 }  // namespace
 
-size_t lvs_ivf_sq8_lds_bytes(int ldc, int kcap) {
-    return (size_t)(ldc / 32) * 2 * 1024 + (size_t)SQ8_TQ * kcap * 8 + (size_t)SQ8_TQ * 4 * 5;
-}
-
-int lvs_ivf_sq8_ldc(int d) { return (int)lvs_round_up(d, 64); }
-
 hipError_t lvs_ivf_sq8_encode_launch(const void* xb, int64_t ldb, int split, int xdpad, int64_t n, int d,
                                      const int64_t* offsets, int nlist, const uint32_t* rows, const float* cent,
                                      const float* vmin, const float* vdiff, uint8_t* codes, float* rnorm, hipStream_t stream) {
@@ -345,7 +339,7 @@ hipError_t lvs_ivf_sq8_encode_launch(const void* xb, int64_t ldb, int split, int
 // batches of U 64-dimension blocks: 4 where they divide ldc / 64, else 2, else 1
 hipError_t lvs_ivf_sq8_scan_launch(const LvsIvfSq8Args& a, int64_t max_items, hipStream_t stream) {
     if (a.ldc % 64 != 0 || a.ldc < a.d || a.ldc > a.qdpad || a.k < 1 || a.k > a.kcap || a.kcap > 64 ||
-        lvs_ivf_sq8_lds_bytes(a.ldc, a.kcap) > 160 * 1024)
+        lvs_ivf_sq8_lds_bytes(a.ldc, a.kcap) > LVS_LDS_MAX)
         return hipErrorInvalidValue;
     if (max_items <= 0) return hipSuccess;
     const int nkb = a.ldc / 64;

@@ -1,7 +1,8 @@
 // The flat search's host planner: every decision a search makes before a kernel starts, as pure functions of integers - operand
 // layout, the tile kernel's slab and XCD-group geometry, sample sizes, the two-phase plan, the query chunks, the grouped and
-// streaming launch geometry, the route and the workspace layout.  No HIP header, no stream, no device pointer: a plain C++17
-// host compiler builds this file (tests/native/plan_check.cpp runs it).  lvs_common.h and lvs_tile.h include it.
+// streaming launch geometry, the route and the workspace layout - and the launches of the threshold join.  No HIP header, no
+// stream, no device pointer: a plain C++17 host compiler builds this file (tests/native/plan_check.cpp runs it).  lvs_common.h
+// and lvs_ivf_plan.h (the searches through inverted lists) include it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -49,6 +50,7 @@ static inline bool lvs_tune_set(const char* name) { return getenv(name) != nullp
 #define LVS3_BQ 128
 #define LVS_KPASS LVS3_KCAP // largest k any single pass selects; k up to LVS_MAX_K runs ceil(k / LVS_KPASS) passes
 constexpr int LVS_SELECT_MAX = 4096;  // most candidates per query select_keys_kernel sorts (32 KB of LDS)
+constexpr size_t LVS_LDS_MAX = 160 * 1024;  // LDS a workgroup may use: all of a CU's
 
 // small-batch streaming kernel (lvs_stream.hip): nq <= 256, k <= LVS_KPASS
 #define LVS_STREAM_MAXQ 256
@@ -517,6 +519,37 @@ inline int64_t lvs_rq_sample_rows(int64_t nb, int64_t cn) {
     return sample >= 4096 && lvs_tune("LVS_STREAM_SEED", 1) != 0 ? sample : 0;
 }
 
+// ---- the threshold join (lvs_range_join) ----------------------------------------------------------------------------------
+// (r6) fp16 rows, inner product, one rank's tiles, 2 048 queries or more: the register-resident-queries kernel in RANGE mode
+// (lvs_rj.hip) serves the call in chunks of range_chunk_len queries; every other call is one launch of the list kernel
+inline bool lvs_range_rj_ok(int64_t nq, int dpad, int32_t xb_pack, int32_t xq_pack, int32_t metric, int32_t qt_stride) {
+    return lvs_tune("LVS_RJ", LVS_RJ_DEFAULT) != 0 && lvs_tune("LVS_RJ_RANGE", 1) != 0 && xb_pack == LVS_PACK_F16 &&
+           xq_pack == LVS_PACK_F16 && metric == LVS_METRIC_IP && qt_stride == 1 && nq >= 2048 && lvs_rq_shape_ok(dpad, 1);
+}
+// The launches of the chunk of queries [c0, c0 + cn) over nb rows: `kernel` over rows [r0, r0 + rn) (rn = 0: none), then the
+// list kernel over [t0, t0 + tn) (tn = 0: none).  The rows start where they can still pair with the chunk - everywhere, or
+// (self-join, q_row0 >= 0: query i is row q_row0 + i of a corpus whose first row is id_offset, only j > i is kept) at the
+// 32-row block of the chunk's first query.  lvs_rj_kernel sees whole 32-row blocks, at least LVS_RQ_JOIN_MINROWS of them,
+// and leaves the corpus' last nb % 32 rows to the list kernel; chunks left with a shorter corpus go to the list kernel whole.
+enum { LVS_RANGE_LIST = 0, LVS_RANGE_RJ = 1 };
+struct LvsRangeChunk {
+    int kernel;
+    int64_t r0, rn, t0, tn;
+};
+inline LvsRangeChunk lvs_range_chunk_plan(int64_t c0, int64_t cn, int64_t nb, int64_t q_row0, int64_t id_offset) {
+    int64_t r0 = 0;
+    if (q_row0 >= 0) {
+        r0 = (q_row0 + c0 - id_offset) / 32 * 32;
+        if (r0 < 0) r0 = 0;
+        if (r0 > nb) r0 = nb;
+    }
+    const int64_t r_full = nb / 32 * 32;
+    const int64_t groups = (cn + LVS_RQ_GROUPQ - 1) / LVS_RQ_GROUPQ;
+    if (r_full - r0 >= LVS_RQ_JOIN_MINROWS && cn > 128 && (groups <= 32 || groups % 32 == 0))
+        return {LVS_RANGE_RJ, r0, r_full - r0, r_full, nb - r_full};
+    return {LVS_RANGE_LIST, r0, nb - r0, nb, 0};
+}
+
 // ---- the small-batch streaming kernel (lvs_stream.hip) -------------------------------------------------------------------
 // corpus ranges of a launch: one per CU when every workgroup has its own range, 256 / G with G sibling groups
 inline int lvs_stream_ranges(int64_t nb, int groups) {
@@ -561,7 +594,7 @@ inline int lvs_stream_plan(int64_t nq, int k, int nbfrag, int* out_kcap, int* ou
         if (nqb > 3) continue;
         // one block keeps the full 64 slots (any k <= 56 costs the same insertion step); more blocks trade slots for queries
         const int kcap = nqb == 1 ? 64 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
-        if (lvs_stream_lds_bytes(nbfrag, nqb, kcap) > 160 * 1024) continue;  // a workgroup may use the whole 160 KiB
+        if (lvs_stream_lds_bytes(nbfrag, nqb, kcap) > LVS_LDS_MAX) continue;  // a workgroup may use the whole 160 KiB
         if (out_kcap) *out_kcap = kcap;
         if (out_nqb) *out_nqb = nqb;
         if (out_groups) *out_groups = groups;

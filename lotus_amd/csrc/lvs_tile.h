@@ -1,6 +1,7 @@
 // Launch interface of the tiled distance / top-k kernel (lvs_tile.hip) and the small-batch kernel (lvs_stream.hip).
 #pragma once
 #include "lvs_common.h"
+#include "lvs_ivf_plan.h"  // the IVF scans' shapes (LVS_IVF_TILEQ, ...), LDS sizes and fits
 
 #define LVS_MODE_TOPK 0
 #define LVS_MODE_SCORES 1
@@ -137,7 +138,6 @@ hipError_t lvs_rj_range_launch(LvsRqArgs& a, int dpad, hipStream_t stream);  // 
 
 // ---- lvs_ivf.hip: the list scan of an IVF-Flat search.  A work item is one inverted list and a tile of up to 32 of the
 // (query, probe rank) pairs that probe it; the list's rows are gathered by number from the flat image. ----
-#define LVS_IVF_TILEQ 32     // pairs per work item (MFMA N)
 #define LVS_IVF_WAVES 4
 // what every scan over gathered rows reads (lvs_ivf_gather.h): the image, the lists, a chunk's queries and its work items
 struct LvsIvfGatherArgs {
@@ -162,10 +162,6 @@ struct LvsIvfArgs {
     u64* out;                    // [nprobe][nq][k]
     int nq, k, kcap;
 };
-size_t lvs_ivf_lds_bytes(int nbfrag, int kcap);
-int lvs_ivf_kcap(int k);
-// work items of a launch can never exceed this bound (sum over lists of ceil(pairs / 32))
-static inline int64_t lvs_ivf_max_items(int64_t npairs, int32_t nlist) { return npairs / LVS_IVF_TILEQ + nlist + 1; }
 hipError_t lvs_ivf_tiles_launch(const uint32_t* pair_offs, int nlist, uint32_t* tile_offs, uint32_t* item_list,
                                 hipStream_t stream);
 hipError_t lvs_ivf_scan_launch(const LvsIvfArgs& a, int64_t max_items, hipStream_t stream);
@@ -184,12 +180,10 @@ struct LvsIvfRangeArgs {
     long long capacity, q_base;
     float threshold, out_scale;  // a hit: score > threshold in the kernel's (scaled) fp32 domain
 };
-size_t lvs_ivf_range_lds_bytes(int nbfrag);
 hipError_t lvs_ivf_range_launch(const LvsIvfRangeArgs& a, int64_t max_items, hipStream_t stream);
 
 // ---- lvs_ivf_sq8.hip: the 8-bit residual codec of IVF-SQ8 and its list scan.  A work item is one list and up to 16 of the
 // (query, probe rank) pairs that probe it (half of a work item of lvs_ivf_tiles_launch); the codes are in list order. ----
-#define LVS_SQ8_TILEQ 16  // pairs per work item (MFMA N of v_mfma_f32_16x16x32_f16)
 #define LVS_SQ8_WAVES 4
 struct LvsIvfSq8Args {
     const uint8_t* codes;        // [n][ldc] codes in list order (position p of `rows`)
@@ -209,8 +203,6 @@ struct LvsIvfSq8Args {
     int nq, nlist, nprobe, k, metric, d, ldc, qsplit, qdpad, kcap;
     const uint32_t* sel;         // [ceil(nb / 32)] row selector over ROW numbers (not positions); NULL: every row
 };
-size_t lvs_ivf_sq8_lds_bytes(int ldc, int kcap);
-int lvs_ivf_sq8_ldc(int d);  // code bytes per row: d rounded up to a multiple of 64
 hipError_t lvs_ivf_sq8_encode_launch(const void* xb, int64_t ldb, int split, int xdpad, int64_t n, int d,
                                      const int64_t* offsets, int nlist, const uint32_t* rows, const float* cent,
                                      const float* vmin, const float* vdiff, uint8_t* codes, float* rnorm, hipStream_t stream);
@@ -219,9 +211,7 @@ hipError_t lvs_ivf_sq8_scan_launch(const LvsIvfSq8Args& a, int64_t max_items, hi
 
 // ---- lvs_ivf_pq.hip: the product-quantizer codec of IVF-PQ (8-bit codes) and its query-major list scan.  A workgroup is one
 // query and a range of up to LVS_PQ_MAXRANGE of its probes; the codes are in list order. ----
-#define LVS_PQ_KSUB 256      // lookup-table entries per subspace (8-bit codes; codebooks may hold fewer)
 #define LVS_PQ_WAVES 8
-#define LVS_PQ_MAXRANGE 16   // probes per workgroup of the scan
 struct LvsIvfPqArgs {
     const uint8_t* codes;        // [n][ldc] codes in list order (position p of `rows`)
     const float* beta;           // [n] |rhat|^2 + 2 <c_l, rhat> per position (L2 only)
@@ -236,8 +226,6 @@ struct LvsIvfPqArgs {
     int nq, nlist, nprobe, prange, k, metric, d, M, ldc, qsplit, qdpad, kcap;
     const uint32_t* sel;         // [ceil(nb / 32)] row selector over ROW numbers (not positions); NULL: every row
 };
-size_t lvs_ivf_pq_lds_bytes(int M, int kcap);
-int lvs_ivf_pq_ldc(int M);  // code bytes per row: M rounded up to a multiple of 16
 hipError_t lvs_ivf_pq_encode_launch(const void* xb, int64_t ldb, int split, int xdpad, int64_t n, int d, int M, int ksub,
                                     const int64_t* offsets, int nlist, const uint32_t* rows, const float* cent,
                                     const float* codebooks, uint8_t* codes, float* beta, hipStream_t stream);

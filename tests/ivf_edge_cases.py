@@ -20,6 +20,7 @@ from typing import Callable, Optional
 import numpy as np
 
 import oracle
+import plan_native
 import synth
 from ivf_oracle_backend import ivf_reference
 from ivf_pq_oracle_backend import pq_decode, pq_reference
@@ -32,7 +33,8 @@ FLAT, SQ8, PQ = "Flat", "SQ8", "PQ"
 SCAN_KERNEL = {FLAT: "lvs_ivf_scan_kernel", SQ8: "lvs_ivf_sq8_scan_kernel", PQ: "lvs_ivf_pq_scan_kernel"}
 NEAR_TIE_CAP = 0.15
 FLT_MAX = float(np.float32(3.4028234663852886e38))
-WS_BUDGET = 512 << 20  # scratch of one search call: beyond it the library halves its chunk of queries
+# scratch of one search call (beyond it the library halves its chunk of queries) and the largest chunk: lvs_ivf_plan.h's own
+WS_BUDGET, CHUNK_MAX = plan_native.ivf_limits()
 
 
 @dataclass
@@ -267,17 +269,21 @@ def check_result(case, mode, res):
         case.post(case, mode, res)
 
 
-def chunk_boundary_sample(nq, seed):
-    """The queries checked of a search that runs in chunks: 300 random ones, plus every multiple of every chunk size the
-    library's planner can arrive at - c, ceil(c / 2), ceil(c / 4), ... for c = min(nq, 16 384) - with its two neighbours.
-    Sizes below 128 are left out: their multiples would be every query, and the planner never gets there - any chunk of up
-    to 255 queries fits the budget at these shapes (test_budget_cases_halve_the_chunk)."""
+def chunk_boundary_sample(nq, seed, chunks=()):
+    """The queries checked of a search that runs in chunks: 300 random ones, plus every multiple of the chunk the planner
+    reports for each mode the case runs in (``chunks``: ``plan_native.ivf_chunk`` answers) with its two neighbours.  Each
+    reported chunk is one of c, ceil(c / 2), ceil(c / 4), ... for c = min(nq, CHUNK_MAX) and at least 128 - any chunk of up to
+    255 queries fits the budget at these shapes (test_budget_cases_halve_the_chunk) -, and the multiples of the other sizes
+    of that sequence down to 128 stay in the sample: it does not shrink when a layout change moves the chunk."""
     pick = set(np.random.default_rng(seed).choice(nq, min(nq, 300), replace=False).tolist()) | {0, nq - 1}
-    c = min(nq, 16384)
-    while c >= 128:
+    halvings = [min(nq, CHUNK_MAX)]
+    while halvings[-1] > 1:
+        halvings.append((halvings[-1] + 1) // 2)
+    for chunk, tail, _ in chunks:
+        assert chunk in halvings and chunk >= 128 and tail == nq % chunk, (chunk, tail, halvings)
+    for c in sorted({c for c in halvings if c >= 128} | {ch[0] for ch in chunks}):
         for b in range(c, nq + 1, c):
             pick |= {b - 1, b, b + 1}
-        c = (c + 1) // 2
     return np.array(sorted(p for p in pick if 0 <= p < nq))
 
 
@@ -454,7 +460,10 @@ def wide(nlist, nprobe, k, nq, metric, pack, sample=False):
     xb = synth.corpus(n, d, seed=401)
     xq = synth.queries(xb, nq, seed=402 + nq)[0]
     c = _sampled_centroids(xb, nlist, 403 + nlist)
-    pick = chunk_boundary_sample(nq, 404) if sample else None
+    pick = None
+    if sample:  # the case runs in all three modes (Flat and SQ8 share one layout; PQ has its tables and no tiling)
+        chunks = [plan_native.ivf_chunk(m, nq, nlist, nprobe, d, k, pack, M=Case.M if m == PQ else 1) for m in (FLAT, SQ8, PQ)]
+        pick = chunk_boundary_sample(nq, 404, chunks)
 
     def pre(case, mode, res):
         if sample:  # the scratch of all queries at once is beyond the budget: the planner halves the chunk
@@ -473,8 +482,9 @@ def wide_pq_tables(metric, pack):
     def pre(case, mode, res):
         assert nq * 159 * 256 * 4 > WS_BUDGET
 
-    return Case(xb, xq, _sampled_centroids(xb, nlist, 413), metric, pack, 56, 4, M=159, pick=chunk_boundary_sample(nq, 414),
-                host_queries=40, pre=pre)
+    chunk = plan_native.ivf_chunk(PQ, nq, nlist, 4, d, 56, pack, M=159)
+    return Case(xb, xq, _sampled_centroids(xb, nlist, 413), metric, pack, 56, 4, M=159,
+                pick=chunk_boundary_sample(nq, 414, [chunk]), host_queries=40, pre=pre)
 
 
 # 5. k sweep over one fixed index per mode (lvs_ivf_kcap switches at 16 and 32)

@@ -1,5 +1,5 @@
-"""tests/native/plan_check.cpp - the flat search's host planner (lotus_amd/csrc/lvs_plan.h) as a program - built once per
-session with the host C++ compiler (no HIP, no GPU)."""
+"""tests/native/plan_check.cpp - the host planners (lotus_amd/csrc/lvs_plan.h: flat search and threshold join; lvs_ivf_plan.h: the
+searches through the lists) as a program - built once per session with the host C++ compiler (no HIP, no GPU)."""
 import atexit
 import functools
 import os
@@ -32,3 +32,19 @@ def ask(questions):
     answers = [None if ln.strip() == "none" else [int(v) for v in ln.split()] for ln in out.stdout.splitlines()]
     assert len(answers) == len(questions)
     return answers
+
+
+IVF_MODE = {"Flat": 0, "SQ8": 1, "PQ": 2, "range": 3}  # LVS_IVF_* of lvs_ivf_plan.h
+
+
+@functools.lru_cache(maxsize=None)
+def ivf_limits():
+    """(IVF_WS_BUDGET, IVF_CHUNK_MAX): the scratch budget of one search through the lists and its largest chunk of queries.  The
+    tests' one source of the two constants."""
+    return tuple(ask(["ivf_limits"])[0])
+
+
+def ivf_chunk(mode, nq, nlist, nprobe, d, k, pack, M=1):
+    """(chunk, last chunk or 0, declared bytes) of a search through the lists (mode: a key of IVF_MODE); None: refused."""
+    ans = ask([f"ivf_chunk {IVF_MODE[mode]} {nq} {nlist} {nprobe} {d} {M} {k} {pack}"])[0]
+    return None if ans is None else tuple(ans)

@@ -261,9 +261,17 @@ def test_planner_invariants_hold_over_the_grid():
 
     out = plan_native.run()
     assert out.returncode == 0 and out.stdout.startswith("ok 147840 shapes"), out.stdout[-1000:]
+    # ... and the second grid: the searches through the lists, the bucket sort and the threshold join's launches
+    assert out.stdout.splitlines()[1].startswith("ok 22732 ivf and bucket shapes (3878 with a halved chunk), 3456 joins"), out.stdout[-1000:]
     # the library answers with the same function
     lib = _capi.load()
-    have = {ln.split("|")[0]: int(ln.rsplit(" ", 1)[1]) for ln in plan_native.run("--dump").stdout.splitlines()}
+    have = {ln.split("|")[0]: int(ln.rsplit(" ", 1)[1]) for ln in plan_native.run("--dump").stdout.splitlines() if "| bytes " in ln}
+    for mode, fn in enumerate((lib.lvs_ivf_search_workspace_bytes, lib.lvs_ivf_sq8_search_workspace_bytes)):
+        for (nq, nlist, nprobe, d, k, pack) in [(40000, 8200, 2048, 64, 56, 0), (16385, 4097, 257, 64, 17, 1), (255, 1, 16, 64, 1, 0)]:
+            assert fn(nq, nlist, nprobe, d, k, pack) == have[f"ivf mode={mode} nq={nq} nlist={nlist} nprobe={nprobe} d={d} M=1 k={k} pack={pack} "]
+    assert lib.lvs_ivf_pq_search_workspace_bytes(10001, 40, 4, 636, 159, 56, 1) == have["ivf mode=2 nq=10001 nlist=40 nprobe=4 d=636 M=159 k=56 pack=1 "]
+    assert lib.lvs_ivf_range_workspace_bytes(32769, 30000, 2048, 1216, 1) == have["ivf mode=3 nq=32769 nlist=30000 nprobe=2048 d=1216 M=1 k=0 pack=1 "]
+    assert lib.lvs_kmeans_accumulate_workspace_bytes(1000000, 24576) == have["bucket n=1000000 k=24576 "]
     for (nq, nb, d, k, bp, qp) in [(100_000, 1_000_000, 768, 10, 0, 0), (100_000, 1_000_000, 768, 2048, 0, 0), (256, 1_000_000, 1536, 10, 1, 1),
                                    (1, 10_000_000, 8, 2048, 0, 0), (0, 0, 8, 1, 0, 0), (65236, 10_000_000, 768, 10, 0, 1)]:
         assert lib.lvs_flat_search_workspace_bytes(nq, nb, d, k, bp, qp) == have[f"nq={nq} nb={nb} d={d} k={k} pack={bp}/{qp} hi=0 "]

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle
+import plan_native
 import synth
 from ivf_edge_cases import rescoring_args
 from ivf_oracle_backend import ivf_reference
@@ -148,7 +149,7 @@ def test_queries_beyond_one_chunk(hip_backend):
     """40 000 queries at M = 64 run as several chunks inside lvs_ivf_pq_search_keys (the tables bound a chunk)."""
     be = hip_backend
     nb, d, M, nq, k, nlist, nprobe = 20000, 128, 64, 40000, 10, 64, 4
-    assert be.lib.lvs_ivf_pq_search_workspace_bytes(nq, nlist, nprobe, d, M, k, SPLIT) <= 512 << 20
+    assert be.lib.lvs_ivf_pq_search_workspace_bytes(nq, nlist, nprobe, d, M, k, SPLIT) <= plan_native.ivf_limits()[0]
     for mode, metric in ((F16, IP), (SPLIT, L2)):
         xb, xb_s, xq, xq_s = _data(nb, nq, d, mode, seed=41 + mode)
         c = _centroids(xb_s, nlist, metric, seed=42)

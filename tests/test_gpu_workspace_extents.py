@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import oracle
+import plan_native
 import synth
 from extent_cases import F16, FLAT, FLAT_BY_NAME, IP, L2, SPLIT, planner_says
 from ivf_oracle_backend import ivf_reference
@@ -521,7 +522,8 @@ def test_ivf_pq_search(hip_backend, nb, d, nq, k, cmode, qmode, metric, nlist, n
     _check_ivf(*_sel_reference(pq_reference, xhat, xq_s, k, metric, off, rows, probe, mask), D, I)
 
 
-IVF_CHUNK = 16384  # IVF_CHUNK_MAX (lvs_capi.hip): a call with more queries runs in chunks of a power-of-two fraction of it
+IVF_BUDGET, IVF_CHUNK = plan_native.ivf_limits()  # IVF_WS_BUDGET, IVF_CHUNK_MAX (lvs_ivf_plan.h): a call with more queries runs in
+# chunks of that many, halved until the scratch of one chunk fits the budget
 
 
 def _r256(n):
@@ -561,9 +563,12 @@ def test_ivf_pq_search_in_query_chunks_bounded_by_the_tables(hip_backend):
     separate one candidate from the next.  The reference on a sample of queries around every chunk edge."""
     be = hip_backend
     nb, d, nq, k, nlist, nprobe, M, ksub = 6000, 128, IVF_CHUNK + 100, 10, 24, 3, 64, 64
-    chunk, table = 4096, M * 256 * 4
+    chunk, table = IVF_CHUNK // 4, M * 256 * 4
     declared = int(be.lib.lvs_ivf_pq_search_workspace_bytes(nq, nlist, nprobe, d, M, k, F16))
     assert chunk * table <= declared < chunk * table + (64 << 20)
+    # halved twice, not once: the tables of 8 192 queries alone fill the budget, and a layout holds more than its tables
+    assert 2 * chunk * table >= IVF_BUDGET >= declared > chunk * table
+    assert plan_native.ivf_chunk("PQ", nq, nlist, nprobe, d, k, F16, M=M) == (chunk, 100, declared)
     xb_s, xq_s, packed, lists, qp, off, rows = _ivf_index(be, nb, d, nq, F16, F16, IP, nlist, seed=9)
     c = be.unpack(lists.centroids).cpu().numpy()
     where = list_of_rows(off, rows, nb)

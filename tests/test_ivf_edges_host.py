@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import ivf_edge_cases as E
+import plan_native
 import synth
 from ivf_pq_oracle_backend import PqOracleBackend
 from lotus_amd import _capi
@@ -47,12 +48,15 @@ def test_shapes_beyond_the_scans_are_refused():
 
 def test_budget_cases_halve_the_chunk():
     """The two cases meant to exceed the 512 MB scratch budget do: all their queries at once need more than the planner ever
-    asks for, so it runs them in chunks of min(nq, 16 384) halved (rounding up) until one fits."""
+    asks for, so it runs them in chunks of min(nq, 16 384) halved (rounding up) until one fits: 3 001 -> 1 501 -> 751 -> 376
+    queries for the two tiled modes, 10 001 -> 5 001 -> 2 501 under the tables of M = 159."""
     lib = _capi.load()
-    for need in (lib.lvs_ivf_search_workspace_bytes(3001, 8200, 2048, 64, 56, E.F16),
-                 lib.lvs_ivf_sq8_search_workspace_bytes(3001, 8200, 2048, 64, 56, E.F16),
-                 lib.lvs_ivf_pq_search_workspace_bytes(10001, 40, 4, 636, 159, 56, E.SPLIT)):
+    for need, plan, chunk in (
+            (lib.lvs_ivf_search_workspace_bytes(3001, 8200, 2048, 64, 56, E.F16), ("Flat", 3001, 8200, 2048, 64, 56, E.F16), 376),
+            (lib.lvs_ivf_sq8_search_workspace_bytes(3001, 8200, 2048, 64, 56, E.F16), ("SQ8", 3001, 8200, 2048, 64, 56, E.F16), 376),
+            (lib.lvs_ivf_pq_search_workspace_bytes(10001, 40, 4, 636, 159, 56, E.SPLIT), ("PQ", 10001, 40, 4, 636, 56, E.SPLIT, 159), 2501)):
         assert 0 < need <= E.WS_BUDGET
+        assert plan_native.ivf_chunk(*plan) == (chunk, plan[1] % chunk, need)
     assert 3001 * 2048 * 56 * 8 > E.WS_BUDGET and 10001 * 159 * 256 * 4 > E.WS_BUDGET
     # the planner never arrives below 128 queries: every halving sequence from 256 or more has an element in [128, 255],
     # and a chunk of 255 fits unhalved (its scratch is more than that of 128, and within the budget)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+import plan_native
 import synth
 from ivf_oracle_backend import IvfOracleBackend, ivf_reference, probe_lists
 from lotus_amd import HipVS, METRIC_INNER_PRODUCT, METRIC_L2, _capi, store
@@ -236,11 +237,11 @@ def test_ivf_workspace_sizes_are_sane():
     one = lib.lvs_ivf_search_workspace_bytes(1, 4096, 32, 768, 10, 0)
     assert 32 * 10 * 8 < one < 64 << 20
     w10k = lib.lvs_ivf_search_workspace_bytes(10000, 4096, 32, 768, 10, 0)
-    assert 10000 * 32 * 10 * 8 <= w10k < 512 << 20
+    assert 10000 * 32 * 10 * 8 <= w10k < plan_native.ivf_limits()[0]
     # many queries go through in chunks: the scratch stays bounded whatever nq is
     big = lib.lvs_ivf_search_workspace_bytes(1_000_000, 4096, 32, 768, 56, _capi.PACK_SPLIT)
-    assert 0 < big <= 512 << 20
-    assert lib.lvs_ivf_search_workspace_bytes(1_000_000, 4096, 2048, 768, 56, 0) <= 512 << 20
+    assert 0 < big <= plan_native.ivf_limits()[0]
+    assert lib.lvs_ivf_search_workspace_bytes(1_000_000, 4096, 2048, 768, 56, 0) <= plan_native.ivf_limits()[0]
     for bad in ((-1, 16, 4, 64, 10, 0), (10, 0, 1, 64, 10, 0), (10, 16, 17, 64, 10, 0), (10, 16, 4, 0, 10, 0),
                 (10, 16, 4, 64, 57, 0), (10, 16, 4, 64, 10, 7)):
         assert lib.lvs_ivf_search_workspace_bytes(*bad) < 0, bad

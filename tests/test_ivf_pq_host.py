@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+import plan_native
 from ivf_pq_oracle_backend import PqOracleBackend, list_of_rows, pq_decode, pq_encode, pq_reference, pq_residuals
 from ivf_sq8_oracle_backend import Sq8OracleBackend
 from lotus_amd import HipVS, METRIC_INNER_PRODUCT, METRIC_L2, _capi, store
@@ -357,7 +358,7 @@ def test_pq_workspace_sizes_and_widths():
         assert lib.lvs_ivf_pq_search_workspace_bytes(10, 64, 4, d, M, k, 1) == _capi.EUNSUPPORTED
     # the per-query tables are part of the scratch: chunked within 512 MB
     big = lib.lvs_ivf_pq_search_workspace_bytes(1_000_000, 4096, 32, 3072, 96, 56, _capi.PACK_SPLIT)
-    assert 0 < big <= 512 << 20
+    assert 0 < big <= plan_native.ivf_limits()[0]
     one = lib.lvs_ivf_pq_search_workspace_bytes(1, 16, 4, 768, 64, 10, _capi.PACK_F16)
     assert one >= 64 * 256 * 4
     for bad in ((-1, 16, 4, 64, 8, 10, 0), (10, 0, 1, 64, 8, 10, 0), (10, 16, 17, 64, 8, 10, 0), (10, 16, 4, 0, 8, 10, 0),

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+import plan_native
 from ivf_sq8_oracle_backend import (Sq8OracleBackend, list_of_rows, sq8_decode, sq8_encode, sq8_reference, sq8_train)
 from lotus_amd import HipVS, METRIC_INNER_PRODUCT, METRIC_L2, _capi, store
 from oracle_backend import _emulate_storage
@@ -296,7 +297,7 @@ def test_sq8_workspace_sizes_and_widths():
     for d, k in ((2369, 56), (2433, 32), (3072, 10)):
         assert lib.lvs_ivf_sq8_search_workspace_bytes(10, 64, 4, d, k, 1) == _capi.EUNSUPPORTED
     big = lib.lvs_ivf_sq8_search_workspace_bytes(1_000_000, 4096, 32, 1536, 56, _capi.PACK_SPLIT)
-    assert 0 < big <= 512 << 20
+    assert 0 < big <= plan_native.ivf_limits()[0]
     for bad in ((-1, 16, 4, 64, 10, 0), (10, 0, 1, 64, 10, 0), (10, 16, 17, 64, 10, 0), (10, 16, 4, 0, 10, 0),
                 (10, 16, 4, 64, 57, 0), (10, 16, 4, 64, 10, 7)):
         assert lib.lvs_ivf_sq8_search_workspace_bytes(*bad) < 0, bad

@@ -1,5 +1,6 @@
-"""The flat search's host planner (lotus_amd/csrc/lvs_plan.h), pinned: dump lines of tests/native/plan_check.cpp recorded from the
-commit before the planner got a header of its own.  A line holds the operand layout, the tile geometry, the two-phase plan, the
+"""The host planners (lotus_amd/csrc/lvs_plan.h, lvs_ivf_plan.h), pinned: dump lines of tests/native/plan_check.cpp recorded from the
+commit before each planner got a header of its own (the "ivf", "bucket" and "join" lines: from that commit's arithmetic
+copied by hand, see profiles/ivf_plan_refactor_check.md).  A line holds the operand layout, the tile geometry, the two-phase plan, the
 route, the chunk list and the workspace offsets of one shape (field order: print_row in plan_check.cpp), so a change of any
 planning decision for these shapes shows here - on purpose or not."""
 import plan_native
@@ -82,11 +83,45 @@ PINS = [
     "nq=0 nb=0 d=8 k=1 pack=0/0 hi=0 | lay 64 1 64 64 1 1 0 0 0 0 0 0 4 | geo 1 1 1 1 0 1 1 1 1 | tp 0 | route 3 0 0 0 0 | chunks - | ws 256 256 256 256 2560 5888 5888 | bytes 5888",
 ]
 
+# field order: ivf_shape, bucket_shape and join_shape in plan_check.cpp
+IVF_PINS = [
+    # IVF-Flat: the budget case of tests/ivf_edge_cases.py - 3 001 queries in chunks of 376 and a last one of 369
+    "ivf mode=0 nq=3001 nlist=8200 nprobe=2048 d=64 M=1 k=56 pack=0 | rc 0 | chunk 376 tail 369 | lay 3033856 9194240 9194240 15392768 15425792 15555072 3033856 6198528 32265 360536576 | prange 0 0 | bytes 360536576",
+    # ... halved once: two chunks of 8 192 and a last chunk of one query
+    "ivf mode=0 nq=16385 nlist=4097 nprobe=257 d=1088 M=1 k=16 pack=1 | rc 0 | chunk 8192 tail 1 | lay 7373056 24215808 24215808 36869120 36885760 37165568 7373056 12653312 69890 306649600 | prange 0 0 | bytes 306649600",
+    # ... the widest fp16 rows at k = 56, and one K-step beyond: LVS_EUNSUPPORTED
+    "ivf mode=0 nq=255 nlist=40 nprobe=4 d=2240 M=1 k=56 pack=0 | rc 0 | chunk 255 tail 0 | lay 2955264 2963456 2963456 2968320 2968576 2969088 2955264 4864 72 3426048 | prange 0 0 | bytes 3426048",
+    "ivf mode=0 nq=255 nlist=40 nprobe=4 d=2304 M=1 k=56 pack=0 | rc -4 | bytes -4",
+    # nprobe > nlist: LVS_EINVAL
+    "ivf mode=0 nq=255 nlist=1 nprobe=16 d=64 M=1 k=16 pack=0 | rc -1 | bytes -1",
+    # IVF-SQ8, two-digit bucket sort of the pairs (nlist + 1 > BUCKET_MAX_BINS)
+    "ivf mode=1 nq=40000 nlist=24576 nprobe=16 d=2368 M=1 k=56 pack=1 | rc 0 | chunk 16384 tail 7232 | lay 30212352 32309504 32309504 35030016 35128576 35259904 30212352 2720512 32769 152700416 | prange 0 0 | bytes 152700416",
+    # IVF-PQ: the tables bound the chunk (10 001 queries at M = 159: 2 501 + ... + 2 498); no tiling regions
+    "ivf mode=2 nq=10001 nlist=40 nprobe=4 d=636 M=159 k=56 pack=1 | rc 0 | chunk 2501 tail 2498 | lay 3170304 3250432 410453248 410453248 410453248 410453248 3170304 0 0 414935040 | prange 1 1 | bytes 414935040",
+    # ... prange 16 for a full chunk
+    "ivf mode=2 nq=40000 nlist=8200 nprobe=2048 d=64 M=8 k=17 pack=0 | rc 0 | chunk 1024 tail 64 | lay 2298112 19075328 27463936 27463936 27463936 27463936 2298112 0 0 312676608 | prange 16 16 | bytes 312676608",
+    # the threshold search: no parts region (off_parts = total)
+    "ivf mode=3 nq=40000 nlist=4097 nprobe=257 d=1216 M=1 k=0 pack=1 | rc 0 | chunk 16384 tail 7232 | lay 14745856 48431360 48431360 73720832 73737472 74280448 14745856 25289472 135682 74280448 | prange 0 0 | bytes 74280448",
+    # the bucket sort: one digit up to 24 575 buckets, two from 24 576
+    "bucket n=1000000 k=24575 | ok 1 | 123 1 24576 0 0 0 4294967295 0 | 0 12091392 12097536 16097536 16097536 | bytes 16196096",
+    "bucket n=1000000 k=24576 | ok 1 | 123 2 4096 7 0 12 4095 4294967295 | 0 2015232 2016256 6016256 10016256 | bytes 10114816",
+    # the threshold join, self-join of 70 001 rows: lvs_rj_kernel on whole blocks from the chunk's first row, the last 17 rows
+    # and the chunks left with a short corpus through the list kernel (kernel:c0:cn:r0:rn)
+    "join nq=70001 nb=70001 q_row0=0 id_offset=0 d=768 pack=0 metric=0 stride=1 | rj 1 | launches 1:0:32768:0:69984 0:0:32768:69984:17 1:32768:32768:32768:37216 0:32768:32768:69984:17 0:65536:4096:65536:4465 0:69632:369:69632:369",
+    # ... a plain join of the same shape
+    "join nq=70001 nb=70001 q_row0=-1 id_offset=0 d=768 pack=0 metric=0 stride=1 | rj 1 | launches 1:0:32768:0:69984 0:0:32768:69984:17 1:32768:32768:0:69984 0:32768:32768:69984:17 1:65536:4096:0:69984 0:65536:4096:69984:17 1:69632:369:0:69984 0:69632:369:69984:17",
+    # ... queries that are rows 5 000 .. of the corpus
+    "join nq=40000 nb=40001 q_row0=5000 id_offset=0 d=768 pack=0 metric=0 stride=1 | rj 1 | launches 1:0:32768:4992:35008 0:0:32768:40000:1 0:32768:4096:37760:2241",
+    # ... below 2 048 queries, or hi|lo rows: one launch of the list kernel
+    "join nq=2047 nb=100031 q_row0=0 id_offset=0 d=768 pack=0 metric=0 stride=1 | rj 0 | launches 0:0:2047:0:100031",
+    "join nq=40000 nb=100000 q_row0=0 id_offset=0 d=768 pack=1 metric=0 stride=1 | rj 0 | launches 0:0:40000:0:100000",
+]
+
 
 def test_pinned_plans():
     out = plan_native.run("--dump")
     assert out.returncode == 0, out.stdout[-500:]
     have = {ln.split("|")[0]: ln for ln in out.stdout.splitlines()}
-    assert len(have) == 147840
-    for pin in PINS:
+    assert sum(key.startswith("nq=") for key in have) == 147840
+    for pin in PINS + IVF_PINS:
         assert have[pin.split("|")[0]] == pin

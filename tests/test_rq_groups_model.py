@@ -168,3 +168,39 @@ def test_the_models_are_the_compiled_rules():
     # chunks() at its default records the threshold join's cut (range_chunk_len)
     nqs = [1, 4096, 4097, 5000, 9000, 10_000, 20_000, 33_000, 40_000, 65_536, 100_000, 1_000_000]
     assert ask([f"range_chunks {nq}" for nq in nqs]) == [chunks(nq) for nq in nqs]
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 4296, 40_000, 70_001])
+def test_self_join_launches_offer_every_pair_above_the_diagonal_once(n):
+    """The threshold join's plan (``lvs_range_rj_ok``, ``range_chunk_len``, ``lvs_range_chunk_plan`` through the ``range_plan``
+    question) for a self-join of n fp16 rows under the inner product: query i is row i and the join reports every pair
+    (i, j > i).  A launch is a rectangle of queries x rows in which the kernel keeps j > i; the rectangles are disjoint, and
+    for every query the rows above it that the rectangles hold are all n - 1 - i of them - so each pair is offered exactly
+    once.  ``lvs_rj_kernel`` gets whole 32-row blocks, at least 32 768 rows and a group count it deals; the last n % 32 rows go
+    to the list kernel, once per chunk that still has rows."""
+    import numpy as np
+
+    flat = plan_native.ask([f"range_plan {n} {n} 0 0 768 0 0 1"])[0]
+    launches = [tuple(flat[i:i + 5]) for i in range(0, len(flat), 5)]  # kernel (1: lvs_rj_kernel, 0: list kernel), c0, cn, r0, rn
+    if n < 2048:
+        assert launches == [(0, 0, n, 0, n)]
+    else:
+        cuts = np.cumsum([0] + chunks(n))
+        assert sorted({(c0, cn) for _, c0, cn, _, _ in launches} | {(int(cuts[-2]), int(cuts[-1] - cuts[-2]))}) == \
+            [(int(a), int(b - a)) for a, b in zip(cuts[:-1], cuts[1:])]  # (the last chunk may have no row left above it)
+    offered = np.zeros(n, np.int64)
+    for a, (kernel, c0, cn, r0, rn) in enumerate(launches):
+        assert cn > 0 and rn > 0 and 0 <= r0 and r0 + rn <= n and c0 + cn <= n
+        for _, c0b, cnb, r0b, rnb in launches[a + 1:]:
+            assert c0 + cn <= c0b or c0b + cnb <= c0 or r0 + rn <= r0b or r0b + rnb <= r0, "rectangles overlap"
+        i = np.arange(c0, c0 + cn)
+        offered[c0:c0 + cn] += np.maximum(0, r0 + rn - np.maximum(r0, i + 1))
+        if kernel == 1:
+            groups = -(-cn // GROUPQ)
+            assert r0 % 32 == 0 and rn % 32 == 0 and rn >= 32768 and cn > 128 and (groups <= 32 or groups % 32 == 0)
+            assert r0 + rn == n // 32 * 32
+            tails = [l for l in launches if l[0] == 0 and l[1:3] == (c0, cn)]
+            assert tails == ([(0, c0, cn, n // 32 * 32, n % 32)] if n % 32 else [])
+        else:
+            assert r0 + rn == n  # the list kernel takes a chunk's rows to the end, ragged block included
+    assert np.array_equal(offered, n - 1 - np.arange(n))

@@ -33,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 PEAK_FLOPS, PEAK_BPS = 2.5e15, 8e12
-IN_CALL_CHUNK = 16384  # queries per chunk inside lvs_ivf_range_search (the tiles are cut per chunk)
+IN_CALL_CHUNK = 16384  # IVF_CHUNK_MAX (lotus_amd/csrc/lvs_ivf_plan.h): queries per chunk inside lvs_ivf_range_search (the tiles are cut per chunk)
 
 
 def timed_rounds(be, paths, reps):
