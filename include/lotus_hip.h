@@ -56,7 +56,8 @@ extern "C" {
                                 three list scans (lvs_ivf_search_keys_sel, lvs_ivf_sq8_search_keys_sel,
                                 lvs_ivf_pq_search_keys_sel) - the plain entries are these with sel_bits = NULL; the threshold
                                 search through the lists (lvs_ivf_range_workspace_bytes, lvs_ivf_range_search,
-                                LVS_KERNEL_IVF_RANGE) */
+                                LVS_KERNEL_IVF_RANGE); recall measurement on resident keys (lvs_keys_overlap, lvs_ivf_row_lists,
+                                lvs_ivf_probe_ranks) */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -598,6 +599,32 @@ int32_t lvs_ivf_pq_search_keys_sel(const uint8_t* codes, const float* beta, cons
 int32_t lvs_refine_keys(const void* xb, int32_t xb_pack, int64_t nb, const float* xb_norms_sq, const void* xq, int32_t xq_pack,
                         int64_t nq, const float* xq_norms_sq, int32_t d, int32_t metric, const uint64_t* cand_keys, int32_t kc,
                         int32_t k, uint64_t* out_keys, void* stream);
+
+/* ---- recall measurement on resident keys (faiss `AutoTune`'s IntersectionCriterion / OneRecallAtRCriterion, computed where
+ * the keys are).  Keys as everywhere: ord32(score) << 32 | (0xFFFFFFFF - row); ONLY the row number is compared - the two
+ * lists may carry scores from different arithmetic.  A key is empty when it is 0, and also when its low half is 0 (row
+ * 2^32 - 1, which no image has).  Plain device pointers, no workspace, no allocation, no synchronisation; every argument
+ * check precedes the first device call. ---- */
+/* truth_keys [nq][kt], got_keys [nq][kg], 1 <= kt, kg <= LVS_MAX_K.  out_hits[q] (int32): how many non-empty entries of
+ * truth_keys[q] name a row that a non-empty entry of got_keys[q] names (a row repeated in got counts once: the count runs
+ * over truth).  out_first[q] (int32): 1 when the row of truth_keys[q][0] is among them, 0 otherwise and when that slot is
+ * empty.  nq == 0: LVS_OK without a launch.  lvs_keys_overlap_kernel: one wave per query, got's rows staged in LDS. */
+int32_t lvs_keys_overlap(const uint64_t* truth_keys, int32_t kt, const uint64_t* got_keys, int32_t kg, int64_t nq,
+                         int32_t* out_hits, int32_t* out_first, void* stream);
+/* The inverse of the lists of lvs_ivf_build_lists: out_row_list[rows[p]] = l (int32 [n]) for every position p in
+ * [offsets[l], offsets[l + 1]); entries of rows in no list are left as the caller set them.  Any number of empty lists
+ * anywhere; a row number >= n is never written through.  n == 0: LVS_OK without a launch. */
+int32_t lvs_ivf_row_lists(const int64_t* offsets, const uint32_t* rows, int64_t n, int32_t nlist, int32_t* out_row_list,
+                          void* stream);
+/* Where does each true neighbour's list stand in the query's coarse ranking?  probe int32 [nq][P], best first, padded with -1
+ * (the out_probe of the list searches), 1 <= P <= LVS_MAX_K; row_list: lvs_ivf_row_lists's array for an image of n rows.
+ * out_rank[q][j] (int32 [nq][kt]): the position in probe[q] of the list that holds the row of truth_keys[q][j]; P when that
+ * list (or any list: row_list < 0) is not among the probes; -1 for an empty key or a row number >= n (never read).
+ * out_hist (uint64 [P + 1], zeroed by the caller or carrying earlier calls' counts): bin r += the non-empty entries of rank r,
+ * by atomics.  The share of the true neighbours that nprobe = p can reach is sum(hist[:p]) / sum(hist).  nq == 0: LVS_OK
+ * without a launch. */
+int32_t lvs_ivf_probe_ranks(const uint64_t* truth_keys, int32_t kt, const int32_t* row_list, int64_t n, const int32_t* probe,
+                            int32_t P, int64_t nq, int32_t* out_rank, uint64_t* out_hist, void* stream);
 
 /* ---- measurement hook: average duration in ms of the dominant search kernel's launches since the last reset,
  * measured with HIP events on the launch stream (enabled with lvs_timing_enable(1)). ---- */

@@ -120,6 +120,9 @@ SIGNATURES = {
     "lvs_ivf_range_search": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32,
                                     _i32, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "lvs_refine_keys": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "lvs_keys_overlap": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "lvs_ivf_row_lists": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "lvs_ivf_probe_ranks": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp]),
     "lvs_timing_enable": (_i32, [_i32]),
     "lvs_timing_read": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),
     "lvs_timing_read_calls": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),

@@ -33,6 +33,7 @@ class IvfLists:
     rows: "object"       # torch.Tensor int32 [n] holding uint32 row numbers, ascending inside a list
     nlist: int
     metric: int
+    row_list: "object" = None  # torch.Tensor int32 [n]: the list of every row; made by ``ivf_row_lists`` on first use
 
 
 def ivf_fits(d: int, k: int, mode: int) -> bool:
@@ -1252,6 +1253,47 @@ class HipBackend:
         self._c("lvs_refine_keys", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(queries.rows), queries.mode,
                 nq, _ptr(queries.norms), corpus.d, metric, _ptr(cand), kc, int(k), _ptr(out), self._stream())
         return out
+
+    # ---- recall measurement on resident keys ----
+    def keys_overlap(self, truth, got):
+        """truth int64 keys [nq, kt], got int64 keys [nq, kg] -> (hits, first), int32 device tensors [nq]: how many of a
+        query's non-empty ``truth`` rows are among its ``got`` rows, and whether its first ``truth`` row is
+        (``lvs_keys_overlap``).  Only row numbers are compared - the score halves may come from different arithmetic."""
+        torch = self.torch
+        nq, kt, kg = int(truth.shape[0]), int(truth.shape[1]), int(got.shape[1])
+        if int(got.shape[0]) != nq:
+            raise ValueError(f"got has {int(got.shape[0])} rows for {nq} queries")
+        truth, got = truth.contiguous(), got.contiguous()
+        hits = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        first = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        self._c("lvs_keys_overlap", _ptr(truth), kt, _ptr(got), kg, nq, _ptr(hits), _ptr(first), self._stream())
+        return hits, first
+
+    def ivf_row_lists(self, lists: IvfLists):
+        """-> int32 device tensor [n]: the list of every row, -1 for a row in no list (``lvs_ivf_row_lists``, the inverse of
+        ``lists.rows``).  Computed on first use and kept on the ``IvfLists`` object."""
+        cached = lists.row_list
+        if cached is None:
+            n = int(lists.rows.numel())
+            cached = self.torch.full((n,), -1, dtype=self.torch.int32, device=self.device)
+            self._c("lvs_ivf_row_lists", _ptr(lists.offsets), _ptr(lists.rows), n, lists.nlist, _ptr(cached), self._stream())
+            lists.row_list = cached
+        return cached
+
+    def ivf_probe_ranks(self, truth, row_list, probe):
+        """truth int64 keys [nq, kt], row_list (``ivf_row_lists``), probe int32 [nq, P] (best first, -1 padded) -> (rank int32
+        [nq, kt], hist int64 [P + 1]), device tensors: the position in ``probe[q]`` of the list of every ``truth`` row (P:
+        not probed, -1: empty slot) and how many non-empty entries have each rank (``lvs_ivf_probe_ranks``)."""
+        torch = self.torch
+        nq, kt, P = int(truth.shape[0]), int(truth.shape[1]), int(probe.shape[1])
+        if int(probe.shape[0]) != nq:
+            raise ValueError(f"probe has {int(probe.shape[0])} rows for {nq} queries")
+        truth, probe = truth.contiguous(), probe.contiguous()
+        rank = torch.empty((nq, kt), dtype=torch.int32, device=self.device)
+        hist = torch.zeros((P + 1,), dtype=torch.int64, device=self.device)
+        self._c("lvs_ivf_probe_ranks", _ptr(truth), kt, _ptr(row_list), int(row_list.numel()), _ptr(probe), P, nq, _ptr(rank),
+                _ptr(hist), self._stream())
+        return rank, hist
 
     def merge_keys(self, parts):
         """parts int64 [P, nq, k] -> [nq, k]."""

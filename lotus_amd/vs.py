@@ -158,6 +158,54 @@ class _CallPlan:
     layout: tuple  # ``_layout()``
 
 
+@dataclass
+class RecallReport:
+    """What ``HipVS.recall`` measured: entry i belongs to ``nprobes[i]``."""
+
+    nprobes: tuple  # lists probed per query, as ``__call__`` would probe them (never more than nlist)
+    intersection: np.ndarray  # float64 [len(nprobes)]: mean over the queries of hits / true neighbours (faiss's
+    #                           IntersectionCriterion, normalised to [0, 1])
+    first: np.ndarray  # float64 [len(nprobes)]: share of the queries whose true best row is among the K returned (faiss's
+    #                    OneRecallAtRCriterion at R = K)
+    served: tuple  # bool per entry: True - the list scan serves this call; False - it is served exactly (recall 1.0, nothing
+    #                was launched for the entry)
+    nq: int
+    K: int
+    kc: int  # candidates per query of the list scan: K, more on a Refine(Flat) store (``refine_candidates``)
+    hits: np.ndarray  # int32 [len(nprobes), nq]: true neighbours returned, per query
+
+
+@dataclass
+class _RecallRun:
+    """One ``recall`` / ``probe_recall_curve`` / ``tune_nprobe`` call: its checked arguments, the queries packed once and, from
+    the first use on, the exact keys every measurement is compared with."""
+
+    ent: Any
+    q: Any  # the query matrix as ``_plan_call`` takes it
+    K: int
+    kw: dict  # the per-call keywords a measured ``__call__`` would carry besides ``nprobe``
+    queries: Any  # backend PackedRows
+    k_eff: int
+    truth: Any = None  # int64 key tensor [nq, k_eff]
+    denom: Any = None  # host int64 [nq]: non-empty slots of ``truth``
+
+
+def _mean_ratio(hits: np.ndarray, denom: np.ndarray) -> float:
+    """Mean over the queries of hits / denom.  With one denominator for all - every exact list full, the usual case - it is
+    sum / sum: ONE rounding, so that equal counts give the same float however they were gathered."""
+    denom = np.maximum(np.asarray(denom, np.int64), 1)
+    if np.all(denom == denom[0]):
+        return float(int(np.sum(hits, dtype=np.int64)) / int(denom.sum()))
+    return float(np.mean(np.asarray(hits, np.float64) / denom))
+
+
+def _curve_of(hist: np.ndarray) -> np.ndarray:
+    """Histogram of probe ranks [P + 1] (last bin: not probed) -> float64 [P + 1]: entry p = share of ranks below p."""
+    total = int(hist.sum())
+    below = np.concatenate([[0], np.cumsum(hist[:-1], dtype=np.int64)])
+    return below / float(max(total, 1))
+
+
 def _host(t) -> np.ndarray:
     return t.cpu().numpy()
 
@@ -907,9 +955,221 @@ class HipVS(VS):
         if self._mode.fits(be, ent, 1):
             _, probe = self._mode.search(be, ent, queries, 1, self.metric, nprobe, want_probe=True)
             return probe.cpu().numpy()
-        # the coarse step on its own: lvs_flat_search_keys over the centroids, as inside lvs_ivf_search_keys
-        keys = be.search_keys(ent.ivf.centroids, queries, nprobe, self.metric, one_pass=False).cpu().numpy().view(np.uint64)
-        return np.where(keys == 0, -1, 0xFFFFFFFF - (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int32)
+        return self._coarse_probe(ent, queries, nprobe).cpu().numpy()
+
+    def _coarse_probe(self, ent: _Resident, queries, nprobe: int):
+        """-> int32 device tensor [nq, nprobe], list ids best first, -1 past them: the coarse step on its own -
+        lvs_flat_search_keys over the centroids, as inside lvs_ivf_search_keys - without a scan behind it."""
+        import torch
+
+        keys = self.backend.search_keys(ent.ivf.centroids, queries, nprobe, self.metric, one_pass=False)
+        return torch.where(keys == 0, -1, 0xFFFFFFFF - (keys & 0xFFFFFFFF)).to(torch.int32)
+
+    # ------------------------------------------------------------------------------------------------ recall
+    def _recall_begin(self, query_vectors, K, k_factor, what: str) -> "_RecallRun":
+        """What ``recall``, ``probe_recall_curve`` and ``tune_nprobe`` check alike; the queries are packed once, here."""
+        ent = self._ivf_current()
+        lay = self._layout()
+        if lay[1] > 1 or lay[3] > 1:
+            raise ValueError(f"{what} needs an unsharded store: this one is split over {lay[1]} x {lay[3]} ranks")
+        q = self._query_matrix(query_vectors, ent)
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or int(K) < 1:
+            raise ValueError(f"K must be an int >= 1, got {K!r}")
+        if int(q.shape[0]) == 0:
+            raise ValueError("query_vectors holds no query: recall over nothing is undefined")
+        be = self.backend
+        missing = [a for a in ("keys_overlap", "ivf_row_lists", "ivf_probe_ranks") if not hasattr(be, a)]
+        if missing:
+            raise ValueError(f"{what} needs a backend that compares keys ({type(be).__name__} lacks {missing[0]})")
+        kw = {} if k_factor is None else {"k_factor": self._check_k_factor(k_factor)}
+        queries = be.pack(q, ent.packed.mode, normalize=self.normalize, exp=ent.packed.exp, check=True)
+        return _RecallRun(ent=ent, q=q, K=int(K), kw=kw, queries=queries, k_eff=min(int(K), ent.n))
+
+    def _recall_truth(self, run: "_RecallRun"):
+        """The exact keys of the run's queries over the full image at ``k_eff``, searched once, and how many slots of each
+        query's list hold a row (host int64 [nq]; all of them unless the image holds non-finite scores)."""
+        if run.truth is None:
+            run.truth = self.backend.search_keys(run.ent.packed, run.queries, run.k_eff, self.metric, id_offset=run.ent.lo)
+            run.denom = _host((run.truth != 0).sum(dim=1)).astype(np.int64)
+        return run.truth
+
+    def _recall_plan(self, run: "_RecallRun", nprobe) -> _CallPlan:
+        """The plan ``__call__(query_vectors, K, nprobe=nprobe[, k_factor=...])`` would follow."""
+        return self._plan_call(run.ent, run.q, run.K, None, dict(run.kw, nprobe=nprobe))
+
+    def _recall_measure(self, run: "_RecallRun", nprobes) -> "RecallReport":
+        """One ``RecallReport`` entry per value of ``nprobes``: the route is decided as ``__call__`` decides it; a list-scan
+        call is searched through ``_route_ivf`` and compared with the exact keys on the device, any other call is exact."""
+        be = self.backend
+        plans = [self._recall_plan(run, p) for p in nprobes]
+        served = [pl.route == "ivf" for pl in plans]
+        nq = run.queries.n
+        hits = np.full((len(plans), nq), run.k_eff, np.int32)
+        first = np.ones((len(plans), nq), np.int32)
+        inter = np.ones(len(plans), np.float64)
+        if any(served):
+            truth = self._recall_truth(run)  # ahead of the first scan
+            score_exp = be.score_exp_of(run.ent.packed, run.queries)
+            counts = {i: be.keys_overlap(truth, self._route_ivf(pl, run.ent, run.queries, score_exp)[0])
+                      for i, pl in enumerate(plans) if served[i]}
+            for i, (h, f) in counts.items():  # every launch is queued; only the counts come back
+                hits[i], first[i] = _host(h), _host(f)
+                inter[i] = _mean_ratio(hits[i], run.denom)
+        return RecallReport(nprobes=tuple(pl.nprobe for pl in plans), intersection=inter,
+                            first=first.mean(axis=1, dtype=np.float64), served=tuple(served), nq=nq, K=run.K, kc=plans[0].kc,
+                            hits=hits)
+
+    def _recall_ceiling(self, run: "_RecallRun", P: int):
+        """-> (rank int32 device tensor [nq, k_eff], histogram of the ranks as host int64 [P + 1]): where the list of every
+        true neighbour stands among the query's ``P`` best lists.  One exact search, one coarse step, ``lvs_ivf_probe_ranks``."""
+        be, ent = self.backend, run.ent
+        probe = self._coarse_probe(ent, run.queries, P)
+        rank, hist = be.ivf_probe_ranks(self._recall_truth(run), be.ivf_row_lists(ent.ivf), probe)
+        return rank, _host(hist).astype(np.int64)
+
+    @_serialised
+    def recall(self, query_vectors, K: int, nprobe=None, k_factor: float | None = None) -> "RecallReport":
+        """What a plain ``__call__(query_vectors, K)`` of this IVF store finds of the exact answer, measured on the device.
+
+        ``nprobe``: an int or a sequence of ints (None: the store's); every value gives one entry of the report, values
+        above ``nlist`` count as ``nlist`` (as in ``__call__``, and so reported).  ``k_factor``: as ``__call__`` takes it
+        (None: the store's).  For every value the route is decided exactly as ``__call__`` decides it.  A call the list scan
+        serves is searched as ``__call__`` searches it - with the re-ranking and candidate count of a ``Refine(Flat)`` store -
+        and its keys are compared, by row number, with the exact top ``min(K, n)`` of the full image, which is searched once;
+        only the per-query counts come back to the host.  A call that would be served exactly anyway (K > 56, rows too wide
+        for the scan, more than 2 048 probes) is reported as recall 1.0 with ``served=False``, and nothing is launched for it.
+
+        Needs an unsharded store with lists.  ``query_vectors`` as ``__call__`` takes them (device tensors included)."""
+        run = self._recall_begin(query_vectors, K, k_factor, "recall")
+        if nprobe is None:
+            nprobes = [self.nprobe]
+        elif isinstance(nprobe, (int, np.integer)) and not isinstance(nprobe, bool):
+            nprobes = [nprobe]
+        else:
+            try:
+                nprobes = list(nprobe)
+            except TypeError:
+                raise ValueError(f"nprobe must be an int >= 1 or a sequence of them, got {nprobe!r}") from None
+            if not nprobes:
+                raise ValueError("nprobe must name at least one value")
+        return self._recall_measure(run, [self._check_nprobe(p) for p in nprobes])
+
+    def _curve_width(self, ent: _Resident, max_nprobe) -> int:
+        nlist = ent.ivf.nlist
+        return min(nlist if max_nprobe is None else self._check_nprobe(max_nprobe), nlist, _capi.MAX_K)
+
+    @_serialised
+    def probe_recall_curve(self, query_vectors, K: int, max_nprobe: int | None = None) -> np.ndarray:
+        """-> float64 [P + 1], ``P = min(max_nprobe or nlist, nlist, 2048)``: entry p is the share of the exact top-``K`` rows
+        whose list is among the query's best p lists (entry 0 is 0) - the recall that probing alone allows at ``nprobe = p``.
+
+        For an ``IVF<nlist>,Flat`` store, whose scan is exact over the probed lists, this IS ``recall(...).intersection`` at
+        every ``nprobe <= P`` (up to near-ties: two rows whose scores the exact search and the list scan order differently can
+        move one slot).  For the code modes it is a ceiling that no codec, ``k_factor`` or refiner lifts: a row whose list is
+        not probed cannot be returned.  Costs one exact search, one coarse step at P (no list scan), one
+        ``lvs_ivf_probe_ranks`` and a cumulative sum of P + 1 counts on the host.  Needs an unsharded store with lists."""
+        run = self._recall_begin(query_vectors, K, None, "probe_recall_curve")
+        _, hist = self._recall_ceiling(run, self._curve_width(run.ent, max_nprobe))
+        return _curve_of(hist)
+
+    @_serialised
+    def tune_nprobe(self, query_vectors, K: int, target: float = 0.95, measure: str = "intersection",
+                    k_factor: float | None = None, apply: bool = True):
+        """-> ``(nprobe, RecallReport)``: the smallest ``nprobe`` found whose MEASURED recall of ``__call__(query_vectors, K)``
+        reaches ``target``, and the one-entry report of that measurement.  ``measure``: ``"intersection"`` (share of the exact
+        top K returned, the default) or ``"first"`` (share of queries whose true best row is returned).
+
+        The search starts at the smallest p whose probe-limited ceiling (``probe_recall_curve``; for ``"first"``, the share
+        of queries whose best row's list is among the p best) reaches the target: nothing below can, in any mode.  For an
+        ``IVF<nlist>,Flat`` store that p is the answer - its recall is the ceiling - and no list scan is run; its report is
+        made from the same ranks.  A code store is measured there, then at doubled values up to ``min(nlist, 2048)`` until the
+        target is met, then bisected between the last miss and the first hit.  The coarse ranking behind the ceiling is
+        taken 56 lists deep first - one pass over the centroids, a fraction of the exact search beside it - and four times
+        deeper only while the ceiling stays below the target, so a Flat tune costs about one exact search.
+
+        The guarantee is about the returned value: its measured recall on THESE queries is >= ``target`` (for a Flat store:
+        up to near-ties, see ``probe_recall_curve``).  Measured recall of a code mode need not be monotone in ``nprobe``, so
+        the value is minimal only up to that: a smaller one between two misses is not looked for.  The sample decides: the
+        queries should look like the ones the store will serve.
+
+        ``ValueError`` when the largest admissible ``nprobe`` misses the target; the message names the best measured value
+        and the ceiling there - a ceiling below the target means the probes fall short (only reachable below ``nlist``); a
+        ceiling above it means the codec does: raise ``k_factor`` on a ``Refine(Flat)`` store, or use one.  When the call
+        would be served exactly whatever ``nprobe`` says (K > 56, rows too wide for the scan), the store's ``nprobe`` comes
+        back unchanged with ``served=(False,)``.  ``apply=True`` sets ``self.nprobe`` to the result and nothing else."""
+        if isinstance(target, bool) or not isinstance(target, (int, float, np.integer, np.floating)) or not 0 < target <= 1:
+            raise ValueError(f"target must be a real number in (0, 1], got {target!r}")
+        if measure not in ("intersection", "first"):
+            raise ValueError(f"measure must be 'intersection' or 'first', got {measure!r}")
+        if not isinstance(apply, (bool, np.bool_)):
+            raise ValueError(f"apply must be a bool, got {apply!r}")
+        target = float(target)
+        run = self._recall_begin(query_vectors, K, k_factor, "tune_nprobe")
+        if self._recall_plan(run, 1).route != "ivf":  # exact whatever nprobe says: nothing to tune, nothing launched
+            return self.nprobe, self._recall_measure(run, [self.nprobe])
+        pmax = self._curve_width(run.ent, None)
+        known = {}  # the coarse ranking as far as it was needed: P, the ranks, the ceiling at every p <= P
+
+        def widen(P: int) -> None:
+            rank, hist = self._recall_ceiling(run, P)
+            if measure == "first":  # the rank of each query's best row's list: nq counts
+                r0 = _host(rank[:, 0]).astype(np.int64)
+                hist = np.bincount(np.where(r0 < 0, P, r0), minlength=P + 1)
+            known.update(P=P, rank=rank, ceiling=_curve_of(hist))
+
+        # a ranking of 2 048 lists costs far more than the exact search beside it (a two-pass k = 2 048 search of the
+        # centroids); the first 56 come from the one-pass search and settle most stores, wider ones only on demand
+        widen(min(pmax, _capi.IVF_MAX_K))
+        while not np.any(known["ceiling"] >= target) and known["P"] < pmax:
+            widen(min(pmax, 4 * known["P"]))
+        reports = {}
+
+        def value(p: int) -> float:
+            if p not in reports:
+                reports[p] = self._recall_measure(run, [p])
+            return float(getattr(reports[p], measure)[0])
+
+        def fail(p: int):
+            if p > known["P"]:
+                widen(p)
+            ceiling = known["ceiling"]
+            if reports:
+                best = max(reports, key=lambda v: (value(v), -v))
+                got = f"the best measured is {value(best):.4f} at nprobe={best}"
+            else:  # an IVF-Flat store: its recall is its ceiling
+                got = f"the best measured is {ceiling[p]:.4f} at nprobe={p}"
+            return ValueError(f"tune_nprobe: {measure} recall {target:g} at K={run.K} is not reached up to nprobe={p}: {got}, "
+                              f"the probe-limited ceiling at nprobe={p} is {ceiling[p]:.4f}")
+
+        reach = np.flatnonzero(known["ceiling"] >= target)
+        if reach.size == 0:  # the probes fall short whatever the codec does; a code store is still measured once, to say by how much
+            if self._mode.kind != "Flat":
+                value(pmax)
+            raise fail(pmax)
+        rank = known["rank"]
+        p = int(reach[0])
+        if self._mode.kind == "Flat":  # exact over the probed lists: the ceiling is the recall
+            inside = (rank >= 0) & (rank < p)
+            hits = _host(inside.sum(dim=1)).astype(np.int32)[None, :]
+            first = _host(inside[:, 0]).astype(np.float64)
+            reports[p] = RecallReport(nprobes=(p,), intersection=np.array([_mean_ratio(hits[0], run.denom)], np.float64),
+                                      first=np.array([first.mean()], np.float64), served=(True,), nq=run.queries.n, K=run.K,
+                                      kc=run.K, hits=hits)
+        else:
+            lo = p - 1  # below p nothing reaches the target
+            while value(p) < target:
+                if p == pmax:
+                    raise fail(pmax)
+                lo, p = p, min(2 * p, pmax)
+            while p - lo > 1:
+                mid = (lo + p) // 2
+                if value(mid) >= target:
+                    p = mid
+                else:
+                    lo = mid
+        if apply:
+            self.nprobe = p
+        return p, reports[p]
 
     def _range_args(self, ent: _Resident, ids, nprobe, what: str):
         """What ``range_search`` and ``ivf_self_pairs`` check alike -> (``ids`` as a vector or None for every row, lists probed

@@ -9,8 +9,8 @@ Per workload, column (exact, then every chosen mode whose list scan takes the wi
   * hbm_share: bytes of the probed rows as the scan reads them (PQ: M code bytes per row; SQ8: d; IVF-Flat: 2 or 4 bytes
     per dimension) over 8 TB/s, over kernel time - 1 query: every probed row once; 10 000 queries: the union of the probed
     lists once (a lower bound);
-  * recall@10 against the exact search on benchdata's configs[2] rows (uniform: the worst case for IVF) and on a seeded
-    clustered set (benchdata.blobs).
+  * recall@10 against the exact search (HipVS.recall: the store's own comparison of its keys with the exact ones, on the
+    device) on benchdata's configs[2] rows (uniform: the worst case for IVF) and on a seeded clustered set (benchdata.blobs).
 The refined modes (sq8r, pqr: "...,Refine(Flat)" at --k-factor) run two timed kernels per call, the codes' scan at kc =
 refine_candidates(k) and lvs_refine_kernel; their kernel ms per call is the sum of both.  Beside it stands the plain store's
 search at K = kc (first_stage_kernel_ms: the same code and shape as the refined store's first stage), the difference
@@ -90,10 +90,6 @@ def columns(a, be, d, k, mode):
     return cols
 
 
-def recall(a, b):
-    return float(np.mean([len(set(x) & set(y)) / len(x) for x, y in zip(a, b)]))
-
-
 def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
     from lotus_amd import _capi
 
@@ -121,13 +117,13 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
         stores[name] = vs
     q1, qb = xq[:1], xq[:a.big]
     res["exact"] = {"q1": timed(exact, q1, k, a.reps1, 5), f"q{a.big}": timed(exact, qb, k, a.repsbig, 1)}
-    ref = exact(xq[:a.recall_queries], k).indices
     stored_row_bytes = d * (2 if storage == "fp16" else 4)
     row_bytes = {"pq": a.M, "sq8": d, "ivf_flat": stored_row_bytes, "pqr": a.M, "sq8r": d}
     for name, vs in stores.items():
         col = {}
         per_call = 2 if name in REFINED else 1
-        for nprobe in a.nprobe:
+        measured = vs.recall(xq[:a.recall_queries], k, nprobe=a.nprobe).intersection
+        for at, nprobe in enumerate(a.nprobe):
             r = {"q1": timed(vs, q1, k, a.reps1, 5, per_call, nprobe=nprobe),
                  f"q{a.big}": timed(vs, qb, k, a.repsbig, 1, per_call, nprobe=nprobe)}
             if name in REFINED:  # the plain store at K = kc is the refined store's first stage: the rest is the re-ranking
@@ -150,7 +146,7 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
             r[f"q{a.big}"]["query_row_pairs"] = pairs
             r[f"q{a.big}"]["union_rows"] = union
             r[f"q{a.big}"]["hbm_share"] = union * row_bytes[name] / HBM_BPS / (r[f"q{a.big}"]["kernel_ms"] * 1e-3)
-            r["recall10_uniform"] = recall(vs(xq[:a.recall_queries], k, nprobe=nprobe).indices, ref)
+            r["recall10_uniform"] = float(measured[at])
             r["speedup_q1_kernel_vs_exact"] = res["exact"]["q1"]["kernel_ms"] / r["q1"]["kernel_ms"]
             r[f"speedup_q{a.big}_kernel_vs_exact"] = res["exact"][f"q{a.big}"]["kernel_ms"] / r[f"q{a.big}"]["kernel_ms"]
             col[str(nprobe)] = r
@@ -160,15 +156,12 @@ def run_workload(d, storage, a, HipVS, benchdata, torch):  # noqa: C901
     if not a.skip_clustered:
         xc, _ = benchdata.blobs(benchdata.CFG_KMEANS, a.n, d, a.nlist, dtype=dtype)
         qc, _ = benchdata.queries(benchdata.CFG_KMEANS, xc, a.recall_queries, dtype=dtype)
-        exact = HipVS(storage=storage, device="cuda:0")
-        exact.index(None, xc, "bench-exact-c", persist=False)
-        ref = exact(qc, k).indices
-        del exact
         for name, kind in kinds.items():
             vs = HipVS(storage=storage, device="cuda:0", factory_string=f"IVF{a.nlist},{kind}", k_factor=a.k_factor)
             vs.index(None, xc, f"bench-{name}-c", persist=False)
-            for nprobe in a.nprobe:
-                res[name][str(nprobe)]["recall10_clustered"] = recall(vs(qc, k, nprobe=nprobe).indices, ref)
+            measured = vs.recall(qc, k, nprobe=a.nprobe).intersection
+            for at, nprobe in enumerate(a.nprobe):
+                res[name][str(nprobe)]["recall10_clustered"] = float(measured[at])
             del vs
         torch.cuda.empty_cache()
     return res
