@@ -954,9 +954,9 @@ int32_t search_two_phase(const SearchCall& sc, const uint32_t** pred) {
     search_tile_args(ta, sc, tp.a, gtau2, lists);
     ta.k = tp.slots;
     ta.no_share = 1;  // the bound needs every slab's own top list, not lists pruned by other slabs' thresholds
-    LVS_HIP_CHECK(hipMemsetAsync(gtau2, 0, (size_t)nq * 4, st));
-    LVS_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
-    LVS_HIP_CHECK(hipMemsetAsync(flag, 0, 4, st));
+    LVS_HIP_CHECK(lvs_zero_async(gtau2, (size_t)nq * 4, st));
+    LVS_HIP_CHECK(lvs_zero_async(cnt, (size_t)nq * 4, st));
+    LVS_HIP_CHECK(lvs_zero_async(flag, 4, st));
     {
         ScopedKernelTimer timer(st);
         LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOPK, ta, st));
@@ -1047,7 +1047,7 @@ int32_t search_rq_chunks(const SearchCall& sc, bool rq_join) {
                 LVS_HIP_CHECK(launch_seed_kth(seeds, rs.nparts, sn, k, gtau + c0 + s0, st));  // writes every gtau[q] of the piece
             }
         } else {
-            LVS_HIP_CHECK(hipMemsetAsync(gtau + c0, 0, (size_t)cn * 4, st));
+            LVS_HIP_CHECK(lvs_zero_async(gtau + c0, (size_t)cn * 4, st));
         }
         const int kernel = lvs_rq_chunk_kernel(cn, nb, p.dpad, k, sc.row_ids != nullptr);
         if (kernel != LVS_CHUNK_RQ) {
@@ -1127,7 +1127,7 @@ int32_t search_stream(const SearchCall& sc, const LvsStreamShape& sh) {
         LVS_HIP_CHECK(lvs_stream_launch(ss, st));
         LVS_HIP_CHECK(launch_seed_kth(seeds, ss.nparts, nq, k, gtau, st));  // writes every gtau[q]
     } else {
-        LVS_HIP_CHECK(hipMemsetAsync(gtau, 0, (size_t)nq * 4, st));
+        LVS_HIP_CHECK(lvs_zero_async(gtau, (size_t)nq * 4, st));
     }
     {
         ScopedKernelTimer timer(st, LVS_KERNEL_STREAM);
@@ -1191,7 +1191,7 @@ int32_t search_list_passes(const SearchCall& sc, const uint32_t* pred) {
             LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_SEED, sd, st));
             LVS_HIP_CHECK(launch_seed_kth(seeds, sd.nslab, nq, kp, gtau, st, a.kc, sc.qn, a.bscale, a.bslack));  // writes every gtau[q]
         } else {
-            LVS_HIP_CHECK(hipMemsetAsync(gtau, 0, (size_t)nq * 4, st));
+            LVS_HIP_CHECK(lvs_zero_async(gtau, (size_t)nq * 4, st));
         }
         if (pred) {  // predicated fallback pass: not a measurement of the dominant kernel
             LVS_HIP_CHECK(lvs_tile_launch(LVS_MODE_TOPK, a, st));
@@ -1253,7 +1253,7 @@ static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, con
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     if (nb == 0) {
-        LVS_HIP_CHECK(hipMemsetAsync(out_keys, 0, (size_t)nq * k * 8, st));
+        LVS_HIP_CHECK(lvs_zero_async(out_keys, (size_t)nq * k * 8, st));
         return LVS_OK;
     }
     LVS_REQUIRE(xb && xq, "NULL rows");
@@ -1792,7 +1792,7 @@ int32_t ivf_group_pairs(const LvsIvfPlan& L, char* w, const uint64_t* coarse, in
     const int32_t rc = lvs_bucket_positions(coarse, nullptr, npairs, nlist, 0, w + L.off_sort, L.sort_bytes, st, pairs, pair_offs);
     if (rc != LVS_OK) return rc;
     LVS_HIP_CHECK(lvs_ivf_tiles_launch(*pair_offs, nlist, (uint32_t*)(w + L.off_tiles), (uint32_t*)(w + L.off_items), st));
-    if (k > 0) LVS_HIP_CHECK(hipMemsetAsync(parts, 0, (size_t)npairs * k * 8, st));
+    if (k > 0) LVS_HIP_CHECK(lvs_zero_async(parts, (size_t)npairs * k * 8, st));
     return LVS_OK;
 }
 
@@ -1866,7 +1866,7 @@ extern "C" int32_t lvs_ivf_build_lists(const int64_t* assign, int64_t n, int32_t
     LVS_DEVICE_GUARD(stream);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        LVS_HIP_CHECK(hipMemsetAsync(out_offsets, 0, (size_t)(nlist + 1) * 8, st));
+        LVS_HIP_CHECK(lvs_zero_async(out_offsets, (size_t)(nlist + 1) * 8, st));
         return LVS_OK;
     }
     const uint32_t *rows = nullptr, *offs = nullptr;

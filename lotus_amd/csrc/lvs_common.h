@@ -213,6 +213,24 @@ struct LvsDeviceGuard {
     LvsDeviceGuard _lvs_guard((hipStream_t)(stream)); \
     LVS_HIP_CHECK(_lvs_guard.err)
 
+// ---- zeroing scratch on the stream -------------------------------------------------------------------------
+// A kernel of the library's own instead of hipMemsetAsync: in a captured graph hipMemsetAsync becomes a memset node, and from the
+// graph's second launch on such a node has been seen (ROCm 7.0, gfx950) to leave part of the buffer non-zero for the kernel behind
+// it - thresholds that reject every row, whole result lists empty (tests/test_gpu_stream_contract.py,
+// profiles/stream_contract_check.md).  A kernel node replays like any launch.  p and bytes: multiples of 4.
+template <int THREADS>
+__global__ void lvs_zero_kernel(uint32_t* p, long long words) {
+    for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < words; i += (long long)gridDim.x * THREADS) p[i] = 0u;
+}
+inline hipError_t lvs_zero_async(void* p, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return hipSuccess;
+    if ((bytes & 3) || ((uintptr_t)p & 3)) return hipErrorInvalidValue;
+    const long long words = (long long)(bytes >> 2);
+    const long long blocks = (words + 255) / 256;
+    hipLaunchKernelGGL(lvs_zero_kernel<256>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (uint32_t*)p, words);
+    return hipGetLastError();
+}
+
 // ---- dynamic-LDS launches ----------------------------------------------------------------------------------
 // More than 64 KB of dynamic LDS needs hipFuncSetAttribute(MaxDynamicSharedMemorySize), a per-device property of a kernel.
 // lvs_arm_lds keeps one latch per kernel instantiation: which devices have the attribute (bit per device id) and for how

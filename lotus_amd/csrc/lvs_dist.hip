@@ -147,7 +147,7 @@ extern "C" int32_t lvs_search_sharded(lvs_all_gather_fn all_gather, void* all_ga
         if (rc != LVS_OK) return rc;
     } else {
         LVS_DEVICE_GUARD(stream);
-        LVS_HIP_CHECK(hipMemsetAsync(keys_local, 0, (size_t)nq * k * 8, st));
+        LVS_HIP_CHECK(lvs_zero_async(keys_local, (size_t)nq * k * 8, st));
     }
     if (nranks == 1) return LVS_OK;
     // 3. one all-gather of the [nq][k] key lists, merged per query on every rank

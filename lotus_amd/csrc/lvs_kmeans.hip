@@ -355,7 +355,7 @@ int32_t km_pack_and_stats(const float* centroids, int32_t k, int32_t d, int32_t 
     if (stats_out) {
         const int dpad = (int)lvs_round_up(d, LVS_BK);
         const int split = pack_mode == LVS_PACK_SPLIT;
-        LVS_HIP_CHECK(hipMemsetAsync(stats_out, 0, 2 * sizeof(float), st));
+        LVS_HIP_CHECK(lvs_zero_async(stats_out, 2 * sizeof(float), st));
         hipLaunchKernelGGL(km_stats_kernel, dim3((unsigned)lvs_ceil_div(k, 4)), dim3(256), 0, st, (const _Float16*)packed_out,
                            (long long)(split ? 2 * dpad : dpad), dpad, split, (const float*)norms_out, k, stats_out);
         LVS_HIP_CHECK(hipGetLastError());

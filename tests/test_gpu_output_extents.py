@@ -269,7 +269,7 @@ def raw_iteration(be, pool, n=20_001, d=64, K=12):
                                   P(cent), SPLIT, P(rows), P(norms), P(cstats), P(keys), P(obj), P(nsplit),
                                   ctypes.addressof(host_counts), P(ws), nbytes, be._stream())
     raw = Raw(need, run, [keys, obj, nsplit], "lvs_kmeans_iteration")
-    raw.extra = dict(p=p, x=x, cent_h=cent_h, cent=cent, reset=reset, K=K)
+    raw.extra = dict(p=p, x=x, cent_h=cent_h, cent=cent, reset=reset, K=K, x2=x2, rows=rows, norms=norms, cstats=cstats)
     return raw
 
 
