@@ -57,7 +57,7 @@ extern "C" {
                                 lvs_ivf_pq_search_keys_sel) - the plain entries are these with sel_bits = NULL; the threshold
                                 search through the lists (lvs_ivf_range_workspace_bytes, lvs_ivf_range_search,
                                 LVS_KERNEL_IVF_RANGE); recall measurement on resident keys (lvs_keys_overlap, lvs_ivf_row_lists,
-                                lvs_ivf_probe_ranks) */
+                                lvs_ivf_probe_ranks); the one-pass bound's coefficients on the host (lvs_nearest_bound_coef) */
 
 #define LVS_OK 0
 #define LVS_EINVAL (-1)   /* bad argument */
@@ -330,6 +330,11 @@ int32_t lvs_margin_select(const uint64_t* keys, const float* second, const float
 int32_t lvs_margin_select_stats(const uint64_t* keys, const float* second, const float* q_norms_sq, int64_t nq,
                                 const float* corpus_stats, const float* coef5, int64_t* out_idx, uint64_t* out_count,
                                 void* stream);
+/* out_coef5 [5] (host floats): the coefficients of that bound for a one-pass search (lvs_nearest_hi, lvs_nearest3) under
+ * `metric` with queries packed as xq_pack, rows of d elements, exp_sum = the two operands' pack exponents added: computed in
+ * double and rounded once (lotus_amd/csrc/lvs_bound.h states them; lvs_kmeans_iteration uses the same).  Host only: touches no
+ * device.  LVS_EINVAL for an unknown metric or pack mode, d <= 0 or a NULL output. */
+int32_t lvs_nearest_bound_coef(int32_t metric, int32_t xq_pack, int32_t d, int32_t exp_sum, float* out_coef5);
 int64_t lvs_kmeans_accumulate_workspace_bytes(int64_t n, int32_t k);
 /* sums [k][d] float32: the packed rows of x, grouped by assign[i] (int64, values outside [0,k) are skipped), are added to
  * what is there, one after the other in row order per centroid (faiss compute_centroids order) - the chain of float32

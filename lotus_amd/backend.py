@@ -611,6 +611,18 @@ class HipBackend:
             for name, v in counts.items():
                 stats[name] = stats.get(name, 0) + v
 
+    def _cert_bound(self, corpus, queries, metric):
+        """-> (scale, slack), Python floats (float64): the certified top-k search's error bound is scale |q| + slack."""
+        # |s - s_hi| <= |q| |lo_row| + |lo_q| |row| + |lo_q| |lo_row| (Cauchy-Schwarz) with the MEASURED largest lo-part norms
+        # E_c, E_q of the two operands (cached per device image; ~0.4 x the worst case 2^-11 |x|, so fewer queries stay open than
+        # under round 3's a-priori bound; being measured, they also cover components in fp16's subnormal range), + float32
+        # accumulation noise relative to |q| |row|
+        R, E_c, E_q = self.row_norm_max(corpus), self.lo_norm_max(corpus), self.lo_norm_max(queries)
+        c = 1.0 if metric == _capi.METRIC_IP else 2.0
+        scale = c * (E_c * (1.0 + 1e-3) + 8e-6 * R)
+        slack = 1e-6 * (2.0 ** (corpus.exp + queries.exp) + R * R) + c * E_q * (R + E_c) * (1.0 + 1e-3)
+        return scale, slack
+
     def _search_keys_certified(self, corpus, queries, k, metric, id_offset, stats, k1=None):
         """Exact top-k of fp32-accurate operands from one MFMA pass (see ``search_keys``).
 
@@ -627,15 +639,7 @@ class HipBackend:
             # of deeper lists is 25-45 % slower - a few more open queries for the second round are the smaller price
             k1 = min(15, k + self.CERT_SPARE_SMALL_K) if k <= 10 else (15 if k <= self.CERT_MAX_K_SMALL_LISTS else min(56, k + 8))
         k1 = min(k1, corpus.n)
-        # |s - s_hi| <= |q| |lo_row| + |lo_q| |row| + |lo_q| |lo_row| (Cauchy-Schwarz) with the MEASURED largest lo-part norms
-        # E_c, E_q of the two operands (cached per device image; ~0.4 x the worst case 2^-11 |x|, so fewer queries stay open than
-        # under round 3's a-priori bound; being measured, they also cover components in fp16's subnormal range), + float32
-        # accumulation noise relative to |q| |row|
-        R = self.row_norm_max(corpus)
-        E_c, E_q = self.lo_norm_max(corpus), self.lo_norm_max(queries)
-        c = 1.0 if metric == _capi.METRIC_IP else 2.0
-        scale = c * (E_c * (1.0 + 1e-3) + 8e-6 * R)
-        slack = 1e-6 * (2.0 ** (corpus.exp + queries.exp) + R * R) + c * E_q * (R + E_c) * (1.0 + 1e-3)
+        scale, slack = self._cert_bound(corpus, queries, metric)
         # BANDED lists: with bound = scale |q| + slack, a row whose one-pass score is more than 2 bound below the k-th best
         # one-pass score cannot reach the exact top k (k-th exact >= k-th one-pass - bound).  So the kernel admits a row only
         # above max(last slot, k-th slot - CERT_BAND_SEARCH x bound): the k1-deep lists then cost the insertions of k-deep
@@ -713,13 +717,8 @@ class HipBackend:
         keys = torch.empty((nq, 1), dtype=torch.int64, device=self.device)
         if nq == 0 or corpus.n == 0:
             return self.search_keys(corpus, queries, 1, metric, id_offset=id_offset, one_pass=False)
-        # error bound per unit of |q|: E = largest lo-part norm and R = largest norm over the corpus rows (a small matrix in
-        # the k-means use: the centroids).  bound = scale |q| + slack with
-        #   scale = c (E + 2^-11 R [queries split] + 8e-6 R) + 2^-16 cm R     (c = 2 / 4, cm = 1 / 2 for IP / L2; 8e-6: fp32
-        #   slack = 1e-6 (1 + R^2) + [L2] 2^-16 R^2 + [queries split] c sqrt(d) 2^-25 R      accumulation noise of both searches)
-        # lvs_nearest_hi tags every running score in its low six mantissa bits (relative perturbation < 2^-17 of u = q.y or
-        # 2 q.y - |y|^2, for the winner and for the runner-up): the 2^-16 terms.  |lo_q| <= 2^-11 |q| + sqrt(d) 2^-25: the
-        # second term covers components in fp16's subnormal range.
+        # bound = (coef[0] E + coef[1] R) |q| + coef[2] + coef[3] R + coef[4] R^2 (E = largest lo-part norm, R = largest norm over
+        # the corpus rows): derived where the library states it, csrc/lvs_bound.h
         coef, dpad = self._nearest_coef(corpus, queries, metric)
         if bounds is not None:
             bounds = _Bounds(self, bounds, corpus_stats, coef, id_offset)
@@ -774,15 +773,11 @@ class HipBackend:
 
     @staticmethod
     def _nearest_coef(corpus, queries, metric):
-        """-> (the five coefficients of the one-pass error bound - see the comment in ``nearest`` -, dpad)."""
-        dpad = int(corpus.rows.shape[1]) // (2 if corpus.mode == _capi.PACK_SPLIT else 1)
-        qsplit = 1.0 if queries.mode == _capi.PACK_SPLIT else 0.0
-        ip = metric == _capi.METRIC_IP
-        c = 2.0 if ip else 4.0
-        coef = [c, c * ((2.0 ** -11) * qsplit + 8e-6) + 2.0 ** -16 * (1.0 if ip else 2.0),
-                1e-6 * 2.0 ** (corpus.exp + queries.exp), qsplit * c * (dpad ** 0.5) * 2.0 ** -25,
-                1e-6 + (0.0 if ip else 2.0 ** -16)]
-        return coef, dpad
+        """-> (the five coefficients of the one-pass error bound, stated in ``csrc/lvs_bound.h``, dpad).  Needs no device."""
+        coef5 = (ctypes.c_float * 5)()
+        _capi.check(_capi.load().lvs_nearest_bound_coef(int(metric), queries.mode, corpus.d, corpus.exp + queries.exp,
+                                                        ctypes.addressof(coef5)), "lvs_nearest_bound_coef")
+        return list(coef5), int(corpus.rows.shape[1]) // (2 if corpus.mode == _capi.PACK_SPLIT else 1)
 
     def _nearest3_step(self, corpus) -> int:
         """Most queries one ``lvs_nearest3`` call may take inside the scratch budget (20 B per corpus tile and query)."""

@@ -17,6 +17,7 @@
 // search over every row.
 #include <string.h>
 
+#include "lvs_certify.h"
 #include "lvs_common.h"
 #include "lvs_kstep.h"
 #include "lvs_tile.h"
@@ -313,9 +314,6 @@ __global__ __launch_bounds__(256) void assign_merge_kernel(const u64* __restrict
     third[q] = T;
 }
 
-struct Coef5 {
-    float c[5];
-};
 // Three-way certificate of a one-pass nearest-row search.  bound(q) = (c0 E + c1 R) |q| + c2 + c3 R + c4 R^2 (R, E: largest
 // row norm / lo-part norm of the corpus, from `stats`), as lvs_margin_select_stats:
 //   best - second > bound            certified: the one-pass winner is the exact winner;
@@ -325,16 +323,11 @@ struct Coef5 {
 __global__ __launch_bounds__(256) void nearest3_select_kernel(const u64* __restrict__ keys1, const u64* __restrict__ keys2,
                                                               const float* __restrict__ second, const float* __restrict__ third,
                                                               const float* __restrict__ qn, long long nq,
-                                                              const float* __restrict__ stats, Coef5 coef, long long per_block,
+                                                              const float* __restrict__ stats, LvsBoundCoef coef, long long per_block,
                                                               long long* __restrict__ pair_idx, long long* __restrict__ open_idx,
                                                               unsigned long long* __restrict__ counts) {
-    const float R = sqrtf(stats[0]), E = sqrtf(stats[1]);
-    const float scale = coef.c[0] * E + coef.c[1] * R;
-    const float slack = coef.c[2] + coef.c[3] * R + coef.c[4] * R * R;
-    __shared__ unsigned long long s_base[2];
-    __shared__ unsigned s_count[2];
-    const long long q_begin = (long long)blockIdx.x * per_block;
-    const long long q_end = q_begin + per_block < nq ? q_begin + per_block : nq;
+    const LvsBound b(coef, stats);
+    const float scale = b.scale(), slack = b.slack();
     auto classify = [&](long long q) -> int {  // 0 certified, 1 pair, 2 open
         const u64 kq = keys1[q];
         if (!kq) return 0;
@@ -344,32 +337,13 @@ __global__ __launch_bounds__(256) void nearest3_select_kernel(const u64* __restr
         if (keys2[q] && (best - third[q]) > bound) return 1;
         return 2;
     };
-    if (threadIdx.x < 2) s_count[threadIdx.x] = 0;
-    __syncthreads();
-    unsigned mine[2] = {0, 0};
-    for (long long q = q_begin + threadIdx.x; q < q_end; q += blockDim.x) {
-        const int c = classify(q);
-        if (c) ++mine[c - 1];
-    }
-    if (mine[0]) atomicAdd(&s_count[0], mine[0]);
-    if (mine[1]) atomicAdd(&s_count[1], mine[1]);
-    __syncthreads();
-    if (s_count[0] == 0 && s_count[1] == 0) return;
-    if (threadIdx.x < 2) {
-        s_base[threadIdx.x] = s_count[threadIdx.x] ? atomicAdd(&counts[threadIdx.x], (unsigned long long)s_count[threadIdx.x]) : 0ull;
-        s_count[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    for (long long q = q_begin + threadIdx.x; q < q_end; q += blockDim.x) {
-        const int c = classify(q);
-        if (c == 1) pair_idx[s_base[0] + atomicAdd(&s_count[0], 1u)] = q;
-        if (c == 2) open_idx[s_base[1] + atomicAdd(&s_count[1], 1u)] = q;
-    }
+    long long* const out[2] = {pair_idx, open_idx};
+    lvs_append_lists<2>(per_block, nq, classify, classify, out, counts);
 }
 
-typedef _Float16 as_half8 __attribute__((ext_vector_type(8)));
 // one wave per listed query: exact (hi + lo of both operands, float32) scores of the query against the rows named by
-// keys1[q] and keys2[q]; the better key (score, then lower id) replaces keys1[q].  Same arithmetic as rescore_keys_kernel.
+// keys1[q] and keys2[q]; the better key (score, then lower id) replaces keys1[q].  rescore_keys_kernel's arithmetic
+// (lvs_exact_dots, lvs_l2_score).
 template <int QSPLIT, int BSPLIT>
 __global__ __launch_bounds__(256) void resolve_pairs_kernel(const _Float16* __restrict__ xb, long long ldb,
                                                             const _Float16* __restrict__ xq, long long ldq, int dpad, int metric,
@@ -389,29 +363,12 @@ __global__ __launch_bounds__(256) void resolve_pairs_kernel(const _Float16* __re
     const _Float16* qr = xq + q * ldq;
     const _Float16* ar = xb + ra * ldb;
     const _Float16* br = xb + rb * ldb;
-    float sa = 0.f, sb = 0.f;
-    for (int j = lane * 8; j < dpad; j += 512) {
-        const as_half8 qh = *(const as_half8*)(qr + j), ah = *(const as_half8*)(ar + j), bh = *(const as_half8*)(br + j);
-        as_half8 ql, al, bl;
-        if (QSPLIT) ql = *(const as_half8*)(qr + dpad + j);
-        if (BSPLIT) {
-            al = *(const as_half8*)(ar + dpad + j);
-            bl = *(const as_half8*)(br + dpad + j);
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float x = (float)qh[t] + (QSPLIT ? (float)ql[t] : 0.f);
-            sa += x * ((float)ah[t] + (BSPLIT ? (float)al[t] : 0.f));
-            sb += x * ((float)bh[t] + (BSPLIT ? (float)bl[t] : 0.f));
-        }
-    }
-    sa = lvs_wave_sum(sa);
-    sb = lvs_wave_sum(sb);
+    const LvsDots s = lvs_exact_dots<QSPLIT, BSPLIT, 2>(qr, ar, br, dpad, lane);
     if (lane == 0) {
-        float fa = sa, fb = sb;
+        float fa = s.a, fb = s.b;
         if (metric == LVS_METRIC_L2) {
-            fa = -fmaxf((qn[q] + bn[ra]) - 2.0f * sa, 0.f);
-            fb = -fmaxf((qn[q] + bn[rb]) - 2.0f * sb, 0.f);
+            fa = lvs_l2_score(qn[q], bn[ra], s.a);
+            fb = lvs_l2_score(qn[q], bn[rb], s.b);
         }
         const u64 na = lvs_pack_key(fa, ida), nb_ = lvs_pack_key(fb, idb);
         keys1[q] = na > nb_ ? na : nb_;
@@ -530,14 +487,13 @@ extern "C" int32_t lvs_nearest3_select(const uint64_t* keys, const uint64_t* key
     LVS_REQUIRE(nq >= 0 && corpus_stats && coef5, "bad arguments");
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(keys && keys2 && second && third && out_pair_idx && out_open_idx && out_counts, "NULL buffer");
-    Coef5 c;
+    LvsBoundCoef c;
     for (int i = 0; i < 5; ++i) {
         LVS_REQUIRE(coef5[i] >= 0.f, "negative coefficient");
         c.c[i] = coef5[i];
     }
     LVS_DEVICE_GUARD(stream);
-    long long per_block = lvs_ceil_div(nq, 2048);
-    per_block = lvs_round_up(per_block < 1024 ? 1024 : per_block, 256);
+    const long long per_block = lvs_append_per_block(nq);
     hipLaunchKernelGGL(nearest3_select_kernel, dim3((unsigned)lvs_ceil_div(nq, per_block)), dim3(256), 0, (hipStream_t)stream,
                        (const u64*)keys, (const u64*)keys2, second, third, q_norms_sq, (long long)nq, corpus_stats, c, per_block,
                        (long long*)out_pair_idx, (long long*)out_open_idx, (unsigned long long*)out_counts);
@@ -561,15 +517,11 @@ extern "C" int32_t lvs_resolve_pairs(const void* xb, int32_t xb_pack, const void
     const long long ldb = l.ldb, ldq = l.ldq;
     const dim3 grid((unsigned)lvs_ceil_div(capacity, 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-#define LVS_RESOLVE(QS, BS)                                                                                                  \
-    hipLaunchKernelGGL((resolve_pairs_kernel<QS, BS>), grid, block, 0, st, (const _Float16*)xb, ldb, (const _Float16*)xq, ldq,  \
-                       dpad, metric, xb_norms_sq, xq_norms_sq, (long long)id_offset, (const long long*)pair_idx,               \
-                       (const unsigned long long*)pair_count, (long long)capacity, (u64*)keys, (const u64*)keys2)
-    if (xq_pack == LVS_PACK_SPLIT && xb_pack == LVS_PACK_SPLIT) LVS_RESOLVE(1, 1);
-    else if (xq_pack == LVS_PACK_SPLIT) LVS_RESOLVE(1, 0);
-    else if (xb_pack == LVS_PACK_SPLIT) LVS_RESOLVE(0, 1);
-    else LVS_RESOLVE(0, 0);
-#undef LVS_RESOLVE
+    lvs_split_dispatch(xq_pack, xb_pack, [&](auto qs, auto bs) {
+        hipLaunchKernelGGL((resolve_pairs_kernel<qs(), bs()>), grid, block, 0, st, (const _Float16*)xb, ldb, (const _Float16*)xq, ldq,
+                           dpad, metric, xb_norms_sq, xq_norms_sq, (long long)id_offset, (const long long*)pair_idx,
+                           (const unsigned long long*)pair_count, (long long)capacity, (u64*)keys, (const u64*)keys2);
+    });
     LVS_HIP_CHECK(hipGetLastError());
     return LVS_OK;
 }

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 
+#include "lvs_certify.h"
 #include "lvs_common.h"
 #include "lvs_count_sort.h"
 #include "lvs_tile.h"
@@ -207,7 +208,6 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const SrcT* __restrict__
     pack_report(bad, flags);
 }
 
-typedef _Float16 pk_half8 __attribute__((ext_vector_type(8)));
 typedef float pk_float4 __attribute__((ext_vector_type(4)));
 
 __device__ inline void pack_load8(const float* s, float (&v)[8]) {
@@ -219,7 +219,7 @@ __device__ inline void pack_load8(const float* s, float (&v)[8]) {
     }
 }
 __device__ inline void pack_load8(const _Float16* s, float (&v)[8]) {
-    pk_half8 a = *(const pk_half8*)s;
+    half8 a = *(const half8*)s;
 #pragma unroll
     for (int t = 0; t < 8; ++t) v[t] = (float)a[t];
 }
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256) void pack_rows_vec_kernel(const SrcT* __restri
 #pragma unroll
             for (int t = 0; t < 8; ++t) v[t] = 0.f;
         }
-        pk_half8 hi, lo;
+        half8 hi, lo;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             float x = (v[t] * scale) * pw;  // pw is a power of two: exact
@@ -269,8 +269,8 @@ __global__ __launch_bounds__(256) void pack_rows_vec_kernel(const SrcT* __restri
             }
             nn += stored * stored;
         }
-        *(pk_half8*)(o + j) = hi;
-        if (SPLIT) *(pk_half8*)(o + dpad + j) = lo;
+        *(half8*)(o + j) = hi;
+        if (SPLIT) *(half8*)(o + dpad + j) = lo;
     }
     if (norms) {
         nn = lvs_wave_sum(nn);
@@ -450,23 +450,10 @@ __global__ __launch_bounds__(256) void rescore_keys_kernel(const _Float16* __res
     const long long row = (long long)id - id_offset;
     const _Float16* qr = xq + q * ldq;
     const _Float16* br = xb + row * ldb;
-    float acc = 0.f;
-    for (int j = lane * 8; j < dpad; j += 512) {
-        const pk_half8 qh = *(const pk_half8*)(qr + j), bh = *(const pk_half8*)(br + j);
-        pk_half8 ql, bl;
-        if (QSPLIT) ql = *(const pk_half8*)(qr + dpad + j);
-        if (BSPLIT) bl = *(const pk_half8*)(br + dpad + j);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float a = (float)qh[t] + (QSPLIT ? (float)ql[t] : 0.f);
-            const float b = (float)bh[t] + (BSPLIT ? (float)bl[t] : 0.f);
-            acc += a * b;
-        }
-    }
-    acc = lvs_wave_sum(acc);
+    const float acc = lvs_exact_dots<QSPLIT, BSPLIT, 1>(qr, br, nullptr, dpad, lane).a;
     if (lane == 0) {
         float better = acc;
-        if (metric == LVS_METRIC_L2) better = -fmaxf((qn[q] + bn[row]) - 2.0f * acc, 0.f);
+        if (metric == LVS_METRIC_L2) better = lvs_l2_score(qn[q], bn[row], acc);
         keys[slot] = lvs_pack_key(better, id);
     }
 }
@@ -526,47 +513,26 @@ __global__ __launch_bounds__(256) void certify_topk_kernel(const u64* __restrict
 // With `stats` (device: [0] = R^2 largest squared row norm, [1] = E^2 largest squared lo-part norm of the corpus rows) the
 // bound is (coef[0] E + coef[1] R) |q| + coef[2] + coef[3] R + coef[4] R^2 - the k-means loop keeps those statistics on the
 // device (lvs_kmeans_update_centroids) so that no iteration waits for the host; without it: scale |q| + slack.
-struct MarginCoef {
-    float c[5];
-};
+// One workgroup owns `per_block` consecutive queries (lvs_append_lists).
 __global__ __launch_bounds__(256) void margin_select_kernel(const u64* __restrict__ keys, const float* __restrict__ sec,
                                                             const float* __restrict__ qn, long long nq, float scale,
-                                                            float slack, const float* __restrict__ stats, MarginCoef coef,
+                                                            float slack, const float* __restrict__ stats, LvsBoundCoef coef,
                                                             long long per_block, long long* __restrict__ out_idx,
                                                             unsigned long long* __restrict__ out_count) {
     if (stats) {
-        const float R = sqrtf(stats[0]), E = sqrtf(stats[1]);
-        scale = coef.c[0] * E + coef.c[1] * R;
-        slack = coef.c[2] + coef.c[3] * R + coef.c[4] * R * R;
+        const LvsBound b(coef, stats);
+        scale = b.scale();
+        slack = b.slack();
     }
-    // One workgroup owns `per_block` consecutive queries: it counts its uncertified ones, reserves their output range
-    // with ONE atomic (10 M queries at 0.4 % uncertified were 30 000 same-address atomics = 1.2 ms when every wave
-    // reserved its own), then writes them in a second sweep over the same 16 bytes per query.
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned s_count;
-    const long long q_begin = (long long)blockIdx.x * per_block;
-    const long long q_end = q_begin + per_block < nq ? q_begin + per_block : nq;
-    auto is_open = [&](long long q) {
+    auto is_open = [&](long long q) -> int {
         const u64 kq = keys[q];
-        if (!kq) return false;
+        if (!kq) return 0;
         const float best = lvs_unord32((uint32_t)(kq >> 32));
         const float bound = scale * sqrtf(qn ? qn[q] : 1.0f) + slack;
         return !((best - sec[q]) > bound);  // also true for NaN / inf - inf: never certify what cannot be compared
     };
-    if (threadIdx.x == 0) s_count = 0;
-    __syncthreads();
-    unsigned mine = 0;
-    for (long long q = q_begin + threadIdx.x; q < q_end; q += blockDim.x) mine += is_open(q) ? 1u : 0u;
-    if (mine) atomicAdd(&s_count, mine);
-    __syncthreads();
-    if (s_count == 0) return;
-    if (threadIdx.x == 0) {
-        s_base = atomicAdd(out_count, (unsigned long long)s_count);
-        s_count = 0;
-    }
-    __syncthreads();
-    for (long long q = q_begin + threadIdx.x; q < q_end; q += blockDim.x)
-        if (is_open(q)) out_idx[s_base + atomicAdd(&s_count, 1u)] = q;
+    long long* const out[1] = {out_idx};
+    lvs_append_lists<1>(per_block, nq, is_open, is_open, out, out_count);
 }
 
 }  // namespace
@@ -1415,14 +1381,11 @@ extern "C" int32_t lvs_rescore_keys(const void* xb, int32_t xb_pack, const void*
     LVS_DEVICE_GUARD(stream);
     const dim3 grid((unsigned)lvs_ceil_div(nq * k, 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-#define LVS_RESCORE(QS, BS)                                                                                              \
-    hipLaunchKernelGGL((rescore_keys_kernel<QS, BS>), grid, block, 0, st, (const _Float16*)xb, (long long)l.ldb, (const _Float16*)xq, \
-                       (long long)l.ldq, l.dpad, metric, xb_norms_sq, xq_norms_sq, (long long)id_offset, (long long)nq, (int)k, (u64*)keys)
-    if (xq_pack == LVS_PACK_SPLIT && xb_pack == LVS_PACK_SPLIT) LVS_RESCORE(1, 1);
-    else if (xq_pack == LVS_PACK_SPLIT) LVS_RESCORE(1, 0);
-    else if (xb_pack == LVS_PACK_SPLIT) LVS_RESCORE(0, 1);
-    else LVS_RESCORE(0, 0);
-#undef LVS_RESCORE
+    lvs_split_dispatch(xq_pack, xb_pack, [&](auto qs, auto bs) {
+        hipLaunchKernelGGL((rescore_keys_kernel<qs(), bs()>), grid, block, 0, st, (const _Float16*)xb, (long long)l.ldb,
+                           (const _Float16*)xq, (long long)l.ldq, l.dpad, metric, xb_norms_sq, xq_norms_sq, (long long)id_offset,
+                           (long long)nq, (int)k, (u64*)keys);
+    });
     LVS_HIP_CHECK(hipGetLastError());
     return LVS_OK;
 }
@@ -1487,14 +1450,12 @@ extern "C" int32_t lvs_certify_topk(const uint64_t* approx_keys, const uint64_t*
 }
 
 static int32_t margin_select_launch(const uint64_t* keys, const float* second, const float* q_norms_sq, int64_t nq, float scale,
-                                    float slack, const float* stats, const MarginCoef& coef, int64_t* out_idx,
+                                    float slack, const float* stats, const LvsBoundCoef& coef, int64_t* out_idx,
                                     uint64_t* out_count, void* stream) {
     if (nq == 0) return LVS_OK;
     LVS_REQUIRE(keys && second && out_idx && out_count, "NULL buffer");
     LVS_DEVICE_GUARD(stream);
-    // at most 2048 workgroups, each at least 1024 queries
-    long long per_block = lvs_ceil_div(nq, 2048);
-    per_block = lvs_round_up(per_block < 1024 ? 1024 : per_block, 256);
+    const long long per_block = lvs_append_per_block(nq);
     hipLaunchKernelGGL(margin_select_kernel, dim3((unsigned)lvs_ceil_div(nq, per_block)), dim3(256), 0, (hipStream_t)stream,
                        (const u64*)keys, second, q_norms_sq, (long long)nq, scale, slack, stats, coef, per_block,
                        (long long*)out_idx, (unsigned long long*)out_count);
@@ -1505,7 +1466,7 @@ static int32_t margin_select_launch(const uint64_t* keys, const float* second, c
 extern "C" int32_t lvs_margin_select(const uint64_t* keys, const float* second, const float* q_norms_sq, int64_t nq,
                                      float scale, float slack, int64_t* out_idx, uint64_t* out_count, void* stream) {
     LVS_REQUIRE(nq >= 0 && scale >= 0.f && slack >= 0.f, "bad arguments");
-    return margin_select_launch(keys, second, q_norms_sq, nq, scale, slack, nullptr, MarginCoef{{0, 0, 0, 0, 0}}, out_idx,
+    return margin_select_launch(keys, second, q_norms_sq, nq, scale, slack, nullptr, LvsBoundCoef{{0, 0, 0, 0, 0}}, out_idx,
                                 out_count, stream);
 }
 
@@ -1513,12 +1474,18 @@ extern "C" int32_t lvs_margin_select_stats(const uint64_t* keys, const float* se
                                            const float* corpus_stats, const float* coef5, int64_t* out_idx,
                                            uint64_t* out_count, void* stream) {
     LVS_REQUIRE(nq >= 0 && corpus_stats && coef5, "bad arguments");
-    MarginCoef c;
+    LvsBoundCoef c;
     for (int i = 0; i < 5; ++i) {
         LVS_REQUIRE(coef5[i] >= 0.f, "negative coefficient");
         c.c[i] = coef5[i];
     }
     return margin_select_launch(keys, second, q_norms_sq, nq, 0.f, 0.f, corpus_stats, c, out_idx, out_count, stream);
+}
+
+extern "C" int32_t lvs_nearest_bound_coef(int32_t metric, int32_t xq_pack, int32_t d, int32_t exp_sum, float* out_coef5) {
+    LVS_REQUIRE(out_coef5 && lvs_nearest_bound_coef(metric, xq_pack, d, exp_sum, *(LvsBoundCoef*)out_coef5) == LVS_OK,
+                "bad arguments metric=%d pack=%d d=%d (or a NULL output)", metric, xq_pack, d);
+    return LVS_OK;
 }
 
 extern "C" int32_t lvs_merge_keys(const uint64_t* parts, int32_t nparts, int64_t nq, int32_t k, uint64_t* out_keys,

@@ -16,6 +16,7 @@
 #include <random>
 #include <vector>
 
+#include "lvs_certify.h"
 #include "lvs_common.h"
 #include "lvs_count_sort.h"
 #include "lvs_tile.h"
@@ -435,10 +436,13 @@ __global__ __launch_bounds__(256) void km_bounds_set_kernel(const u64* __restric
                                                             float* __restrict__ ub, float* __restrict__ lb) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const float R = sqrtf(stats[0]), E = sqrtf(stats[1]);
+    // (five scalar parameters here and in km_bounds_fix_kernel: with the struct as the parameter the compiler sums err1 of the
+    // fix kernel in another order and lb moves in its last bit, profiles/certify_refactor_check.md)
+    const LvsBoundCoef coef{{c0, c1, c2, c3, c4}};
+    const LvsBound b(coef, stats);
     const long long row = pos ? pos[i] : i;
     const u64 kq = keys[i * key_stride];
-    const float err = (c0 * E + c1 * R) * sqrtf(qn[i]) + c2 + c3 * R + c4 * R * R;
+    const float err = b.at(sqrtf(qn[i]));
     const float d1 = kq ? fmaxf(-lvs_unord32((uint32_t)(kq >> 32)), 0.f) : 3.0e38f;
     const float s2 = second ? second[i] : lvs_unord32((uint32_t)(keys[i * key_stride + 1] >> 32));
     const float d2 = fmaxf(-s2, 0.f);  // -inf runner-up (a single centroid) -> +inf
@@ -458,13 +462,14 @@ __global__ __launch_bounds__(256) void km_bounds_fix_kernel(const u64* __restric
                                                             float* __restrict__ lb) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const float R = sqrtf(stats[0]), E = sqrtf(stats[1]);
+    const LvsBoundCoef coef{{c0, c1, c2, c3, c4}};
+    const LvsBound b(coef, stats);
     const long long row = pos ? pos[i] : i;
     const u64 ka = approx[i], ke = exact[i];
     if (!ke) return;
     const float qnorm = sqrtf(qn[i]);
-    const float err1 = (c0 * E + c1 * R) * qnorm + c2 + c3 * R + c4 * R * R;  // the one-pass search's error bound
-    const float err2 = e1 * R * qnorm + e4 * R * R;                           // float32 rounding of the exact distance
+    const float err1 = b.at(qnorm);                        // the one-pass search's error bound
+    const float err2 = e1 * b.R * qnorm + e4 * b.R * b.R;  // float32 rounding of the exact distance
     const float d1e = fmaxf(-lvs_unord32((uint32_t)(ke >> 32)), 0.f);
     assign[row] = (int)((long long)(0xFFFFFFFFu - (uint32_t)(ke & 0xFFFFFFFFull)) - id_offset);
     ub[row] = sqrtf(d1e + err2) * (1.0f + 1e-6f);
@@ -479,16 +484,9 @@ __global__ __launch_bounds__(256) void km_bounds_step_kernel(const int* __restri
                                                              const float* __restrict__ top2, long long n, long long per_block,
                                                              long long* __restrict__ out_idx,
                                                              unsigned long long* __restrict__ out_count) {
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned s_count;
     const float g1 = top2[0], g2 = top2[2];
     const int gi = __float_as_int(top2[1]);
-    const long long q_begin = (long long)blockIdx.x * per_block;
-    const long long q_end = q_begin + per_block < n ? q_begin + per_block : n;
-    if (threadIdx.x == 0) s_count = 0;
-    __syncthreads();
-    unsigned mine = 0;
-    for (long long q = q_begin + threadIdx.x; q < q_end; q += blockDim.x) {
+    auto move = [&](long long q) -> int {  // the first sweep is the one read-modify-write pass over the bounds
         const int a = assign[q];
         float u = ub[q], l = lb[q];
         if (a >= 0) {
@@ -497,20 +495,11 @@ __global__ __launch_bounds__(256) void km_bounds_step_kernel(const int* __restri
         }
         ub[q] = u;
         lb[q] = l;
-        mine += (a < 0 || !(u * (1.0f + 1e-5f) < l)) ? 1u : 0u;
-    }
-    if (mine) atomicAdd(&s_count, mine);
-    __syncthreads();
-    if (s_count == 0) return;
-    if (threadIdx.x == 0) {
-        s_base = atomicAdd(out_count, (unsigned long long)s_count);
-        s_count = 0;
-    }
-    __syncthreads();
-    for (long long q = q_begin + threadIdx.x; q < q_end; q += blockDim.x) {
-        const int a = assign[q];
-        if (a < 0 || !(ub[q] * (1.0f + 1e-5f) < lb[q])) out_idx[s_base + atomicAdd(&s_count, 1u)] = q;
-    }
+        return a < 0 || !(u * (1.0f + 1e-5f) < l);
+    };
+    auto moved = [&](long long q) -> int { return assign[q] < 0 || !(ub[q] * (1.0f + 1e-5f) < lb[q]); };
+    long long* const out[1] = {out_idx};
+    lvs_append_lists<1>(per_block, n, move, moved, out, out_count);
 }
 }  // namespace
 
@@ -561,8 +550,7 @@ extern "C" int32_t lvs_kmeans_bounds_step(const int32_t* assign, float* ub, floa
     if (n == 0) return LVS_OK;
     LVS_REQUIRE(assign && ub && lb && delta && top2 && out_idx && out_count, "NULL buffer");
     LVS_DEVICE_GUARD(stream);
-    long long per_block = lvs_ceil_div(n, 2048);
-    per_block = lvs_round_up(per_block < 1024 ? 1024 : per_block, 256);
+    const long long per_block = lvs_append_per_block(n);
     hipLaunchKernelGGL(km_bounds_step_kernel, dim3((unsigned)lvs_ceil_div(n, per_block)), dim3(256), 0, (hipStream_t)stream,
                        assign, ub, lb, delta, top2, (long long)n, per_block, (long long*)out_idx,
                        (unsigned long long*)out_count);

@@ -15,6 +15,7 @@
 #include <dlfcn.h>
 #include <math.h>
 
+#include "lvs_bound.h"
 #include "lvs_common.h"
 #include "lvs_tile.h"
 
@@ -76,17 +77,6 @@ bool iter_plan(int64_t n, int32_t d, int32_t k, int32_t x_pack, int32_t c_pack, 
     return true;
 }
 
-// the one-pass search's error bound per unit of |q| (lotus_amd/backend.py _nearest_coef, squared L2): see lvs_margin_select_stats
-void nearest_coef(int32_t x_pack, int32_t d, int32_t exp_sum, float coef[5]) {
-    const double dpad = (double)lvs_round_up(d, 64);
-    const double qsplit = x_pack == LVS_PACK_SPLIT ? 1.0 : 0.0, c = 4.0;
-    coef[0] = (float)c;
-    coef[1] = (float)(c * (ldexp(1.0, -11) * qsplit + 8e-6) + ldexp(1.0, -16) * 2.0);
-    coef[2] = (float)(1e-6 * ldexp(1.0, exp_sum));
-    coef[3] = (float)(qsplit * c * sqrt(dpad) * ldexp(1.0, -25));
-    coef[4] = (float)(1e-6 + ldexp(1.0, -16));
-}
-
 }  // namespace
 
 extern "C" int64_t lvs_kmeans_iteration_workspace_bytes(int64_t n, int32_t d, int32_t k, int32_t x_pack, int32_t c_pack) {
@@ -121,8 +111,8 @@ extern "C" int32_t lvs_kmeans_iteration(lvs_all_reduce_fn all_reduce, void* all_
     uint64_t* counts = (uint64_t*)(ws + p.off_counts);
     float* sums = (float*)(ws + p.off_sums);
     float* cnt = (float*)(ws + p.off_cnt);
-    float coef[5];
-    nearest_coef(x_pack, d, exp_sum, coef);
+    LvsBoundCoef bound;  // the one-pass search's error bound (squared L2; iter_plan has checked x_pack and d)
+    lvs_nearest_bound_coef(LVS_METRIC_L2, x_pack, d, exp_sum, bound);
     const char* xr = (const char*)x;
     int64_t tot_pair = 0, tot_open = 0;
 
@@ -137,7 +127,7 @@ extern "C" int32_t lvs_kmeans_iteration(lvs_all_reduce_fn all_reduce, void* all_
                                   third + r0, ws + p.off_n3, p.n3_bytes, stream);
         if (rc != LVS_OK) return rc;
         LVS_HIP_CHECK(hipMemsetAsync(counts, 0, 16, st));
-        rc = lvs_nearest3_select(keys, keys2 + r0, sec + r0, third + r0, qn, m, c_stats, coef, pair_idx, open_idx, counts, stream);
+        rc = lvs_nearest3_select(keys, keys2 + r0, sec + r0, third + r0, qn, m, c_stats, bound.c, pair_idx, open_idx, counts, stream);
         if (rc != LVS_OK) return rc;
         uint64_t hc[2] = {0, 0};  // the call's host round trip (per chunk of rows): the exact search below is sized by it
         LVS_HIP_CHECK(hipMemcpyAsync(hc, counts, 16, hipMemcpyDeviceToHost, st));

@@ -1,13 +1,16 @@
 // Runs the host planners (lotus_amd/csrc/lvs_plan.h: the flat search and the threshold join; lvs_ivf_plan.h: the searches
-// through the lists and the bucket sort - the only project headers included) on a CPU.
+// through the lists and the bucket sort; lvs_bound.h: the one-pass error bound's coefficients - the only project headers
+// included) on a CPU.
 //   plan_check           walks the grids below and fails on the first violated invariant of geometry, layout, route and chunks
 //   plan_check --dump    one line per grid shape with every field of layout, geometry, two-phase plan, route, chunk list and
 //                        workspace offsets; then "ivf", "bucket" and "join" lines: every field of the IVF plan, the bucket
 //                        sort's plan, the join's launch list (tests/test_plan_pins.py pins some; the whole dump is what a
 //                        refactor diffs)
 //   plan_check --query   answers questions read from stdin, one per line, for the Python models of tests/test_rq_*.py, the
-//                        route tables of tests/test_widths_host.py and tests/extent_cases.py and the IVF tests' chunks
+//                        route tables of tests/test_widths_host.py and tests/extent_cases.py, the IVF tests' chunks and the
+//                        bound coefficients of tests/test_cert_rules_host.py
 // Built with a plain host compiler by tests/plan_native.py (run from tests/test_capi.py).
+#include "../../lotus_amd/csrc/lvs_bound.h"
 #include "../../lotus_amd/csrc/lvs_ivf_plan.h"
 
 #include <cstdio>
@@ -479,6 +482,13 @@ static int query_mode() {
             for (const JoinLaunch& l : join_launches(a[0], a[1], a[2], a[3], (int)a[4], (int)a[5], (int)a[6], (int)a[7], &rj))
                 printf("%d %lld %lld %lld %lld ", l.kernel, l.c0, l.cn, l.r0, l.rn);
             printf("\n");
+        } else if (c == "bound_coef" && n == 5) {  // metric pack d exp_sum -> the five floats' bit patterns
+            LvsBoundCoef k;
+            if (lvs_nearest_bound_coef((int)a[0], (int)a[1], (int)a[2], (int)a[3], k) == LVS_OK) {
+                uint32_t bits[5];
+                memcpy(bits, k.c, sizeof(bits));
+                printf("%u %u %u %u %u\n", bits[0], bits[1], bits[2], bits[3], bits[4]);
+            } else printf("none\n");
         } else {
             printf("?\n");
         }

@@ -34,6 +34,12 @@ def ask(questions):
     return answers
 
 
+def bound_coefs(cases):
+    """lvs_bound.h's lvs_nearest_bound_coef on every (metric, pack, d, exp_sum) of ``cases`` -> per case the five float32 bit
+    patterns as a tuple of ints (None: refused)."""
+    return [None if a is None else tuple(a) for a in ask([f"bound_coef {m} {p} {d} {e}" for m, p, d, e in cases])]
+
+
 IVF_MODE = {"Flat": 0, "SQ8": 1, "PQ": 2, "range": 3}  # LVS_IVF_* of lvs_ivf_plan.h
 
 

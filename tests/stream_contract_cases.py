@@ -42,7 +42,7 @@ HOST_ONLY = "host-only: touches no stream"
 EXCLUDED = {
     **{name: HOST_ONLY for name in (
         "lvs_abi_version", "lvs_last_error", "lvs_build_flags", "lvs_device_count", "lvs_device_info", "lvs_packed_ld",
-        "lvs_flat_search_seed_tiles", "lvs_flat_search_workspace_bytes", "lvs_search_sharded_workspace_bytes",
+        "lvs_flat_search_seed_tiles", "lvs_nearest_bound_coef", "lvs_flat_search_workspace_bytes", "lvs_search_sharded_workspace_bytes",
         "lvs_sort_rows_workspace_bytes", "lvs_nearest_hi_workspace_bytes", "lvs_nearest3_workspace_bytes",
         "lvs_kmeans_accumulate_workspace_bytes", "lvs_kmeans_objective_workspace_bytes", "lvs_kmeans_iteration_workspace_bytes",
         "lvs_ivf_build_workspace_bytes", "lvs_ivf_search_workspace_bytes", "lvs_ivf_range_workspace_bytes",

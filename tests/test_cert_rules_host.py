@@ -1,10 +1,16 @@
 """The float64 restatements in tests/cert_rules.py against brute force (no GPU): the Hamerly chain set -> shift -> step never
 skips a row whose nearest centroid changed, the certify restatement agrees with the host model of test_exactness_rules.py,
-and the select rules treat empty keys, NaN and infinities as the header says."""
+and the select rules treat empty keys, NaN and infinities as the header says.  The one-pass bound's coefficients: the header
+lvs_bound.h, the library entry lvs_nearest_bound_coef and a float64 restatement agree bit for bit."""
+import ctypes
+
 import numpy as np
 import pytest
 
 import cert_rules as cr
+import plan_native
+from lotus_amd import _capi
+from lotus_amd.backend import HipBackend, PackedRows
 from oracle.flat import pack_keys
 from test_exactness_rules import certified
 
@@ -118,6 +124,56 @@ def test_margin_rules_on_empty_keys_nan_and_infinities():
     cls, s2, s3 = cr.nearest3(pack_keys(np.float32([4, 4, 4, 4, 4]), np.arange(5)), k2, np.float32([1, 3, 3, 3, nan]),
                               np.float32([0, 1, -inf, 3, 0]), None, stats, coef)
     assert list(cls) == [cr.CERTIFIED, cr.PAIR, cr.OPEN, cr.OPEN, cr.PAIR] and s2[1] == 1 - 1.125 and s3[1] == 3 - 1.125
+
+
+def _coef_restated(metric, pack, d, exp_sum):
+    """The five coefficients of the one-pass bound (c[0] E + c[1] R) |q| + c[2] + c[3] R + c[4] R^2, restated in float64 from the
+    comment of lvs_margin_select_stats (include/lotus_hip.h) and the text HipBackend._nearest_coef had before the library
+    stated them: written here once, never imported from the product.  -> float32 [5]."""
+    ip, qsplit = metric == _capi.METRIC_IP, 1.0 if pack == _capi.PACK_SPLIT else 0.0
+    c = 2.0 if ip else 4.0
+    dpad = (d + 63) // 64 * 64
+    return np.array([c, c * ((2.0 ** -11) * qsplit + 8e-6) + 2.0 ** -16 * (1.0 if ip else 2.0), 1e-6 * 2.0 ** exp_sum,
+                     qsplit * c * (dpad ** 0.5) * 2.0 ** -25, 1e-6 + (0.0 if ip else 2.0 ** -16)], np.float64).astype(np.float32)
+
+
+_COEF_GRID = [(m, p, d, e) for m in (_capi.METRIC_IP, _capi.METRIC_L2) for p in (_capi.PACK_F16, _capi.PACK_SPLIT)
+              for d in (1, 8, 63, 64, 65, 100, 768, 1536, 4096) for e in (-40, -1, 0, 3, 40)]
+
+
+def _lib_coef(lib, metric, pack, d, exp_sum, out=True):
+    buf = (ctypes.c_float * 5)()
+    rc = lib.lvs_nearest_bound_coef(metric, pack, d, exp_sum, ctypes.addressof(buf) if out else None)
+    return rc, np.array(buf, np.float32)
+
+
+def test_bound_coefficients_header_library_and_restatement_agree_bit_for_bit():
+    lib = _capi.load()  # no GPU: the entry touches no device
+    from_header = plan_native.bound_coefs(_COEF_GRID)
+    for case, bits in zip(_COEF_GRID, from_header):
+        metric, pack, d, exp_sum = case
+        want = _coef_restated(*case)
+        assert bits is not None and np.array_equal(np.array(bits, np.uint32), want.view(np.uint32)), (case, bits, want)
+        rc, got = _lib_coef(lib, *case)
+        assert rc == _capi.OK and np.array_equal(got.view(np.uint32), want.view(np.uint32)), (case, got, want)
+        # HipBackend._nearest_coef on stand-in operands: the same numbers (as Python floats), dpad from the rows' width
+        dpad = (d + 63) // 64 * 64
+        corpus = PackedRows(rows=np.empty((0, 2 * dpad), np.float16), norms=None, n=0, d=d, mode=_capi.PACK_SPLIT, exp=exp_sum - 7)
+        queries = PackedRows(rows=np.empty((0, dpad * (1 + pack)), np.float16), norms=None, n=0, d=d, mode=pack, exp=7)
+        coef, got_dpad = HipBackend._nearest_coef(corpus, queries, metric)
+        assert got_dpad == dpad and len(coef) == 5 and all(type(v) is float for v in coef)
+        assert np.array_equal(np.array(coef, np.float64), want.astype(np.float64)), (case, coef, want)
+    # every argument moves the answer: 2 metrics x 5 exponents x (fp16 queries: no width term | hi|lo queries: 5 padded widths)
+    assert len(set(from_header)) == 2 * 5 * (1 + 5)
+
+
+def test_bound_coefficients_refuse_bad_arguments():
+    lib = _capi.load()
+    for bad in [(2, 0, 64, 0), (-1, 0, 64, 0), (0, 2, 64, 0), (1, -1, 64, 0), (0, 1, 0, 0), (1, 1, -5, 0)]:
+        assert _lib_coef(lib, *bad)[0] == _capi.EINVAL, bad
+        assert plan_native.bound_coefs([bad]) == [None], bad
+    assert _lib_coef(lib, 1, 1, 64, 0, out=False)[0] == _capi.EINVAL  # a NULL output
+    assert _lib_coef(lib, 1, 1, 64, 0)[0] == _capi.OK
 
 
 def test_shift_and_top2():

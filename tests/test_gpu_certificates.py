@@ -3,7 +3,7 @@ lvs_nearest3_select - called through the C ABI on synthetic arrays and compared 
 (tests/cert_rules.py): at the decision boundary itself with inputs for which every float32 operation is exact, on edge
 contents (empty keys, infinities, NaN, NULL norms), on random inputs wherever the float64 slack is outside float32 rounding,
 and the compaction of the listed indices at every block / wave edge.  Plus the two small kernels the certified search
-depends on: lvs_sort_keys_desc and lvs_rescore_keys."""
+depends on, lvs_sort_keys_desc and lvs_rescore_keys, and lvs_resolve_pairs, which claims the latter's arithmetic."""
 import ctypes
 import itertools
 
@@ -495,13 +495,14 @@ def test_sort_keys_desc(hip_backend):
         assert np.array_equal(h[:nq * k].view(np.uint64).reshape(nq, k), np.sort(keys, axis=1)[:, ::-1]), (k, nq)
 
 
-@pytest.mark.parametrize("d", [8, 64, 200])
+@pytest.mark.parametrize("d", [8, 64, 200, 520])
 @pytest.mark.parametrize("metric", [IP, L2])
 @pytest.mark.parametrize("qmode,bmode", [(F16, F16), (F16, SPLIT), (SPLIT, F16), (SPLIT, SPLIT)])
 def test_rescore_keys(hip_backend, qmode, bmode, metric, d):
     """Shuffled candidate lists with empty slots: ids, empty slots and the order stay as they are; every new score is the
     float64 score of the STORED values within the float32 accumulation bound (dpad / 64 + 10) 2^-24 |q| |row| (+ 3 * 2^-24 (|q|^2
-    + |row|^2) for the three float32 operations of the squared distance)."""
+    + |row|^2) for the three float32 operations of the squared distance).  d = 520 (dpad 576) is the smallest width at which
+    some lanes (0 - 7) take a second trip of the scorer's stride-512 loop and the others do not."""
     be = hip_backend
     rng = np.random.default_rng(d + 7 * metric + 3 * qmode + bmode)
     nb, nq, k, off = 50, 9, 6, 11
@@ -530,3 +531,70 @@ def test_rescore_keys(hip_backend, qmode, bmode, metric, d):
     err = np.abs(got.astype(np.float64) - want)[~empty]
     print("rescore", qmode, bmode, metric, d, "max err / tol", float((err / tol[~empty]).max()))
     assert (err <= tol[~empty]).all()
+
+
+@pytest.mark.parametrize("d", [8, 200, 520])
+@pytest.mark.parametrize("metric", [IP, L2])
+@pytest.mark.parametrize("qmode,bmode", [(F16, F16), (F16, SPLIT), (SPLIT, F16), (SPLIT, SPLIT)])
+def test_resolve_pairs(hip_backend, qmode, bmode, metric, d):
+    """lvs_resolve_pairs on its own: 64 queries, 300 rows, ids from 11; the index list names 48 of the queries in shuffled order
+    and the device count says 30 of a capacity of 48, then 60 of a capacity of 25.  A query that is not listed, listed beyond
+    min(count, capacity) or has an empty key keeps its key bit for bit; every other keys[q] is, bit for bit, the larger of the
+    two keys lvs_rescore_keys makes of the same two rows ("the arithmetic of lvs_rescore_keys") - the higher exact score and,
+    among equal scores (duplicated corpus rows), the lower id.
+
+    Before the two kernels shared one scorer with its multiply-adds fused by name (csrc/lvs_certify.h) the last assertion failed for
+    16 of the 24 cases: the compiler fused one kernel's multiply-adds and not the other's, and with a lo part in an operand 1 to
+    22 of the 22 to 27 settled keys were 1 to 32 float32 ulps from lvs_rescore_keys' (never another winner)."""
+    import torch
+
+    be = hip_backend
+    rng = np.random.default_rng(1000 + d + 7 * metric + 3 * qmode + bmode)
+    nb, nq, off, listed_n = 300, 64, 11, 48
+    xb = rng.standard_normal((nb, d)).astype(np.float32)
+    xb[1::2][:20] = xb[0::2][:20]                       # rows 2 i and 2 i + 1 (i < 20) are equal: equal exact scores
+    xq = (xb[rng.integers(0, nb, nq)] + 0.2 * rng.standard_normal((nq, d))).astype(np.float32)
+    cb = be.pack(xb.astype(np.float16) if bmode == F16 else xb, bmode)
+    cq = be.pack(xq.astype(np.float16) if qmode == F16 else xq, qmode)
+    rows = np.stack([rng.permutation(nb)[:2] for _ in range(nq)])
+    twins = 2 * rng.integers(0, 20, 24)
+    rows[:24, 0], rows[:24, 1] = twins, twins + 1       # 24 ties ...
+    rows[:12] = rows[:12, ::-1]                         # ... half of them with the higher id in keys1
+    keys = pack_keys(rng.standard_normal((nq, 2)).astype(np.float32), rows + off)   # stale scores, in no order
+    keys[[3, 30, 40, 50], 1] = 0                        # no runner-up
+    keys[[4, 31, 41, 51], 0] = 0                        # no winner
+    keys[5] = 0
+    exact = _keys_dev(be, keys)                         # [nq, 2] -> the two exact keys of every query
+    be._c("lvs_rescore_keys", _ptr(cb.rows), cb.mode, _ptr(cq.rows), cq.mode, nq, d, metric, _ptr(cb.norms), _ptr(cq.norms), off, 2,
+          _ptr(exact), be._stream())
+    exact = exact.cpu().numpy().view(np.uint64)
+    s, ids, _ = unpack_keys(exact)
+    first_wins = (s[:, 0] > s[:, 1]) | ((s[:, 0] == s[:, 1]) & (ids[:, 0] < ids[:, 1]))
+    both = (keys != 0).all(axis=1)
+    ties = both & (s[:, 0] == s[:, 1])
+    assert ties[:12].any() and ties[12:24].any() and not ties[24:].any()
+    idx = np.array([q for q in rng.permutation(nq) if q not in (3, 4, 5)])
+    idx = np.insert(idx, [1, 7, 20], [3, 4, 5])         # three of the queries with an empty key among the first 25 listed
+    k2 = _keys_dev(be, keys[:, 1].copy())
+    idx_dev = be.to_device(idx.astype(np.int64))        # past the list: the queries that are not listed (they stay untouched)
+    for count, cap in [(30, listed_n), (60, 25)]:
+        k1 = torch.full((nq + 64,), SENT, dtype=torch.int64, device=be.device)
+        k1[:nq] = _keys_dev(be, keys[:, 0].copy())
+        cnt = be.to_device(np.array([count], np.int64))
+        be._c("lvs_resolve_pairs", _ptr(cb.rows), cb.mode, _ptr(cq.rows), cq.mode, d, metric, _ptr(cb.norms), _ptr(cq.norms), off,
+              _ptr(idx_dev), _ptr(cnt), cap, _ptr(k1), _ptr(k2), be._stream())
+        h = k1.cpu().numpy()
+        assert (h[nq:] == SENT).all() and int(cnt.cpu()[0]) == count
+        got = h[:nq].view(np.uint64)
+        done = np.zeros(nq, bool)
+        done[idx[:min(count, cap)]] = True
+        done &= both
+        assert 10 <= done.sum() < min(count, cap) and (done & ties).sum() >= 2
+        want = exact[done].max(axis=1)
+        ulps = np.abs((got[done] >> np.uint64(32)).astype(np.int64) - (want >> np.uint64(32)).astype(np.int64))
+        print("resolve_pairs", qmode, bmode, metric, d, (count, cap), "settled", int(done.sum()), "keys that differ", int((got[done] != want).sum()),
+              "other winner", int(((got[done] ^ want) & np.uint64(0xFFFFFFFF) != 0).sum()), "largest score distance in ulps", int(ulps.max()))
+        assert np.array_equal(got[~done], keys[~done, 0])
+        low = np.uint64(0xFFFFFFFF)   # the id half: the row with the higher exact score and, among equal scores, the lower id
+        assert np.array_equal(got[done] & low, np.where(first_wins, exact[:, 0], exact[:, 1])[done] & low)
+        assert np.array_equal(got[done], want)

@@ -184,12 +184,6 @@ def case_fallback(be):
     return Case(lambda: run_raw(be, raw, ws), raw.outs, s.load, [ws], check=check, keep=[pool, raw])
 
 
-def _cert_bound(be, cb, cq):
-    """scale, slack of the certified search's error bound, as HipBackend._search_keys_certified has them (inner product)."""
-    R, E_c, E_q = be.row_norm_max(cb), be.lo_norm_max(cb), be.lo_norm_max(cq)
-    return E_c * (1.0 + 1e-3) + 8e-6 * R, 1e-6 * (1.0 + R * R) + E_q * (R + E_c) * (1.0 + 1e-3)
-
-
 def case_certified(be):
     """_hi_banded -> rescore -> sort -> certify (banded, and the plain rule on the same lists) as ONE graph.  A: fp16-valued rows,
     every query certifies.  B: test_one_pass_certificate_refuses_rows_that_differ_below_fp16_resolution's twins (same hi part,
@@ -205,7 +199,7 @@ def case_certified(be):
         xbB[rows] = xbB[qi]
         xbB[rows, :8] += (np.arange(30)[:, None] / 100.0) * np.spacing(np.abs(h16[qi, :8])).astype(np.float32)
     pA, pB, cq = be.pack(xbA, SPLIT), be.pack(xbB, SPLIT), be.pack(xq, SPLIT)
-    scale, slack = (max(v) for v in zip(_cert_bound(be, pA, cq), _cert_bound(be, pB, cq)))
+    scale, slack = (max(v) for v in zip(be._cert_bound(pA, cq, IP), be._cert_bound(pB, cq, IP)))
     s, pool = Sets(), GuardedPool(be.device)
     cb = s.packed(pA, pB)
     raw = raw_flat(be, pool, c, cb, cq, "lvs_flat_search_keys_hi_banded")  # (its band: 1e-3 |q| + 1e-3 below the k-th slot)
