@@ -5,8 +5,10 @@ loudly when the library has not been built; there is no fallback implementation.
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 import re
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblotus_hip.so")
@@ -23,111 +25,73 @@ ABI_VERSION = 7
 BUILD_TUNING, BUILD_COUNT_EVENTS = 1, 2
 PACK_FLAG_NONFINITE, PACK_FLAG_RANGE = 1, 2
 
-_i32, _i64, _vp, _dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = ("void", "char", "float", "double", "int32_t", "int64_t", "uint8_t", "uint32_t", "uint64_t")
 
-# name -> (restype, argtypes); must list every symbol declared in include/lotus_hip.h
-SIGNATURES = {
-    "lvs_abi_version": (_i32, []),
-    "lvs_last_error": (ctypes.c_char_p, []),
-    "lvs_build_flags": (_i32, []),
-    "lvs_device_count": (_i32, [ctypes.POINTER(_i32)]),
-    "lvs_device_info": (_i32, [_i32, ctypes.c_char_p, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
-    "lvs_packed_ld": (_i32, [_i32, _i32]),
-    "lvs_pack_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "lvs_pack_rows_checked": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "lvs_absmax": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp]),
-    "lvs_gather_rows": (_i32, [_vp, _i32, _vp, _i64, _vp, _vp]),
-    "lvs_gather_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
-    "lvs_unpack_rows": (_i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp]),
-    "lvs_flat_search_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32, _i32]),
-    "lvs_flat_search_keys": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp,
-                                    _vp, _i64, _vp]),
-    "lvs_flat_search_seed_tiles": (_i32, [_i64, _i64, _i32]),
-    "lvs_flat_search_seed_scores": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
-    "lvs_flat_search_keys_seeded": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i32,
-                                           _vp, _vp, _i64, _vp]),
-    "lvs_merge_keys": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp]),
-    "lvs_search_sharded_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32]),
-    "lvs_search_sharded": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp,
-                                  _vp, _i64, _vp]),
-    "lvs_rccl_available": (_i32, []),
-    "lvs_rccl_bind": (_i32, [_vp, _vp, _vp]),
-    "lvs_search_sharded_rccl": (_i32, [_vp, _vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp,
-                                       _i64, _vp]),
-    "lvs_keys_to_result": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
-    "lvs_scores": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
-    "lvs_sort_rows_workspace_bytes": (_i64, [_i64, _i64]),
-    "lvs_sort_rows_desc": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
-    "lvs_range_join": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _vp, ctypes.c_float, _i32, _i64, _i64, _i32,
-                              _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "lvs_nearest_hi_workspace_bytes": (_i64, [_i64, _i64, _i32]),
-    "lvs_nearest_hi": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_nearest3_workspace_bytes": (_i64, [_i64, _i64, _i32]),
-    "lvs_nearest3": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_nearest3_select": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "lvs_resolve_pairs": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "lvs_rescore_keys": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
-    "lvs_flat_search_keys_hi": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp,
-                                       _vp, _i64, _vp]),
-    "lvs_flat_search_keys_hi_banded": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, ctypes.c_float,
-                                              ctypes.c_float, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_sort_keys_desc": (_i32, [_vp, _i64, _i32, _vp]),
-    "lvs_certify_topk": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
-    "lvs_certify_topk_banded": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp,
-                                       _vp, _vp]),
-    "lvs_margin_select": (_i32, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
-    "lvs_margin_select_stats": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "lvs_nearest_bound_coef": (_i32, [_i32, _i32, _i32, _i32, _vp]),
-    "lvs_kmeans_accumulate_workspace_bytes": (_i64, [_i64, _i32]),
-    "lvs_kmeans_accumulate": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_kmeans_accumulate_keys": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_kmeans_objective_workspace_bytes": (_i64, [_i32]),
-    "lvs_kmeans_objective": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_kmeans_pack_centroids": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "lvs_kmeans_update_centroids": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
-    "lvs_kmeans_centroid_shift": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
-    "lvs_kmeans_bounds_set": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "lvs_kmeans_bounds_fix": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "lvs_kmeans_bounds_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "lvs_rand_perm_host": (_i32, [_i64, _i64, _vp]),
-    "lvs_rand_perm_prefix_host": (_i32, [_i64, _i64, _i64, _vp]),
-    "lvs_kmeans_split_clusters_host": (_i32, [_i32, _i32, _i64, _vp, _vp, ctypes.POINTER(_i32)]),
-    "lvs_kmeans_iteration_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
-    "lvs_kmeans_iteration": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _i64, _vp]),
-    "lvs_kmeans_iteration_rccl": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _i64, _vp]),
-    "lvs_rccl_bind_all_reduce": (_i32, [_vp]),
-    "lvs_ivf_build_workspace_bytes": (_i64, [_i64, _i32]),
-    "lvs_ivf_build_lists": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_search_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
-    "lvs_ivf_search_keys": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32,
-                                   _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_search_keys_sel": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _i32, _i32,
-                                       _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_sq8_encode": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "lvs_ivf_sq8_search_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
-    "lvs_ivf_sq8_search_keys": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _i32,
-                                       _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_sq8_search_keys_sel": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i64,
-                                           _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_pq_encode": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "lvs_ivf_pq_search_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
-    "lvs_ivf_pq_search_keys": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _vp,
-                                      _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_pq_search_keys_sel": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32,
-                                          _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_ivf_range_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
-    "lvs_ivf_range_search": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32,
-                                    _i32, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "lvs_refine_keys": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
-    "lvs_keys_overlap": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
-    "lvs_ivf_row_lists": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
-    "lvs_ivf_probe_ranks": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp]),
-    "lvs_timing_enable": (_i32, [_i32]),
-    "lvs_timing_read": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),
-    "lvs_timing_read_calls": (_i32, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
-}
+
+class Prototype(NamedTuple):
+    """One function (or callback typedef) of the header: what ctypes needs, and the parameter names in order."""
+
+    restype: type
+    argtypes: tuple
+    names: tuple
+    types: tuple  # every parameter's type as the header spells it ("const float*", "int64_t", "lvs_all_gather_fn")
+
+
+def parse_header(text: str):
+    """-> (prototypes, callbacks, defines) of a header written like include/lotus_hip.h: ``ret lvs_name(type name, ...);`` and
+    ``typedef int32_t (*lvs_name_fn)(...);`` between comments and preprocessor lines.  Not a C parser: a statement or a type
+    outside that vocabulary raises ``ValueError`` naming the prototype."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)
+    prototypes, callbacks = {}, {}
+
+    def param(decl: str, where: str):
+        m = re.fullmatch(r"(const\s+)?(\w+)\s*(\*?)\s*(\w+)", decl.strip())
+        if m is None:
+            raise ValueError(f"{where}: cannot read the parameter {decl.strip()!r} (a type and a name are needed)")
+        const, base, star, name = m.groups()
+        if star and base in _POINTEES:
+            return ctypes.c_void_p, name, f"{'const ' if const else ''}{base}*"
+        if not star and not const and base in _SCALARS:
+            return _SCALARS[base], name, base
+        if not star and not const and base in callbacks:
+            return ctypes.c_void_p, name, base  # callers cast their CFUNCTYPE object
+        raise ValueError(f"{where}: unknown type of the parameter {decl.strip()!r}")
+
+    for stmt in (s.strip() for s in text.split(";")):
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(typedef\s+)?([\w\s\*]+?)\s*(?:\(\s*\*\s*(lvs_\w+)\s*\)|\b(lvs_\w+))\s*\(([^()]*)\)", stmt)
+        if m is None or bool(m.group(1)) != bool(m.group(3)):
+            raise ValueError(f"cannot read the declaration {' '.join(stmt.split())[:80]!r}")
+        name = m.group(3) or m.group(4)
+        ret = " ".join(m.group(2).replace("*", " * ").split())
+        if ret in ("int32_t", "int64_t"):
+            restype = _SCALARS[ret]
+        elif ret == "const char *" and not m.group(1):
+            restype = ctypes.c_char_p
+        else:
+            raise ValueError(f"{name}: unknown return type {ret!r}")
+        decls = [] if m.group(5).strip() in ("", "void") else m.group(5).split(",")
+        params = [param(d, name) for d in decls]
+        proto = Prototype(restype, tuple(p[0] for p in params), tuple(p[1] for p in params), tuple(p[2] for p in params))
+        if len(set(proto.names)) != len(proto.names):
+            raise ValueError(f"{name}: a parameter name is used twice")
+        if m.group(1):
+            callbacks[name] = ctypes.CFUNCTYPE(proto.restype, *proto.argtypes)
+        else:
+            prototypes[name] = proto
+    return prototypes, callbacks, defines
+
+
+with open(HEADER_PATH) as _f:
+    # PROTOTYPES: every function of the header; CALLBACKS: its callback typedefs as CFUNCTYPEs; DEFINES: its integer #defines
+    PROTOTYPES, CALLBACKS, DEFINES = parse_header(_f.read())
+SIGNATURES = {name: (p.restype, list(p.argtypes)) for name, p in PROTOTYPES.items()}  # name -> (restype, argtypes)
 
 
 class LotusHipError(RuntimeError):
@@ -139,10 +103,34 @@ _lib = None
 
 def declared_symbols() -> list[str]:
     """Function names declared in include/lotus_hip.h."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(lvs_[a-z0-9_]+)\s*\(", text)))
+    return sorted(PROTOTYPES)
+
+
+_tails = {}  # (entry, positional arguments given) -> (how many parameters remain, kw -> their values in header order)
+
+
+def _tail(name: str, npos: int):
+    rest = PROTOTYPES[name].names[npos:]
+    get = operator.itemgetter(*rest) if len(rest) > 1 else (lambda kw: (kw[rest[0]],)) if rest else (lambda kw: ())
+    _tails[name, npos] = len(rest), get
+    return _tails[name, npos]
+
+
+def bind(name: str, args: tuple, kw: dict) -> tuple:
+    """The arguments of entry ``name`` in the header's order: ``args`` as given, then ``kw`` by the header's parameter names.
+    A name that is missing, unknown or already given by position raises ``TypeError``; nothing is dropped or defaulted."""
+    if not kw:
+        return args
+    names = PROTOTYPES[name].names
+    n, get = _tails.get((name, len(args))) or _tail(name, len(args))
+    try:
+        tail = get(kw)
+    except KeyError as e:
+        raise TypeError(f"{name}: missing parameter {e.args[0]!r}") from None
+    if len(kw) != n:
+        extra = next(k for k in kw if k not in names[len(args):])
+        raise TypeError(f"{name}: parameter {extra!r} given twice" if extra in names else f"{name}: unknown parameter {extra!r}")
+    return args + tail
 
 
 def load(path: str | None = None):
@@ -187,6 +175,6 @@ def check(status: int, what: str = "") -> None:
 
 
 def device_count() -> int:
-    n = _i32(0)
+    n = ctypes.c_int32(0)
     st = load().lvs_device_count(ctypes.byref(n))
     return int(n.value) if st == OK else 0

@@ -92,6 +92,12 @@ def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
 
+def _operands(corpus: "PackedRows", queries: "PackedRows") -> dict:
+    """A packed corpus and packed queries under the nine parameter names of the entry points that take both whole."""
+    return dict(xb=_ptr(corpus.rows), xb_pack=corpus.mode, nb=corpus.n, xb_norms_sq=_ptr(corpus.norms), xq=_ptr(queries.rows),
+                xq_pack=queries.mode, nq=queries.n, xq_norms_sq=_ptr(queries.norms), d=corpus.d)
+
+
 class _Bounds:
     """The Hamerly bounds that a squared-L2 ``nearest`` call keeps beside its search: the caller's ``bounds`` tuple
     ``(assign, ub, lb, positions)``, the corpus statistics and the five coefficients of the search's own error bound."""
@@ -109,8 +115,9 @@ class _Bounds:
 
     def set(self, keys, sec, q_norms, nq: int) -> None:
         """Every query's bounds from the one-pass result (see ``HipBackend.nearest``)."""
-        self.be._c("lvs_kmeans_bounds_set", _ptr(keys), 1, _ptr(sec), _ptr(q_norms), _ptr(self.pos), nq, _ptr(self.corpus_stats),
-                   ctypes.addressof(self.coef5), self.id_offset, _ptr(self.assign), _ptr(self.ub), _ptr(self.lb), self.be._stream())
+        self.be._call("lvs_kmeans_bounds_set", keys=_ptr(keys), key_stride=1, second=_ptr(sec), q_norms_sq=_ptr(q_norms),
+                   positions=_ptr(self.pos), m=nq, corpus_stats=_ptr(self.corpus_stats), coef5=ctypes.addressof(self.coef5),
+                   id_offset=self.id_offset, assign=_ptr(self.assign), ub=_ptr(self.ub), lb=_ptr(self.lb), stream=self.be._stream())
 
     def fix(self, approx, exact, q_norms, sel) -> None:
         """The bounds of the queries ``sel`` again, from their one-pass keys ``approx`` and the ``exact`` keys that decided them."""
@@ -119,9 +126,10 @@ class _Bounds:
         # relative margin of lvs_kmeans_bounds_step
         exact2 = (ctypes.c_float * 2)(8e-6, 4e-6)
         pos = sel if self.pos is None else self.pos[sel]
-        self.be._c("lvs_kmeans_bounds_fix", _ptr(approx), _ptr(exact), _ptr(q_norms), _ptr(pos), int(sel.numel()),
-                   _ptr(self.corpus_stats), ctypes.addressof(self.coef5), ctypes.addressof(exact2), self.id_offset,
-                   _ptr(self.assign), _ptr(self.ub), _ptr(self.lb), self.be._stream())
+        self.be._call("lvs_kmeans_bounds_fix", approx_keys=_ptr(approx), exact_keys=_ptr(exact), q_norms_sq=_ptr(q_norms),
+                   positions=_ptr(pos), m=int(sel.numel()), corpus_stats=_ptr(self.corpus_stats),
+                   coef5=ctypes.addressof(self.coef5), exact_coef2=ctypes.addressof(exact2), id_offset=self.id_offset,
+                   assign=_ptr(self.assign), ub=_ptr(self.ub), lb=_ptr(self.lb), stream=self.be._stream())
 
 
 @dataclass
@@ -173,11 +181,18 @@ class HipBackend:
     def _stream(self) -> int:
         return int(self.torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _c(self, name: str, *args) -> None:
-        """One C-ABI call on this backend's device.  The library makes the stream's device current itself, but torch's
-        default stream is the NULL handle, which names no device - so the device is also made current here."""
+    def _c(self, name: str, *args, **kw) -> None:
+        """One C-ABI call on this backend's device: positional arguments as the header orders them, keywords by the header's
+        parameter names (``_capi.bind``).  The library makes the stream's device current itself, but torch's default stream
+        is the NULL handle, which names no device - so the device is also made current here."""
+        args = _capi.bind(name, args, kw)
         with self.torch.cuda.device(self.device):
             _capi.check(getattr(self.lib, name)(*args), name)
+
+    def _call(self, name: str, *args, **kw) -> None:
+        """``_c`` as this module calls it: the keywords are bound here, so ``_c`` itself always sees one positional call in the
+        header's order - what a wrapper put around ``_c`` (the tests record the entries called that way) can rely on."""
+        self._c(name, *_capi.bind(name, args, kw))
 
     def _workspace(self, nbytes: int):
         """The scratch buffer of the CURRENT stream (one per stream: launches queued on a side stream - the k-means sums and
@@ -374,8 +389,8 @@ class HipBackend:
         if t.dtype not in (torch.float16, torch.float32):
             t = t.to(torch.float32)
         n, d = (int(t.shape[0]), int(t.shape[1])) if t.dim() == 2 else (1, int(t.numel()))
-        self._c("lvs_absmax", _ptr(t), _capi.DTYPE_F16 if t.dtype == torch.float16 else _capi.DTYPE_F32, n, d, _ptr(bits),
-                self._stream())
+        self._call("lvs_absmax", src=_ptr(t), src_dtype=_capi.DTYPE_F16 if t.dtype == torch.float16 else _capi.DTYPE_F32, n=n, d=d,
+                inout_bits=_ptr(bits), stream=self._stream())
         return float(np.array([int(bits.item())], np.uint32).view(np.float32)[0])
 
     @classmethod
@@ -433,11 +448,13 @@ class HipBackend:
                 chunk = chunk_of(r0, r1)
                 src_dtype = _capi.DTYPE_F16 if chunk.dtype == torch.float16 else _capi.DTYPE_F32
                 if auto:
-                    self._c("lvs_absmax", _ptr(chunk), src_dtype, r1 - r0, d, _ptr(amax_bits), self._stream())
+                    self._call("lvs_absmax", src=_ptr(chunk), src_dtype=src_dtype, n=r1 - r0, d=d, inout_bits=_ptr(amax_bits),
+                            stream=self._stream())
                     if r0 == 0 and e is None:  # the exponent comes from the first chunk (one read-back per index build)
                         e = self.exp_for(float(np.array([int(amax_bits.item())], np.uint32).view(np.float32)[0]))
-                self._c("lvs_pack_rows_checked", _ptr(chunk), src_dtype, r1 - r0, d, mode, int(bool(normalize)), int(e),
-                        _ptr(rows[r0:r1]), _ptr(norms[r0:r1]), _ptr(flags), self._stream())
+                self._call("lvs_pack_rows_checked", src=_ptr(chunk), src_dtype=src_dtype, n=r1 - r0, d=d, pack_mode=mode,
+                        normalize=int(bool(normalize)), scale_exp=int(e), dst=_ptr(rows[r0:r1]), out_norms_sq=_ptr(norms[r0:r1]),
+                        out_flags=_ptr(flags), stream=self._stream())
                 del chunk
             return e
 
@@ -466,8 +483,8 @@ class HipBackend:
         ld = int(src.rows.shape[1])
         rows = torch.empty((m, ld), dtype=torch.float16, device=self.device)
         norms = torch.empty((m,), dtype=torch.float32, device=self.device)
-        self._c("lvs_gather_rows", _ptr(src.rows), ld, _ptr(ids_dev), m, _ptr(rows), self._stream())
-        self._c("lvs_gather_f32", _ptr(src.norms), _ptr(ids_dev), m, _ptr(norms), self._stream())
+        self._call("lvs_gather_rows", src=_ptr(src.rows), ld=ld, ids=_ptr(ids_dev), n_ids=m, dst=_ptr(rows), stream=self._stream())
+        self._call("lvs_gather_f32", _ptr(src.norms), _ptr(ids_dev), m, _ptr(norms), self._stream())
         return PackedRows(rows=rows, norms=norms, n=m, d=src.d, mode=src.mode, exp=src.exp)
 
     def unpack(self, src: PackedRows, ids_dev=None, raw: bool = False):
@@ -476,8 +493,8 @@ class HipBackend:
         torch = self.torch
         m = src.n if ids_dev is None else int(ids_dev.numel())
         out = torch.empty((m, src.d), dtype=torch.float32, device=self.device)
-        self._c("lvs_unpack_rows", _ptr(src.rows), src.d, src.mode, _ptr(ids_dev), m, 0 if raw else int(src.exp), _ptr(out),
-                self._stream())
+        self._call("lvs_unpack_rows", src=_ptr(src.rows), d=src.d, pack_mode=src.mode, ids=_ptr(ids_dev), n=m,
+                scale_exp=0 if raw else int(src.exp), dst=_ptr(out), stream=self._stream())
         return out
 
     @staticmethod
@@ -516,9 +533,8 @@ class HipBackend:
         torch = self.torch
         out = torch.empty((int(tiles), queries.n), dtype=torch.float32, device=self.device)
         if tiles and queries.n:
-            self._c("lvs_flat_search_seed_scores", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode,
-                    queries.n, corpus.d, metric, _ptr(corpus.norms), _ptr(queries.norms), int(tiles), _ptr(out),
-                    self._stream())
+            self._call("lvs_flat_search_seed_scores", **_operands(corpus, queries), metric=metric, tiles=int(tiles),
+                    out_scores=_ptr(out), stream=self._stream())
         return out
 
     def search_keys(self, corpus: PackedRows, queries: PackedRows, k: int, metric: int, id_offset: int = 0,
@@ -551,7 +567,7 @@ class HipBackend:
                 raise ValueError("seed_scores must be float32 [rows, nq]")
             seed_scores = seed_scores.contiguous()
             return self._search_call("lvs_flat_search_keys_seeded", corpus, queries, k, metric, id_offset, row_ids,
-                                     seeded=(_ptr(seed_scores), int(seed_scores.shape[0])))
+                                     seed_scores=_ptr(seed_scores), seed_rows=int(seed_scores.shape[0]))
         return self._search_call("lvs_flat_search_keys", corpus, queries, k, metric, id_offset, row_ids)
 
     @staticmethod
@@ -586,23 +602,23 @@ class HipBackend:
             return 0.0
         return self._cached_max(pk, "_row_norm_max", lambda: float(pk.norms.max().sqrt().item()))
 
-    def _search_call(self, name: str, corpus, queries, k, metric, id_offset, row_ids=None, banded=(), seeded=()):
-        """One flat search (``lvs_flat_search_keys`` / ``_seeded`` / ``_hi`` / ``_hi_banded``) -> keys [nq, k].  ``banded``: what goes
-        between ``k`` and the norms (the band's k, scale and slack); ``seeded``: after ``row_ids`` (the seed scores, their rows)."""
+    def _search_call(self, name: str, corpus, queries, k, metric, id_offset, row_ids=None, **extra):
+        """One flat search (``lvs_flat_search_keys`` / ``_seeded`` / ``_hi`` / ``_hi_banded``) -> keys [nq, k].  ``extra``: what the
+        entry declares beyond the plain search (``kc``, ``band_scale``, ``band_slack``; ``seed_scores``, ``seed_rows``)."""
         keys = self.torch.empty((queries.n, k), dtype=self.torch.int64, device=self.device)
         need = int(self.lib.lvs_flat_search_workspace_bytes(queries.n, corpus.n, corpus.d, k, corpus.mode, queries.mode))
         if need < 0:
             raise LotusHipError("the flat search's workspace query rejected the shape")
         ws = self._workspace(need)
-        self._c(name, _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode, queries.n, corpus.d, metric,
-                k, *banded, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(row_ids), *seeded, _ptr(keys), _ptr(ws),
-                int(ws.numel()), self._stream())
+        self._call(name, **_operands(corpus, queries), metric=metric, k=k, id_offset=int(id_offset), row_ids=_ptr(row_ids),
+                out_keys=_ptr(keys), workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream(), **extra)
         return keys
 
     def _rescore(self, corpus, queries, metric, id_offset, keys) -> None:
         """Put the exact scores into the keys [nq, k] of every query, in place (one wave per query, HBM-bound)."""
-        self._c("lvs_rescore_keys", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, queries.n, corpus.d, metric,
-                _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), int(keys.shape[1]), _ptr(keys), self._stream())
+        self._call("lvs_rescore_keys", xb=_ptr(corpus.rows), xb_pack=corpus.mode, xq=_ptr(queries.rows), xq_pack=queries.mode,
+                nq=queries.n, d=corpus.d, metric=metric, xb_norms_sq=_ptr(corpus.norms), xq_norms_sq=_ptr(queries.norms),
+                id_offset=int(id_offset), k=int(keys.shape[1]), keys=_ptr(keys), stream=self._stream())
 
     @staticmethod
     def _count(stats: dict | None, **counts) -> None:
@@ -655,16 +671,18 @@ class HipBackend:
             banded = False
         if banded:
             approx = self._search_call("lvs_flat_search_keys_hi_banded", corpus, queries, k1, metric, id_offset,
-                                       banded=(k, float(self.CERT_BAND_SEARCH * scale), float(self.CERT_BAND_SEARCH * slack)))
+                                       kc=k, band_scale=float(self.CERT_BAND_SEARCH * scale),
+                                       band_slack=float(self.CERT_BAND_SEARCH * slack))
         else:
             approx = self._search_call("lvs_flat_search_keys_hi", corpus, queries, k1, metric, id_offset)
         exact = approx.clone()
         self._rescore(corpus, queries, metric, id_offset, exact)
-        self._c("lvs_sort_keys_desc", _ptr(exact), nq, k1, self._stream())
+        self._call("lvs_sort_keys_desc", _ptr(exact), nq, k1, self._stream())
         idx = torch.empty((nq,), dtype=torch.int64, device=self.device)
         cnt = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("lvs_certify_topk_banded", _ptr(approx), _ptr(exact), _ptr(queries.norms), nq, k1, k, float(scale), float(slack),
-                float(self.CERT_BAND_CERTIFY if banded else 0.0), _ptr(idx), _ptr(cnt), self._stream())
+        self._call("lvs_certify_topk_banded", approx_keys=_ptr(approx), exact_keys=_ptr(exact), q_norms_sq=_ptr(queries.norms), nq=nq,
+                k1=k1, k=k, scale=float(scale), slack=float(slack), band=float(self.CERT_BAND_CERTIFY if banded else 0.0),
+                out_idx=_ptr(idx), out_count=_ptr(cnt), stream=self._stream())
         keys = exact[:, :k].contiguous()
         n_open = int(cnt.item())
         n_plain = 0
@@ -742,18 +760,18 @@ class HipBackend:
         sec = torch.empty((nq,), dtype=torch.float32, device=self.device)
         need = int(self.lib.lvs_nearest_hi_workspace_bytes(nq, corpus.n, corpus.d))
         ws = self._workspace(need)
-        self._c("lvs_nearest_hi", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode, nq, corpus.d,
-                metric, _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(keys), _ptr(sec), _ptr(ws),
-                int(ws.numel()), self._stream())
+        self._call("lvs_nearest_hi", **_operands(corpus, queries), metric=metric, id_offset=int(id_offset), out_keys=_ptr(keys),
+                out_second=_ptr(sec), workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream())
         idx = torch.empty((nq,), dtype=torch.int64, device=self.device)
         cnt = torch.zeros((1,), dtype=torch.int64, device=self.device)
         if corpus_stats is None:
-            self._c("lvs_margin_select", _ptr(keys), _ptr(sec), _ptr(queries.norms), nq, float(scale), float(slack),
-                    _ptr(idx), _ptr(cnt), self._stream())
+            self._call("lvs_margin_select", keys=_ptr(keys), second=_ptr(sec), q_norms_sq=_ptr(queries.norms), nq=nq,
+                    scale=float(scale), slack=float(slack), out_idx=_ptr(idx), out_count=_ptr(cnt), stream=self._stream())
         else:
             coef5 = (ctypes.c_float * 5)(*coef)
-            self._c("lvs_margin_select_stats", _ptr(keys), _ptr(sec), _ptr(queries.norms), nq, _ptr(corpus_stats),
-                    ctypes.addressof(coef5), _ptr(idx), _ptr(cnt), self._stream())
+            self._call("lvs_margin_select_stats", keys=_ptr(keys), second=_ptr(sec), q_norms_sq=_ptr(queries.norms), nq=nq,
+                    corpus_stats=_ptr(corpus_stats), coef5=ctypes.addressof(coef5), out_idx=_ptr(idx), out_count=_ptr(cnt),
+                    stream=self._stream())
         if bounds is not None:  # every row's bounds from the one-pass result first; the uncertified rows are redone below
             bounds.set(keys, sec, queries.norms, nq)
         n_open = int(cnt.item())  # the call's one host round trip: the exact search below is sized by it
@@ -817,13 +835,14 @@ class HipBackend:
         if need < 0:
             raise LotusHipError("lvs_nearest3_workspace_bytes rejected the shape")
         ws = self._workspace(need)
-        self._c("lvs_nearest3", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode, nq, corpus.d, metric,
-                _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(keys), _ptr(keys2), _ptr(sec), _ptr(third),
-                _ptr(ws), int(ws.numel()), self._stream())
+        self._call("lvs_nearest3", **_operands(corpus, queries), metric=metric, id_offset=int(id_offset), out_keys=_ptr(keys),
+                out_keys2=_ptr(keys2), out_second=_ptr(sec), out_third=_ptr(third), workspace=_ptr(ws),
+                workspace_bytes=int(ws.numel()), stream=self._stream())
         pair_idx, open_idx, counts = torch.empty((nq,), **i64), torch.empty((nq,), **i64), torch.zeros((2,), **i64)
         coef5 = (ctypes.c_float * 5)(*coef)
-        self._c("lvs_nearest3_select", _ptr(keys), _ptr(keys2), _ptr(sec), _ptr(third), _ptr(queries.norms), nq,
-                _ptr(corpus_stats), ctypes.addressof(coef5), _ptr(pair_idx), _ptr(open_idx), _ptr(counts), self._stream())
+        self._call("lvs_nearest3_select", keys=_ptr(keys), keys2=_ptr(keys2), second=_ptr(sec), third=_ptr(third),
+                q_norms_sq=_ptr(queries.norms), nq=nq, corpus_stats=_ptr(corpus_stats), coef5=ctypes.addressof(coef5),
+                out_pair_idx=_ptr(pair_idx), out_open_idx=_ptr(open_idx), out_counts=_ptr(counts), stream=self._stream())
         if bounds is not None:  # every row's bounds from the one-pass result first; the uncertified rows are redone below
             bounds.set(keys, sec, queries.norms, nq)
         return _NearestHandle(queries=queries, corpus=corpus, metric=metric, id_offset=id_offset, exact_scores=exact_scores,
@@ -842,9 +861,10 @@ class HipBackend:
         if h.exact_scores:
             self._rescore(corpus, queries, metric, id_offset, keys)
         if n_pair:
-            self._c("lvs_resolve_pairs", _ptr(corpus.rows), corpus.mode, _ptr(queries.rows), queries.mode, corpus.d, metric,
-                    _ptr(corpus.norms), _ptr(queries.norms), int(id_offset), _ptr(pair_idx), _ptr(h.counts), n_pair, _ptr(keys),
-                    _ptr(h.keys2), self._stream())
+            self._call("lvs_resolve_pairs", xb=_ptr(corpus.rows), xb_pack=corpus.mode, xq=_ptr(queries.rows), xq_pack=queries.mode,
+                    d=corpus.d, metric=metric, xb_norms_sq=_ptr(corpus.norms), xq_norms_sq=_ptr(queries.norms),
+                    id_offset=int(id_offset), pair_idx=_ptr(pair_idx), pair_count=_ptr(h.counts), capacity=n_pair, keys=_ptr(keys),
+                    keys2=_ptr(h.keys2), stream=self._stream())
             if bounds is not None:
                 bounds.fix(approx_pair, keys[psel].contiguous(), queries.norms[psel].contiguous(), psel)
         if n_open:
@@ -893,7 +913,8 @@ class HipBackend:
         k, d = int(c_new.shape[0]), int(c_new.shape[1])
         delta = torch.empty((k,), dtype=torch.float32, device=self.device)
         top2 = torch.empty((3,), dtype=torch.float32, device=self.device)
-        self._c("lvs_kmeans_centroid_shift", _ptr(c_old), _ptr(c_new), k, d, _ptr(delta), _ptr(top2), self._stream())
+        self._call("lvs_kmeans_centroid_shift", c_old=_ptr(c_old), c_new=_ptr(c_new), k=k, d=d, out_delta=_ptr(delta),
+                out_top2=_ptr(top2), stream=self._stream())
         return delta, top2
 
     def kmeans_bounds_step(self, assign, ub, lb, delta, top2):
@@ -902,8 +923,8 @@ class HipBackend:
         n = int(assign.numel())
         idx = torch.empty((n,), dtype=torch.int64, device=self.device)
         cnt = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("lvs_kmeans_bounds_step", _ptr(assign), _ptr(ub), _ptr(lb), _ptr(delta), _ptr(top2), n, _ptr(idx), _ptr(cnt),
-                self._stream())
+        self._call("lvs_kmeans_bounds_step", assign=_ptr(assign), ub=_ptr(ub), lb=_ptr(lb), delta=_ptr(delta), top2=_ptr(top2), n=n,
+                out_idx=_ptr(idx), out_count=_ptr(cnt), stream=self._stream())
         return idx[:int(cnt.item())]
 
     def search_sharded(self, shard: PackedRows, queries: PackedRows, k: int, metric: int, id_offset: int, world: int,
@@ -919,7 +940,6 @@ class HipBackend:
         if shard.d != queries.d:
             raise ValueError("corpus / query dimension mismatch")
         errors = []
-        FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
 
         def transport(_ctx, send, recv, nbytes, _stream):
             try:  # the library's stream is torch's current stream (self._stream()): torch work queued here stays in order
@@ -931,21 +951,23 @@ class HipBackend:
                 errors.append(e)
                 return _capi.EDEVICE
 
-        cb = FN(transport)
+        cb = _capi.CALLBACKS["lvs_all_gather_fn"](transport)
         need = int(self.lib.lvs_search_sharded_workspace_bytes(world, nq, shard.n, shard.d, k, shard.mode, queries.mode,
                                                                int(seed_tiles)))
         if need < 0:
             raise LotusHipError("lvs_search_sharded_workspace_bytes rejected the shape")
         ws = self._workspace(need)
         keys = torch.zeros((nq, k), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            st = self.lib.lvs_search_sharded(ctypes.cast(cb, ctypes.c_void_p), None, world, _ptr(shard.rows) if shard.n else None,
-                                             shard.mode, shard.n, _ptr(queries.rows), queries.mode, nq, shard.d, metric, k,
-                                             _ptr(shard.norms) if shard.n else None, _ptr(queries.norms), int(id_offset),
-                                             int(seed_tiles), _ptr(keys), _ptr(ws), int(ws.numel()), self._stream())
-        if errors:
-            raise errors[0]
-        _capi.check(st, "lvs_search_sharded")
+        try:
+            self._call("lvs_search_sharded", all_gather=ctypes.cast(cb, ctypes.c_void_p), all_gather_ctx=None, nranks=world,
+                    xb=_ptr(shard.rows) if shard.n else None, xb_pack=shard.mode, nb_local=shard.n, xq=_ptr(queries.rows),
+                    xq_pack=queries.mode, nq=nq, d=shard.d, metric=metric, k=k, xb_norms_sq=_ptr(shard.norms) if shard.n else None,
+                    xq_norms_sq=_ptr(queries.norms), id_offset=int(id_offset), seed_tiles=int(seed_tiles), out_keys=_ptr(keys),
+                    workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream())
+        except LotusHipError:  # the library hands back the status its all-gather returned: what the callback raised is the cause
+            if errors:
+                raise errors[0]
+            raise
         return keys
 
     # ---- IVF-Flat ----
@@ -977,8 +999,8 @@ class HipBackend:
         if need < 0:
             raise LotusHipError("lvs_ivf_build_workspace_bytes rejected the shape")
         ws = self._workspace(need)
-        self._c("lvs_ivf_build_lists", _ptr(assign), n, nlist, _ptr(off), _ptr(out_rows), _ptr(ws), int(ws.numel()),
-                self._stream())
+        self._call("lvs_ivf_build_lists", assign=_ptr(assign), n=n, nlist=nlist, out_offsets=_ptr(off), out_rows=_ptr(out_rows),
+                workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream())
         return IvfLists(centroids=cpk, offsets=off, rows=out_rows, nlist=nlist, metric=metric)
 
     def ivf_fits(self, d: int, k: int, mode: int) -> bool:
@@ -1002,35 +1024,34 @@ class HipBackend:
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] list ids of the probes, best first): the exact
         top k over the rows of each query's ``nprobe`` best lists (``lvs_ivf_search_keys``); key 0 past those rows.  ``sel``
         (``row_bitmap``'s tensor): only the selected rows of those lists take part (``lvs_ivf_search_keys_sel``)."""
-        cpk = lists.centroids
-        head = (_ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets), _ptr(lists.rows), lists.nlist,
-                _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms))
-        return self._ivf_search("lvs_ivf_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe, sel, 6)
+        need = self.lib.lvs_ivf_search_workspace_bytes(queries.n, lists.nlist, nprobe, corpus.d, k, queries.mode)
+        return self._ivf_search("lvs_ivf_search", need, corpus, lists, queries, k, metric, nprobe, want_probe, sel,
+                                xb=_ptr(corpus.rows), xb_pack=corpus.mode, xb_norms_sq=_ptr(corpus.norms))
 
-    def _ivf_search(self, entry: str, ws_extra: tuple, head: tuple, corpus: PackedRows, lists: IvfLists, queries: PackedRows,
-                    k: int, metric: int, nprobe: int, want_probe: bool, sel=None, sel_at: int = 0):
-        """What the three IVF searches share: ``<entry>_keys`` with its scratch from ``<entry>_workspace_bytes``.
-        ``ws_extra``: the workspace function's arguments between d and k (PQ: M); ``head``: the entry point's arguments
-        ahead of the queries.  ``sel``: a row selector - the call goes to ``<entry>_keys_sel``, whose ``sel_bits`` follows
-        ``rows``, argument ``sel_at`` of ``head``."""
+    def _ivf_search(self, entry: str, need: int, corpus: PackedRows, lists: IvfLists, queries: PackedRows, k: int, metric: int,
+                    nprobe: int, want_probe: bool, sel=None, **mode):
+        """What the three IVF searches share: ``<entry>_keys`` on ``need`` bytes of scratch, the answer of its
+        ``<entry>_workspace_bytes``.  ``mode``: the parameters only this mode's entry declares.  ``sel``: a row selector - the
+        call goes to ``<entry>_keys_sel``, which takes it as ``sel_bits``."""
         torch = self.torch
         if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
             raise ValueError("squared L2 needs both operands packed with the same scale exponent")
-        nq = queries.n
+        nq, cpk = queries.n, lists.centroids
         keys = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         probe = torch.empty((nq, nprobe), dtype=torch.int32, device=self.device) if want_probe else None
-        need = int(getattr(self.lib, entry + "_workspace_bytes")(nq, lists.nlist, nprobe, corpus.d, *ws_extra, k, queries.mode))
         if need < 0:
-            m = f" M={ws_extra[0]}" if ws_extra else ""
+            m = f" M={mode['M']}" if "M" in mode else ""
             raise LotusHipError(f"{entry}_workspace_bytes rejected nq={nq} nlist={lists.nlist} nprobe={nprobe}{m} k={k}")
-        ws = self._workspace(need)
+        ws = self._workspace(int(need))
         name = entry + "_keys"
         if sel is not None:
             if int(sel.numel()) != -(-corpus.n // 32):
                 raise ValueError(f"the row selector has {int(sel.numel())} words for {corpus.n} rows")
-            name, head = name + "_sel", head[:sel_at] + (_ptr(sel),) + head[sel_at:]
-        self._c(name, *head, _ptr(queries.rows), queries.mode, nq, _ptr(queries.norms), corpus.d, metric, int(nprobe),
-                int(k), _ptr(keys), _ptr(probe), _ptr(ws), int(ws.numel()), self._stream())
+            name, mode["sel_bits"] = name + "_sel", _ptr(sel)
+        self._call(name, offsets=_ptr(lists.offsets), rows=_ptr(lists.rows), nb=corpus.n, nlist=lists.nlist, centroids=_ptr(cpk.rows),
+                c_pack=cpk.mode, c_norms_sq=_ptr(cpk.norms), xq=_ptr(queries.rows), xq_pack=queries.mode, nq=nq,
+                xq_norms_sq=_ptr(queries.norms), d=corpus.d, metric=metric, nprobe=int(nprobe), k=int(k), out_keys=_ptr(keys),
+                out_probe=_ptr(probe), workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream(), **mode)
         return (keys, probe) if want_probe else keys
 
     # ---- threshold search through the lists ----
@@ -1077,11 +1098,12 @@ class HipBackend:
                     oj = torch.empty((cap,), dtype=torch.int64, device=self.device)
                     os_ = torch.empty((cap,), dtype=torch.float32, device=self.device)
                 cnt.zero_()
-                self._c("lvs_ivf_range_search", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(lists.offsets),
-                        _ptr(lists.rows), _ptr(sel), lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(qs.rows),
-                        qs.mode, qs.n, _ptr(qs.norms), _ptr(q_rows[c0:c1]) if q_rows is not None else None, corpus.d, metric,
-                        int(nprobe), float(threshold), self.score_exp_of(corpus, qs), cap, _ptr(oq), _ptr(oj), _ptr(os_),
-                        _ptr(cnt), _ptr(ws), int(ws.numel()), self._stream())
+                self._call("lvs_ivf_range_search", **_operands(corpus, qs), offsets=_ptr(lists.offsets), rows=_ptr(lists.rows),
+                        sel_bits=_ptr(sel), nlist=lists.nlist, centroids=_ptr(cpk.rows), c_pack=cpk.mode, c_norms_sq=_ptr(cpk.norms),
+                        q_rows=_ptr(q_rows[c0:c1]) if q_rows is not None else None, metric=metric, nprobe=int(nprobe),
+                        threshold=float(threshold), score_exp=self.score_exp_of(corpus, qs), capacity=cap, out_q=_ptr(oq),
+                        out_j=_ptr(oj), out_s=_ptr(os_), out_count=_ptr(cnt), workspace=_ptr(ws), workspace_bytes=int(ws.numel()),
+                        stream=self._stream())
                 n = int(cnt.item())
                 if n <= cap:
                     break
@@ -1140,8 +1162,9 @@ class HipBackend:
         else:
             out = torch.empty((n, ldc), dtype=torch.uint8, device=self.device)
             rn = torch.empty((n,), dtype=torch.float32, device=self.device)
-            self._c("lvs_ivf_sq8_encode", _ptr(packed.rows), packed.mode, n, d, _ptr(lists.offsets), _ptr(lists.rows),
-                    lists.nlist, _ptr(c), _ptr(vmin), _ptr(vdiff), _ptr(out), _ptr(rn), self._stream())
+            self._call("lvs_ivf_sq8_encode", xb=_ptr(packed.rows), xb_pack=packed.mode, n=n, d=d, offsets=_ptr(lists.offsets),
+                    rows=_ptr(lists.rows), nlist=lists.nlist, centroids=_ptr(c), vmin=_ptr(vmin), vdiff=_ptr(vdiff),
+                    out_codes=_ptr(out), out_residual_norms_sq=_ptr(rn), stream=self._stream())
         return IvfSq8Lists(vmin=vmin.contiguous(), vdiff=vdiff.contiguous(), centroids=c, codes=out, rnorm=rn,
                            exp=int(packed.exp))
 
@@ -1154,10 +1177,10 @@ class HipBackend:
                        nprobe: int, want_probe: bool = False, sel=None):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
         query's ``nprobe`` best lists (``lvs_ivf_sq8_search_keys``); key 0 past those rows.  ``sel``: as ``ivf_search``."""
-        cpk = lists.centroids
-        head = (_ptr(sq8.codes), _ptr(sq8.rnorm), _ptr(sq8.vmin), _ptr(sq8.vdiff), _ptr(lists.offsets), _ptr(lists.rows), corpus.n,
-                lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(sq8.centroids))
-        return self._ivf_search("lvs_ivf_sq8_search", (), head, corpus, lists, queries, k, metric, nprobe, want_probe, sel, 6)
+        need = self.lib.lvs_ivf_sq8_search_workspace_bytes(queries.n, lists.nlist, nprobe, corpus.d, k, queries.mode)
+        return self._ivf_search("lvs_ivf_sq8_search", need, corpus, lists, queries, k, metric, nprobe, want_probe, sel,
+                                codes=_ptr(sq8.codes), residual_norms_sq=_ptr(sq8.rnorm), vmin=_ptr(sq8.vmin), vdiff=_ptr(sq8.vdiff),
+                                centroids_f32=_ptr(sq8.centroids))
 
     # ---- IVF-PQ ----
     PQ_SEED = 1234          # faiss's ClusteringParameters default, the same for every subspace
@@ -1210,8 +1233,9 @@ class HipBackend:
         else:
             out = torch.empty((n, ldc), dtype=torch.uint8, device=self.device)
             bt = torch.empty((n,), dtype=torch.float32, device=self.device)
-            self._c("lvs_ivf_pq_encode", _ptr(packed.rows), packed.mode, n, d, _ptr(lists.offsets), _ptr(lists.rows),
-                    lists.nlist, _ptr(c), M, ksub, _ptr(books), _ptr(out), _ptr(bt), self._stream())
+            self._call("lvs_ivf_pq_encode", xb=_ptr(packed.rows), xb_pack=packed.mode, n=n, d=d, offsets=_ptr(lists.offsets),
+                    rows=_ptr(lists.rows), nlist=lists.nlist, centroids=_ptr(c), M=M, ksub=ksub, codebooks=_ptr(books),
+                    out_codes=_ptr(out), out_beta=_ptr(bt), stream=self._stream())
         return IvfPqLists(M=M, ksub=ksub, codebooks=books, centroids=c, codes=out, beta=bt, exp=int(packed.exp))
 
     def ivf_pq_fits(self, d: int, M: int, k: int, mode: int) -> bool:
@@ -1223,11 +1247,10 @@ class HipBackend:
                       nprobe: int, want_probe: bool = False, sel=None):
         """-> int64 key tensor [nq, k] (and, ``want_probe``, int32 [nq, nprobe] probes): the top k of the DECODED rows of each
         query's ``nprobe`` best lists (``lvs_ivf_pq_search_keys``); key 0 past those rows.  ``sel``: as ``ivf_search``."""
-        cpk = lists.centroids
-        head = (_ptr(pq.codes), _ptr(pq.beta), _ptr(pq.codebooks), pq.M, pq.ksub, _ptr(lists.offsets), _ptr(lists.rows), corpus.n,
-                lists.nlist, _ptr(cpk.rows), cpk.mode, _ptr(cpk.norms), _ptr(pq.centroids))
-        return self._ivf_search("lvs_ivf_pq_search", (pq.M,), head, corpus, lists, queries, k, metric, nprobe, want_probe, sel,
-                                7)
+        need = self.lib.lvs_ivf_pq_search_workspace_bytes(queries.n, lists.nlist, nprobe, corpus.d, pq.M, k, queries.mode)
+        return self._ivf_search("lvs_ivf_pq_search", need, corpus, lists, queries, k, metric, nprobe, want_probe, sel,
+                                codes=_ptr(pq.codes), beta=_ptr(pq.beta), codebooks=_ptr(pq.codebooks), M=pq.M, ksub=pq.ksub,
+                                centroids_f32=_ptr(pq.centroids))
 
     # ---- exact re-ranking ("...,Refine(Flat)") ----
     REFINE_MAX_CANDIDATES = 64  # candidate slots per query of lvs_refine_keys: one per lane of the query's wave
@@ -1245,8 +1268,8 @@ class HipBackend:
             raise ValueError(f"cand_keys has {nq} rows for {queries.n} queries")
         cand = cand_keys.contiguous()
         out = torch.empty((nq, int(k)), dtype=torch.int64, device=self.device)
-        self._c("lvs_refine_keys", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(corpus.norms), _ptr(queries.rows), queries.mode,
-                nq, _ptr(queries.norms), corpus.d, metric, _ptr(cand), kc, int(k), _ptr(out), self._stream())
+        self._call("lvs_refine_keys", **_operands(corpus, queries), metric=metric, cand_keys=_ptr(cand), kc=kc, k=int(k),
+                out_keys=_ptr(out), stream=self._stream())
         return out
 
     # ---- recall measurement on resident keys ----
@@ -1261,7 +1284,8 @@ class HipBackend:
         truth, got = truth.contiguous(), got.contiguous()
         hits = torch.empty((nq,), dtype=torch.int32, device=self.device)
         first = torch.empty((nq,), dtype=torch.int32, device=self.device)
-        self._c("lvs_keys_overlap", _ptr(truth), kt, _ptr(got), kg, nq, _ptr(hits), _ptr(first), self._stream())
+        self._call("lvs_keys_overlap", truth_keys=_ptr(truth), kt=kt, got_keys=_ptr(got), kg=kg, nq=nq, out_hits=_ptr(hits),
+                out_first=_ptr(first), stream=self._stream())
         return hits, first
 
     def ivf_row_lists(self, lists: IvfLists):
@@ -1271,7 +1295,8 @@ class HipBackend:
         if cached is None:
             n = int(lists.rows.numel())
             cached = self.torch.full((n,), -1, dtype=self.torch.int32, device=self.device)
-            self._c("lvs_ivf_row_lists", _ptr(lists.offsets), _ptr(lists.rows), n, lists.nlist, _ptr(cached), self._stream())
+            self._call("lvs_ivf_row_lists", offsets=_ptr(lists.offsets), rows=_ptr(lists.rows), n=n, nlist=lists.nlist,
+                    out_row_list=_ptr(cached), stream=self._stream())
             lists.row_list = cached
         return cached
 
@@ -1286,8 +1311,8 @@ class HipBackend:
         truth, probe = truth.contiguous(), probe.contiguous()
         rank = torch.empty((nq, kt), dtype=torch.int32, device=self.device)
         hist = torch.zeros((P + 1,), dtype=torch.int64, device=self.device)
-        self._c("lvs_ivf_probe_ranks", _ptr(truth), kt, _ptr(row_list), int(row_list.numel()), _ptr(probe), P, nq, _ptr(rank),
-                _ptr(hist), self._stream())
+        self._call("lvs_ivf_probe_ranks", truth_keys=_ptr(truth), kt=kt, row_list=_ptr(row_list), n=int(row_list.numel()),
+                probe=_ptr(probe), P=P, nq=nq, out_rank=_ptr(rank), out_hist=_ptr(hist), stream=self._stream())
         return rank, hist
 
     def merge_keys(self, parts):
@@ -1295,7 +1320,7 @@ class HipBackend:
         torch = self.torch
         P, nq, k = (int(s) for s in parts.shape)
         out = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        self._c("lvs_merge_keys", _ptr(parts.contiguous()), P, nq, k, _ptr(out), self._stream())
+        self._call("lvs_merge_keys", parts=_ptr(parts.contiguous()), nparts=P, nq=nq, k=k, out_keys=_ptr(out), stream=self._stream())
         return out
 
     def keys_to_result(self, keys, metric: int, id_map=None, score_exp: int = 0):
@@ -1305,8 +1330,8 @@ class HipBackend:
         nq, k = int(keys.shape[0]), int(keys.shape[1])
         D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        self._c("lvs_keys_to_result", _ptr(keys), nq, k, metric, _ptr(id_map), int(score_exp), _ptr(D), _ptr(I),
-                self._stream())
+        self._call("lvs_keys_to_result", keys=_ptr(keys), nq=nq, k=k, metric=metric, id_map=_ptr(id_map), score_exp=int(score_exp),
+                out_D=_ptr(D), out_I=_ptr(I), stream=self._stream())
         return D, I
 
     @staticmethod
@@ -1318,9 +1343,8 @@ class HipBackend:
         out = torch.empty((queries.n, corpus.n), dtype=torch.float32, device=self.device)
         if metric == _capi.METRIC_L2 and corpus.exp != queries.exp:
             raise ValueError("squared L2 needs both operands packed with the same scale exponent")
-        self._c("lvs_scores", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(queries.rows), queries.mode, queries.n,
-                corpus.d, metric, _ptr(corpus.norms), _ptr(queries.norms), self.score_exp_of(corpus, queries), _ptr(out),
-                corpus.n, self._stream())
+        self._call("lvs_scores", **_operands(corpus, queries), metric=metric, score_exp=self.score_exp_of(corpus, queries),
+                out=_ptr(out), ld_out=corpus.n, stream=self._stream())
         return out
 
     def rank_scores(self, sc, id_offset: int = 0):
@@ -1338,8 +1362,8 @@ class HipBackend:
             if need < 0:
                 raise LotusHipError("lvs_sort_rows_workspace_bytes rejected the shape")
             ws = self._workspace(need)
-            self._c("lvs_sort_rows_desc", _ptr(sc[q0:q1]), q1 - q0, nb, int(sc.stride(0)), int(id_offset),
-                    _ptr(keys[q0:q1]), _ptr(ws), int(ws.numel()), self._stream())
+            self._call("lvs_sort_rows_desc", scores=_ptr(sc[q0:q1]), nq=q1 - q0, nb=nb, ld=int(sc.stride(0)), id_offset=int(id_offset),
+                    out_keys=_ptr(keys[q0:q1]), workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream())
         return keys
 
     def rank_all(self, corpus: PackedRows, queries: PackedRows, metric: int, id_offset: int = 0):
@@ -1390,11 +1414,11 @@ class HipBackend:
                     oj = torch.empty((cap,), dtype=torch.int64, device=self.device)
                     os_ = torch.empty((cap,), dtype=torch.float32, device=self.device)
                 cnt.zero_()
-                self._c("lvs_range_join", _ptr(corpus.rows), corpus.mode, corpus.n, _ptr(qs.rows), qs.mode, qs.n,
-                        corpus.d, metric, _ptr(corpus.norms), _ptr(qs.norms), float(threshold),
-                        self.score_exp_of(corpus, qs), int(q_row0 + c0) if q_row0 >= 0 else -1, int(id_offset),
-                        1 if deal_chunks else int(stride), 0 if deal_chunks else int(phase), int(cap),
-                        _ptr(oq), _ptr(oj), _ptr(os_), _ptr(cnt), self._stream())
+                self._call("lvs_range_join", **_operands(corpus, qs), metric=metric, threshold=float(threshold),
+                        score_exp=self.score_exp_of(corpus, qs), q_row0=int(q_row0 + c0) if q_row0 >= 0 else -1,
+                        id_offset=int(id_offset), qt_stride=1 if deal_chunks else int(stride),
+                        qt_phase=0 if deal_chunks else int(phase), capacity=int(cap), out_q=_ptr(oq), out_j=_ptr(oj),
+                        out_s=_ptr(os_), out_count=_ptr(cnt), stream=self._stream())
                 n = int(cnt.item())
                 if n <= cap:
                     break
@@ -1414,8 +1438,8 @@ class HipBackend:
         counts = torch.zeros((k,), dtype=torch.float32, device=self.device)
         need = int(self.lib.lvs_kmeans_accumulate_workspace_bytes(x.n, k))
         ws = self._workspace(need)
-        self._c("lvs_kmeans_accumulate", _ptr(x.rows), x.n, x.d, x.mode, _ptr(assign), k, _ptr(sums), _ptr(counts),
-                _ptr(ws), int(ws.numel()), self._stream())
+        self._call("lvs_kmeans_accumulate", x=_ptr(x.rows), n=x.n, d=x.d, pack_mode=x.mode, assign=_ptr(assign), k=k, sums=_ptr(sums),
+                counts=_ptr(counts), workspace=_ptr(ws), workspace_bytes=int(ws.numel()), stream=self._stream())
         return sums, counts
 
     def kmeans_accumulate_keys(self, x: PackedRows, keys, k: int, id_offset: int = 0):
@@ -1434,8 +1458,9 @@ class HipBackend:
         ws = workspace if workspace is not None else self._workspace(need)
         if int(ws.numel()) < need:
             raise ValueError("workspace too small")
-        self._c("lvs_kmeans_accumulate_keys", _ptr(x.rows), x.n, x.d, x.mode, _ptr(keys), int(id_offset), k, _ptr(sums),
-                _ptr(counts), _ptr(ws), int(ws.numel()), self._stream())
+        self._call("lvs_kmeans_accumulate_keys", x=_ptr(x.rows), n=x.n, d=x.d, pack_mode=x.mode, keys=_ptr(keys),
+                id_offset=int(id_offset), k=k, sums=_ptr(sums), counts=_ptr(counts), workspace=_ptr(ws),
+                workspace_bytes=int(ws.numel()), stream=self._stream())
 
     def kmeans_objective(self, centroids, sums, counts, x2, out) -> None:
         """out[0] (device float64) = x2[0] - 2 sum_j <c_j, S_j> + sum_j n_j |c_j|^2: faiss's objective of the iteration
@@ -1444,8 +1469,9 @@ class HipBackend:
         need = int(self.lib.lvs_kmeans_objective_workspace_bytes(k))
         if getattr(self, "_obj_ws", None) is None or self._obj_ws.numel() < need:
             self._obj_ws = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
-        self._c("lvs_kmeans_objective", _ptr(centroids), _ptr(sums), _ptr(counts), k, d, _ptr(x2), _ptr(out),
-                _ptr(self._obj_ws), int(self._obj_ws.numel()), self._stream())
+        self._call("lvs_kmeans_objective", centroids=_ptr(centroids), sums=_ptr(sums), counts=_ptr(counts), k=k, d=d,
+                x_norms_sq_sum=_ptr(x2), out_obj=_ptr(out), workspace=_ptr(self._obj_ws),
+                workspace_bytes=int(self._obj_ws.numel()), stream=self._stream())
 
     def _centroid_image(self, centroids, mode: int, exp: int):
         """-> (PackedRows for the image of ``centroids`` [k,d], float32 [2] for its statistics), both still to be written."""
@@ -1460,8 +1486,8 @@ class HipBackend:
         """-> (PackedRows of the centroids, device float32 [2] = (largest |c|^2, largest |lo part|^2)).  ``centroids`` are
         in the points' scaled domain already (``exp``: the points' pack exponent, recorded on the result)."""
         pk, cstats = self._centroid_image(centroids, mode, exp)
-        self._c("lvs_kmeans_pack_centroids", _ptr(centroids), pk.n, pk.d, mode, _ptr(pk.rows), _ptr(pk.norms), _ptr(cstats),
-                self._stream())
+        self._call("lvs_kmeans_pack_centroids", centroids=_ptr(centroids), k=pk.n, d=pk.d, pack_mode=mode, packed_out=_ptr(pk.rows),
+                norms_out=_ptr(pk.norms), stats_out=_ptr(cstats), stream=self._stream())
         return pk, cstats
 
     def kmeans_finish(self, sums, counts, centroids, n_train: int, mode: int, nsplit_out=None, exp: int = 0):
@@ -1469,8 +1495,9 @@ class HipBackend:
         [k,d], in place) = sums / counts where counts > 0 (compute_centroids), faiss's empty-cluster split on the device
         (``nsplit_out``: device int32 [1]), and the repacked centroids -> (PackedRows, stats) as ``kmeans_pack_centroids``."""
         pk, cstats = self._centroid_image(centroids, mode, exp)
-        self._c("lvs_kmeans_update_centroids", _ptr(sums), _ptr(counts), pk.n, pk.d, int(n_train), _ptr(centroids),
-                _ptr(nsplit_out), mode, _ptr(pk.rows), _ptr(pk.norms), _ptr(cstats), self._stream())
+        self._call("lvs_kmeans_update_centroids", sums=_ptr(sums), counts=_ptr(counts), k=pk.n, d=pk.d, n_train=int(n_train),
+                centroids=_ptr(centroids), out_nsplit=_ptr(nsplit_out), pack_mode=mode, packed_out=_ptr(pk.rows),
+                norms_out=_ptr(pk.norms), stats_out=_ptr(cstats), stream=self._stream())
         return pk, cstats
 
     def kmeans_iteration(self, x: PackedRows, x2, k: int, n_train_total: int, centroids, cpk: PackedRows, cstats, keys_out,
@@ -1488,8 +1515,6 @@ class HipBackend:
         ws = self._workspace(need)
         cb, errors = None, []
         if all_reduce is not None:
-            FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p)
-
             def transport(_ctx, buf, count, dtype, _stream):
                 try:  # the library's stream is torch's current stream: torch work queued here stays in order
                     dt, size = (torch.float32, 4) if dtype == 0 else (torch.float64, 8)
@@ -1499,14 +1524,16 @@ class HipBackend:
                     errors.append(e)
                     return _capi.EDEVICE
 
-            fn = FN(transport)
+            fn = _capi.CALLBACKS["lvs_all_reduce_fn"](transport)
             cb = ctypes.cast(fn, ctypes.c_void_p)
         host_counts = (ctypes.c_int64 * 2)()
         try:
-            self._c("lvs_kmeans_iteration", cb, None, _ptr(x.rows), x.mode, x.n, x.d, _ptr(x.norms), _ptr(x2),
-                    int(x.exp) + int(cpk.exp), int(k), int(n_train_total), _ptr(centroids), cpk.mode, _ptr(cpk.rows), _ptr(cpk.norms),
-                    _ptr(cstats), _ptr(keys_out), _ptr(obj_out), _ptr(nsplit_out), ctypes.addressof(host_counts), _ptr(ws),
-                    int(ws.numel()), self._stream())
+            self._call("lvs_kmeans_iteration", all_reduce=cb, all_reduce_ctx=None, x=_ptr(x.rows), x_pack=x.mode, n=x.n, d=x.d,
+                    x_norms_sq=_ptr(x.norms), x_norms_sq_sum=_ptr(x2), exp_sum=int(x.exp) + int(cpk.exp), k=int(k),
+                    n_train_total=int(n_train_total), centroids=_ptr(centroids), c_pack=cpk.mode, c_packed=_ptr(cpk.rows),
+                    c_norms=_ptr(cpk.norms), c_stats=_ptr(cstats), out_keys=_ptr(keys_out), out_obj=_ptr(obj_out),
+                    out_nsplit=_ptr(nsplit_out), out_host_counts=ctypes.addressof(host_counts), workspace=_ptr(ws),
+                    workspace_bytes=int(ws.numel()), stream=self._stream())
         except LotusHipError:
             if errors:
                 raise errors[0]
@@ -1518,8 +1545,8 @@ class HipBackend:
         """centroids (device float32 [k,d], in place) = sums / counts where counts > 0 (faiss compute_centroids) - the
         division alone, for callers that split empty clusters on the host (``split_clusters``)."""
         k, d = int(centroids.shape[0]), int(centroids.shape[1])
-        self._c("lvs_kmeans_update_centroids", _ptr(sums), _ptr(counts), k, d, 0, _ptr(centroids), None, 0, None, None,
-                None, self._stream())
+        self._call("lvs_kmeans_update_centroids", sums=_ptr(sums), counts=_ptr(counts), k=k, d=d, n_train=0, centroids=_ptr(centroids),
+                out_nsplit=None, pack_mode=0, packed_out=None, norms_out=None, stats_out=None, stream=self._stream())
 
     def rand_perm(self, n: int, seed: int, m: int | None = None) -> np.ndarray:
         """faiss ``rand_perm(n, seed)``; with ``m`` only its first ``m`` entries (O(m) host time instead of O(n))."""

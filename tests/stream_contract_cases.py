@@ -54,10 +54,3 @@ EXCLUDED = {
     "lvs_search_sharded_rccl": "needs a communicator",
     "lvs_kmeans_iteration_rccl": "needs a communicator (and synchronises by contract)",
 }
-
-
-def declared_functions(header_text):
-    """The names of every function include/lotus_hip.h declares."""
-    import re
-
-    return set(re.findall(r"^(?:int32_t|int64_t|const char\*) (lvs_\w+)\(", header_text, re.M))

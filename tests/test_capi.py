@@ -1,8 +1,14 @@
 """The C-ABI library builds for gfx950 without a GPU, loads, and exports exactly what include/lotus_hip.h declares.
 No compute call is made here."""
+import ast
+import contextlib
 import ctypes
+import glob
 import os
 import subprocess
+import types
+
+import pytest
 
 from lotus_amd import _capi
 
@@ -11,9 +17,219 @@ def test_library_exports_every_declared_symbol():
     lib = _capi.load()
     declared = _capi.declared_symbols()
     assert len(declared) >= 14
-    assert set(declared) == set(_capi.SIGNATURES), "ctypes table and header out of sync"
+    assert set(declared) == set(_capi.SIGNATURES) == set(_capi.PROTOTYPES), "ctypes table and header out of sync"
     for name in declared:
         assert hasattr(lib, name), name
+        assert (getattr(lib, name).restype, list(getattr(lib, name).argtypes)) == _capi.SIGNATURES[name], name
+
+
+# ---- the header is the table: its parser, on the real header and on small ones ------------------------------------------------
+I32, I64, F32, F64, VP = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
+# the header's whole vocabulary of parameter types: four scalars, pointers to nine base types, the two callback typedefs
+PARAMETER_TYPES = ({"int32_t", "int64_t", "float", "double", "lvs_all_gather_fn", "lvs_all_reduce_fn"}
+                   | {const + base + "*" for const in ("", "const ")
+                      for base in ("void", "char", "float", "double", "int32_t", "int64_t", "uint8_t", "uint32_t", "uint64_t")})
+
+
+def test_the_header_parses_to_83_prototypes_and_2_callbacks():
+    protos = _capi.PROTOTYPES
+    assert len(protos) == 83 and sorted(_capi.CALLBACKS) == ["lvs_all_gather_fn", "lvs_all_reduce_fn"]
+    spelled = {t for p in protos.values() for t in p.types}
+    assert spelled <= PARAMETER_TYPES and len(spelled) == 22, spelled - PARAMETER_TYPES
+    for name, p in protos.items():
+        assert len(p.argtypes) == len(p.names) == len(p.types) and len(set(p.names)) == len(p.names), name
+        for ctype, spelling in zip(p.argtypes, p.types):  # scalars keep their width, everything else is an address
+            assert ctype is {"int32_t": I32, "int64_t": I64, "float": F32, "double": F64}.get(spelling, VP), (name, spelling)
+        assert _capi.SIGNATURES[name] == (p.restype, list(p.argtypes))
+    assert {p.restype for p in protos.values()} == {I32, I64, ctypes.c_char_p}
+    assert all((p.restype is I64) == name.endswith("_workspace_bytes") for name, p in protos.items() if name != "lvs_last_error")
+
+
+def test_the_entries_where_a_wrong_type_would_hurt_most():
+    protos = _capi.PROTOTYPES
+    p = protos["lvs_ivf_range_search"]
+    assert len(p.names) == 29
+    assert [n for n, t in zip(p.names, p.argtypes) if t is F32] == ["threshold"]
+    assert [n for n, t in zip(p.names, p.argtypes) if t is I64] == ["nb", "nq", "capacity", "workspace_bytes"]
+    p = protos["lvs_flat_search_keys_hi_banded"]
+    at = p.names.index("kc")
+    assert p.names[at:at + 3] == ("kc", "band_scale", "band_slack") and p.argtypes[at:at + 3] == (I32, F32, F32)
+    assert [n for n, t in zip(p.names, p.argtypes) if t is F32] == ["band_scale", "band_slack"]
+    p = protos["lvs_search_sharded"]
+    assert (p.names[0], p.types[0], p.argtypes[0]) == ("all_gather", "lvs_all_gather_fn", VP)
+    assert protos["lvs_kmeans_iteration"].types[0] == "lvs_all_reduce_fn"
+    assert protos["lvs_last_error"] == _capi.Prototype(ctypes.c_char_p, (), (), ())
+    assert protos["lvs_flat_search_keys"].names == (
+        "xb", "xb_pack", "nb", "xq", "xq_pack", "nq", "d", "metric", "k", "xb_norms_sq", "xq_norms_sq", "id_offset", "row_ids",
+        "out_keys", "workspace", "workspace_bytes", "stream")
+    assert protos["lvs_flat_search_keys"].argtypes == (VP, I32, I64, VP, I32, I64, I32, I32, I32, VP, VP, I64, VP, VP, VP, I64, VP)
+
+
+def test_parser_on_small_headers():
+    protos, callbacks, defines = _capi.parse_header("""
+        /* lvs_x(int32_t a); in a comment declares nothing */
+        // nor does lvs_y(int32_t a); here
+        #ifndef H
+        #define H
+        #define LVS_SEVEN 7 /* a comment
+                               over two lines */
+        #define LVS_MINUS (-3)
+        extern "C" {
+        typedef int32_t (*lvs_cb_fn)(void* ctx, int64_t n);
+        int64_t
+        lvs_split(const void* a,   /* a comment between parameters */
+                  int64_t n, float
+                  scale, lvs_cb_fn cb);
+        const char* lvs_nothing(void);
+        int32_t lvs_empty();
+        }
+        #endif
+    """)
+    assert defines == {"LVS_SEVEN": 7, "LVS_MINUS": -3}
+    assert list(protos) == ["lvs_split", "lvs_nothing", "lvs_empty"]
+    assert protos["lvs_split"] == _capi.Prototype(I64, (VP, I64, F32, VP), ("a", "n", "scale", "cb"),
+                                                  ("const void*", "int64_t", "float", "lvs_cb_fn"))
+    assert protos["lvs_nothing"] == _capi.Prototype(ctypes.c_char_p, (), (), ()) and protos["lvs_empty"].names == ()
+    assert list(callbacks) == ["lvs_cb_fn"]
+    assert (callbacks["lvs_cb_fn"]._restype_, callbacks["lvs_cb_fn"]._argtypes_) == (I32, (VP, I64))
+    for bad, names in [("int32_t lvs_sized(size_t n);", ("lvs_sized", "size_t n")),          # a type outside the vocabulary
+                       ("int32_t lvs_unnamed(int32_t);", ("lvs_unnamed", "int32_t")),        # no parameter name
+                       ("int32_t lvs_deep(float** rows);", ("lvs_deep", "float** rows")),
+                       ("int32_t lvs_later(lvs_late_fn cb);", ("lvs_later", "lvs_late_fn")),   # a callback type nobody declared
+                       ("int32_t lvs_twice(int32_t a, float a);", ("lvs_twice",)),
+                       ("float lvs_ret(int32_t a);", ("lvs_ret", "float")),
+                       ("struct lvs_s { int a; };", ("struct",))]:
+        with pytest.raises(ValueError) as e:
+            _capi.parse_header(bad)
+        assert all(n in str(e.value) for n in names), (bad, str(e.value))
+
+
+# ---- the binder, against a stub in place of the library ------------------------------------------------------------------------
+class _StubLib:
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        return lambda *args: self.calls.append((name, args)) or 0
+
+
+def _stub_backend():
+    from lotus_amd.backend import HipBackend
+
+    be = object.__new__(HipBackend)
+    be.lib, be.device = _StubLib(), None
+    be.torch = types.SimpleNamespace(cuda=types.SimpleNamespace(device=lambda dev: contextlib.nullcontext()))
+    return be
+
+
+def test_binder_orders_keywords_as_the_header_does():
+    be = _stub_backend()
+    # lvs_merge_keys(parts, nparts, nq, k, out_keys, stream)
+    be._c("lvs_merge_keys", stream=6, k=4, out_keys=5, nq=3, parts=1, nparts=2)
+    be._c("lvs_merge_keys", 1, 2, 3, stream=6, out_keys=5, k=4)   # positional, then the rest by name
+    be._c("lvs_merge_keys", 1, 2, 3, 4, 5, stream=6)
+    be._c("lvs_merge_keys", 1, 2, 3, 4, 5, 6)
+    assert be.lib.calls == [("lvs_merge_keys", (1, 2, 3, 4, 5, 6))] * 4
+    args = (object(), None, 2.5)
+    assert _capi.bind("lvs_merge_keys", args, {}) is args  # a positional call is handed on as it is, whatever its length
+    assert _capi.bind("lvs_abi_version", (), {}) == ()
+    # the longest entry, every argument by name in reverse order
+    names = _capi.PROTOTYPES["lvs_ivf_range_search"].names
+    assert _capi.bind("lvs_ivf_range_search", (), {n: i for i, n in reversed(list(enumerate(names)))}) == tuple(range(29))
+    for kw, complaint in [(dict(parts=1, nparts=2, nq=3, k=4, out_keys=5), "missing parameter 'stream'"),
+                          (dict(parts=1, nparts=2, nq=3, k=4, out_keys=5, stream=6, streem=6), "unknown parameter 'streem'"),
+                          (dict(parts=1, nparts=2, nq=3, k=4, out_keys=5, streem=6), "missing parameter 'stream'")]:
+        with pytest.raises(TypeError, match="lvs_merge_keys: " + complaint):
+            be._c("lvs_merge_keys", **kw)
+    with pytest.raises(TypeError, match="lvs_merge_keys: parameter 'nparts' given twice"):
+        be._c("lvs_merge_keys", 1, 2, nparts=2, nq=3, k=4, out_keys=5, stream=6)
+    with pytest.raises(TypeError, match="lvs_merge_keys: unknown parameter 'extra'"):
+        be._c("lvs_merge_keys", 1, 2, 3, 4, 5, 6, extra=7)
+    with pytest.raises(TypeError, match="lvs_abi_version: unknown parameter 'x'"):
+        be._c("lvs_abi_version", x=1)
+    assert len(be.lib.calls) == 4  # none of the refused calls reached the library
+    # the product's own calls bind in _call: a wrapper around _c (ws_guard.exact_workspace) sees positional arguments only
+    seen, plain_c = [], be._c
+    be._c = lambda name, *args: seen.append((name, args)) or plain_c(name, *args)
+    be._call("lvs_merge_keys", stream=6, k=4, out_keys=5, nq=3, parts=1, nparts=2)
+    be._call("lvs_merge_keys", 1, 2, 3, 4, stream=6, out_keys=5)
+    assert seen == be.lib.calls[4:] == [("lvs_merge_keys", (1, 2, 3, 4, 5, 6))] * 2
+    with pytest.raises(TypeError, match="lvs_merge_keys: missing parameter 'stream'"):
+        be._call("lvs_merge_keys", 1, 2, 3, 4, out_keys=5)
+    assert len(seen) == 2
+
+
+def _c_calls(tree):
+    """(entry name, call node) of every ``<anything>._c("lvs_...", ...)`` or ``._call("lvs_...", ...)`` in a module."""
+    for node in ast.walk(tree):
+        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ("_c", "_call") and node.args
+                and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str)):
+            yield node.args[0].value, node
+
+
+OPERANDS = ("xb", "xb_pack", "nb", "xb_norms_sq", "xq", "xq_pack", "nq", "xq_norms_sq", "d")  # what backend._operands names
+
+
+def test_every_call_of_the_product_names_its_entry_s_parameters():
+    """A misspelt, missing or doubled keyword in lotus_amd/*.py fails here, without a device."""
+    root = os.path.dirname(os.path.abspath(_capi.__file__))
+    seen = 0
+    for path in sorted(glob.glob(os.path.join(root, "*.py"))):
+        for entry, node in _c_calls(ast.parse(open(path).read())):
+            where = f"{os.path.basename(path)}:{node.lineno} {entry}"
+            assert entry in _capi.PROTOTYPES, where
+            names = _capi.PROTOTYPES[entry].names
+            positional, given = node.args[1:], [k.arg for k in node.keywords if k.arg is not None]
+            assert not any(isinstance(a, ast.Starred) for a in positional), where
+            splats = [k.value for k in node.keywords if k.arg is None]
+            blocks = [v for v in splats if isinstance(v, ast.Call) and getattr(v.func, "id", "") == "_operands"]
+            given += OPERANDS * len(blocks)  # the operand block goes only where the entry declares all nine
+            assert len(set(given)) == len(given) and set(given) <= set(names[len(positional):]), \
+                (where, set(given) - set(names[len(positional):]))
+            if len(blocks) == len(splats):  # no other ** splat: the call spells out every parameter
+                assert len(positional) + len(given) == len(names), (where, set(names[len(positional):]) - set(given))
+                assert len(names) < 6 or not positional, where + ": six or more arguments go by name"
+            seen += 1
+    assert seen >= 40
+
+
+def test_operand_block():
+    from lotus_amd.backend import PackedRows, _operands
+
+    t = types.SimpleNamespace(data_ptr=lambda: 64)
+    block = _operands(PackedRows(rows=t, norms=t, n=3, d=8, mode=0), PackedRows(rows=t, norms=t, n=2, d=8, mode=1))
+    assert block == dict(xb=64, xb_pack=0, nb=3, xb_norms_sq=64, xq=64, xq_pack=1, nq=2, xq_norms_sq=64, d=8)
+    assert tuple(block) == OPERANDS
+    assert len([name for name, p in _capi.PROTOTYPES.items() if set(OPERANDS) <= set(p.names)]) >= 12
+
+
+def test_constants_equal_the_header_s_defines():
+    d = _capi.DEFINES
+    for name in ("OK", "EINVAL", "ENOMEM", "EDEVICE", "EUNSUPPORTED", "DTYPE_F32", "DTYPE_F16", "METRIC_IP", "METRIC_L2", "PACK_F16",
+                 "PACK_SPLIT", "MAX_K", "NEAREST3_MAX_ROWS", "ABI_VERSION", "BUILD_TUNING", "BUILD_COUNT_EVENTS",
+                 "PACK_FLAG_NONFINITE", "PACK_FLAG_RANGE"):
+        assert getattr(_capi, name) == d["LVS_" + name], name
+    assert (_capi.EINVAL, _capi.EUNSUPPORTED, _capi.MAX_K, _capi.ABI_VERSION) == (-1, -4, 2048, 7)
+    from lotus_amd.backend import HipBackend
+
+    assert HipBackend.KERNEL_NAMES.keys() == {v for n, v in d.items() if n.startswith("LVS_KERNEL_")}
+    gather, reduce_ = _capi.CALLBACKS["lvs_all_gather_fn"], _capi.CALLBACKS["lvs_all_reduce_fn"]
+    assert (gather._restype_, gather._argtypes_) == (I32, (VP, VP, VP, I64, VP))
+    assert (reduce_._restype_, reduce_._argtypes_) == (I32, (VP, VP, I64, I32, VP))
+
+
+def test_host_out_parameters_take_byref_arrays_and_string_buffers():
+    lib = _capi.load()
+    assert _capi.device_count() >= 0
+    name, cus, hbm = ctypes.create_string_buffer(64), I32(-5), I64(-5)
+    st = lib.lvs_device_info(1 << 20, name, 64, ctypes.byref(cus), ctypes.byref(hbm))  # no such device: refused, not a TypeError
+    assert st != _capi.OK
+    tot, launches, calls, kernel = F64(-1), I64(-1), I64(-1), I32(-1)
+    assert lib.lvs_timing_read(ctypes.byref(tot), ctypes.byref(launches)) == _capi.OK and launches.value == 0
+    assert lib.lvs_timing_read_calls(ctypes.byref(tot), ctypes.byref(launches), ctypes.byref(calls), ctypes.byref(kernel)) == _capi.OK
+    assert (tot.value, launches.value, calls.value) == (0.0, 0, 0)
+    coef = (F32 * 5)()
+    assert lib.lvs_nearest_bound_coef(_capi.METRIC_L2, _capi.PACK_SPLIT, 64, 0, coef) == _capi.OK and coef[1] > 0  # an array as it is
 
 
 def test_shared_object_is_gfx950_code():

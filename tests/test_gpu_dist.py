@@ -160,7 +160,7 @@ def test_sharded_search_inside_the_library_with_a_thread_all_gather(hip_backend,
     assert W == 1 or tiles > 0
     pool = torch.empty((W, max(tiles * nq * 4, nq * k * 8)), dtype=torch.uint8, device=be.device)
     barrier = threading.Barrier(W)
-    FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
+    FN = _capi.CALLBACKS["lvs_all_gather_fn"]
     outs, errs, calls = [None] * W, [], [0] * W
 
     def rank(r):

@@ -217,7 +217,7 @@ def raw_ivf_range(be, pool, ivf, nprobe, thr, cap):
 
 def raw_sharded(be, pool, corpus, queries, k, keep):
     """World of one rank; the all-gather callback copies ``send`` to ``recv`` (kept alive in ``keep``)."""
-    FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
+    FN = _capi.CALLBACKS["lvs_all_gather_fn"]
 
     def gather(ctx, send, recv, nbytes, stream):
         try:

@@ -1,15 +1,11 @@
 """Every function of include/lotus_hip.h is captured and replayed by a case of tests/test_gpu_stream_contract.py, or is excluded
 with a reason (tests/stream_contract_cases.py).  A new entry point fails here until someone decides which it is."""
-import os
-
 from lotus_amd import _capi
-from stream_contract_cases import CASES, EXCLUDED, FLAT_ROUTES, declared_functions
-
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lotus_hip.h")
+from stream_contract_cases import CASES, EXCLUDED, FLAT_ROUTES
 
 
 def test_every_entry_point_is_captured_or_excluded_with_a_reason():
-    declared = declared_functions(open(HEADER).read())
+    declared = set(_capi.PROTOTYPES)
     assert len(declared) >= 80 and declared == set(_capi.SIGNATURES), declared ^ set(_capi.SIGNATURES)
     covered = {entry for entries in CASES.values() for entry in entries}
     assert not covered & set(EXCLUDED), covered & set(EXCLUDED)
@@ -17,16 +13,9 @@ def test_every_entry_point_is_captured_or_excluded_with_a_reason():
     reasons = ("host-only", "synchronises by contract", "needs a communicator")
     assert all(reason.startswith(reasons) for reason in EXCLUDED.values())
     # an excluded name is what its reason says: the host-only ones take no stream, the others do
-    takes_stream = {name for name in declared if _takes_stream(name)}
+    takes_stream = {name for name, p in _capi.PROTOTYPES.items() if "void* stream" in map(" ".join, zip(p.types, p.names))}
     assert {n for n, r in EXCLUDED.items() if r.startswith("host-only")} == declared - takes_stream
     assert covered == takes_stream - {"lvs_kmeans_iteration", "lvs_search_sharded_rccl", "lvs_kmeans_iteration_rccl"}
-
-
-def _takes_stream(name):
-    import re
-
-    m = re.search(rf"^(?:int32_t|int64_t|const char\*) {name}\(([^;]*)\);", open(HEADER).read(), re.M)
-    return "void* stream" in m.group(1)
 
 
 def test_one_flat_shape_per_route():
