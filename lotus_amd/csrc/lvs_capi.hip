@@ -1213,7 +1213,7 @@ static int32_t flat_search_impl(const void* xb, int32_t xb_pack, int64_t nb, con
                 "bad shape nq=%lld nb=%lld d=%d k=%d pack=%d/%d", (long long)nq, (long long)nb, d, k, xb_pack, xq_pack);
     LVS_REQUIRE(metric == LVS_METRIC_IP || metric == LVS_METRIC_L2, "bad metric %d", metric);
     LVS_REQUIRE(k <= LVS_MAX_K, "k=%d exceeds LVS_MAX_K", k);
-    LVS_REQUIRE(id_offset >= 0 && id_offset + nb < 0xFFFFFFFFll, "ids must stay below 2^32-1");
+    LVS_REQUIRE(id_offset >= 0 && id_offset + nb <= 0xFFFFFFFFll, "ids must stay below 2^32-1");  // the last id is id_offset + nb - 1
     if (nq == 0 || k == 0) return LVS_OK;
     LVS_REQUIRE(out_keys, "out_keys is NULL");
     LVS_DEVICE_GUARD(stream);
