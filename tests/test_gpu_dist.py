@@ -112,13 +112,6 @@ def test_bench_self_launches_its_ranks_and_prints_one_line(gpus, split, queries,
 
 
 # ---- the row-sharded search with its exchange steps inside the library (lvs_search_sharded / _rccl) --------------------------
-class _DevBytes:
-    """A raw device pointer as something torch.as_tensor understands."""
-
-    def __init__(self, ptr, nbytes):
-        self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-
-
 def _sharded_inputs(hip_backend, n, nq, d, seed):
     import numpy as np
 
@@ -139,13 +132,11 @@ def test_sharded_search_inside_the_library_with_a_thread_all_gather(hip_backend,
     library calls back into is a device copy through a shared pool + a thread barrier.  Uneven shards, an EMPTY shard, pooled
     sample thresholds on: every rank's merged keys equal the single-launch search of the whole corpus bit for bit (and the
     oracle's ids)."""
-    import ctypes
-    import threading
-
     import numpy as np
     import torch
 
     import oracle
+    import thread_ranks
     from lotus_amd import _capi
     from lotus_amd.backend import _ptr
 
@@ -158,57 +149,26 @@ def test_sharded_search_inside_the_library_with_a_thread_all_gather(hip_backend,
     offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     tiles = int(lib.lvs_flat_search_seed_tiles(nq, max(sizes), k))
     assert W == 1 or tiles > 0
-    pool = torch.empty((W, max(tiles * nq * 4, nq * k * 8)), dtype=torch.uint8, device=be.device)
-    barrier = threading.Barrier(W)
-    FN = _capi.CALLBACKS["lvs_all_gather_fn"]
-    outs, errs, calls = [None] * W, [], [0] * W
 
-    def rank(r):
-        try:
-            s = torch.cuda.Stream(device=be.device)
+    def rank(rk):
+        r, s = rk.r, rk.stream
+        shard = be.slice_rows(corpus, int(offs[r]), int(offs[r + 1]))
+        need = int(lib.lvs_search_sharded_workspace_bytes(W, nq, shard.n, d, k, shard.mode, queries.mode, tiles))
+        assert need > 0
+        with rk.on_stream():
+            ws = torch.empty(need, dtype=torch.uint8, device=be.device)
+            keys = torch.zeros((nq, k), dtype=torch.int64, device=be.device)
+            st = lib.lvs_search_sharded(rk.all_gather.ptr, None, W, _ptr(shard.rows) if shard.n else None,
+                                        shard.mode, shard.n, _ptr(queries.rows), queries.mode, nq, d, _capi.METRIC_IP, k,
+                                        _ptr(shard.norms) if shard.n else None, _ptr(queries.norms), int(offs[r]), tiles,
+                                        _ptr(keys), _ptr(ws), need, int(s.cuda_stream))
+        s.synchronize()
+        assert st == 0, lib.lvs_last_error()
+        return keys, rk.all_gather.calls
 
-            def all_gather(ctx, send, recv, nbytes, stream):
-                try:
-                    assert int(stream or 0) == int(s.cuda_stream)
-                    calls[r] += 1
-                    with torch.cuda.stream(s):
-                        pool[r, :nbytes].copy_(torch.as_tensor(_DevBytes(send, nbytes), device=be.device))
-                    s.synchronize()
-                    barrier.wait(timeout=120)
-                    with torch.cuda.stream(s):
-                        torch.as_tensor(_DevBytes(recv, W * nbytes), device=be.device).copy_(pool[:, :nbytes].reshape(-1))
-                    s.synchronize()
-                    barrier.wait(timeout=120)
-                    return 0
-                except Exception as e:  # noqa: BLE001 - reported through the status
-                    errs.append(repr(e))
-                    return _capi.EDEVICE
-
-            cb = FN(all_gather)
-            shard = be.slice_rows(corpus, int(offs[r]), int(offs[r + 1]))
-            need = int(lib.lvs_search_sharded_workspace_bytes(W, nq, shard.n, d, k, shard.mode, queries.mode, tiles))
-            assert need > 0
-            with torch.cuda.stream(s):
-                ws = torch.empty(need, dtype=torch.uint8, device=be.device)
-                keys = torch.zeros((nq, k), dtype=torch.int64, device=be.device)
-                st = lib.lvs_search_sharded(ctypes.cast(cb, ctypes.c_void_p), None, W, _ptr(shard.rows) if shard.n else None,
-                                            shard.mode, shard.n, _ptr(queries.rows), queries.mode, nq, d, _capi.METRIC_IP, k,
-                                            _ptr(shard.norms) if shard.n else None, _ptr(queries.norms), int(offs[r]), tiles,
-                                            _ptr(keys), _ptr(ws), need, int(s.cuda_stream))
-            s.synchronize()
-            assert st == 0, lib.lvs_last_error()
-            outs[r] = keys
-        except Exception as e:  # noqa: BLE001
-            errs.append(repr(e))
-            barrier.abort()
-
-    threads = [threading.Thread(target=rank, args=(r,)) for r in range(W)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(300)
-    assert not errs, errs
-    assert calls == [0 if W == 1 else 2] * W  # sample scores + key lists
+    res = thread_ranks.run_ranks(W, rank, be.device, pool_bytes=max(tiles * nq * 4, nq * k * 8))
+    outs = [keys for keys, _ in res]
+    assert [c for _, c in res] == [0 if W == 1 else 2] * W  # sample scores + key lists
     for r in range(W):
         assert torch.equal(outs[r], want), r
     _, I = be.keys_to_result(outs[0], _capi.METRIC_IP)
